@@ -2,7 +2,12 @@
 """Headline benchmark: complex MSamples/s demodulated (uint8 IQ -> packed bits -> preamble
 matches -> 10-byte packets with RSSI/SNR) on synthetic Davis streams, per BASELINE.json.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+measures or checks: the sustained leg (with the chip's power samples), the live HBM-traffic measurement (rocprofv3
+child runs), the verification against the reference fixtures and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step returned (packets, and the packed bits of a fixed sample of streams) as DIR/<name>.npy.
 
 One process per GPU: for N > 1 either under a launcher (torch.distributed.run sets RANK / WORLD_SIZE) or plainly as
 `python bench.py --gpus N`, which starts the N ranks itself (launch_ranks).  Streams are
@@ -18,7 +23,7 @@ inside the timed region.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (fused demod):
 algorithmic 2 B per complex sample / its mean HIP-event duration on the launch stream.
-`cpu_baseline` times the reference's algorithm (oracle/: per-block NumPy, vectorised NumPy, C port) on
+`cpu_baseline` (--full) times the reference's algorithm (oracle/: per-block NumPy, vectorised NumPy, C port) on
 this box's host cores on a bounded sample of the same streams.
 """
 from __future__ import annotations
@@ -53,15 +58,22 @@ def parse_args():
                          "(profiles/r02_clock_settle.txt); 0 switches it off")
     ap.add_argument("--streams", type=int, default=4096, help="streams per GPU")
     ap.add_argument("--blocks", type=int, default=33, help="8192-sample blocks per stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--live-traffic", type=int, default=1,
-                    help="1 (default, N = 1 only): after the timed region, measure roofline.traffic on THIS box - two child "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sustained leg, the live traffic "
+                         "measurement, the verification against the reference fixtures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--live-traffic", type=int, default=None,
+                    help="1 (default with --full, N = 1 only): after the timed region, measure roofline.traffic on THIS box - two child "
                          "runs of this script under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE: separate passes, counters "
-                         "only), ~30 s; 0 or any failure: the committed profiles/rNN_traffic.json whose kernel stamp matches")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--sustain", type=float, default=6.0,
+                         "only), ~30 s; 0 (default without --full) or any failure: the committed profiles/rNN_traffic.json whose "
+                         "kernel stamp matches")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the verification against the fixtures")
+    ap.add_argument("--sustain", type=float, default=None,
                     help="seconds of back-to-back steps after the timed region (reported separately, never `value`; "
-                         "0 = off).  Longer than a 5 s utilisation sampler's period, so that one cannot miss the GPU work")
+                         "0 = off, the default without --full; 6 with it).  Longer than a 5 s utilisation sampler's period, "
+                         "so that one cannot miss the GPU work")
     ap.add_argument("--two-streams", action="store_true", help="one HIP stream per resident batch")
     ap.add_argument("--step-times", action="store_true", help="diagnostic: print the slowest steps' host times to stderr")
     ap.add_argument("--resident", type=int, default=2,
@@ -83,7 +95,41 @@ def parse_args():
                          "falling back to gloo in the same process when its initialisation fails")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="N > 1 dry run on a one-GPU box: all ranks on cuda:0, gloo barrier (not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.sustain is None:
+        args.sustain = 6.0 if args.full else 0.0
+    if args.live_traffic is None:
+        args.live_traffic = 1 if args.full else 0
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.verify = args.full and not args.no_verify
+    return args
+
+
+DUMP_BITS_STREAMS = 64  # streams whose packed bits --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_outputs(dirpath: str, recs: np.ndarray, bd, n_streams: int) -> None:
+    """--dump-outputs: the packet records of the last timed step (one array per field, in the order results() returns
+    them: stream, call, reference order) and the packed sign bits of a fixed sample of streams, as float32/float64
+    .npy files.  Called right after the timed region, before anything else runs on the batches."""
+    os.makedirs(dirpath, exist_ok=True)
+    recs = np.array(recs)  # (results() returns a view of a buffer that the next call overwrites)
+    cap = (48 << 20) // 176  # 176 bytes per packet once written out; more packets than that: a seeded sample of them
+    if len(recs) > cap:
+        recs = recs[np.sort(np.random.default_rng(1).choice(len(recs), size=cap, replace=False))]
+    data = recs["data"].astype(np.float32)
+    data[np.arange(data.shape[1])[None, :] >= recs["nbytes"][:, None]] = 0  # bytes past nbytes carry nothing
+    out = {"packets_stream": recs["stream"].astype(np.float64), "packets_call": recs["call"].astype(np.float64),
+           "packets_index": recs["index"].astype(np.float64), "packets_nbytes": recs["nbytes"].astype(np.float64),
+           "packets_data": data, "packets_rssi": recs["rssi"].astype(np.float64),
+           "packets_snr": recs["snr"].astype(np.float64)}
+    sample = np.sort(np.random.default_rng(0).choice(n_streams, size=min(DUMP_BITS_STREAMS, n_streams), replace=False))
+    out["bits_sample_streams"] = sample.astype(np.float64)
+    out["bits_sample"] = np.stack([bd.bits(int(s)) for s in sample]).astype(np.float32)  # packed bytes, LSB first
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def cpu_baseline(uniq: np.ndarray, budget_s: float = 10.0):
@@ -243,6 +289,8 @@ def wideband(args):
     for _ in range(args.steps):
         recs = step()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, recs, bd, cz.n_channels)
     import ctypes
     hip = ctypes.CDLL("libamdhip64.so")  # (the library's own HIP runtime: already loaded)
     hip.hipDeviceSynchronize()
@@ -486,6 +534,8 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, recs, bd, n_streams)
     if step_log is not None and rank == 0:
         timed = step_log[-args.steps:]
         worst = sorted(range(len(timed)), key=lambda j: -(timed[j][0] + timed[j][1]))[:6]
@@ -559,7 +609,7 @@ def main():
 
     # ---- verification outside the timed region: packets and bit hashes against the fixtures
     verified = None
-    if not args.no_verify and n_blocks == synth.BLOCKS_PER_STREAM:
+    if args.verify and n_blocks == synth.BLOCKS_PER_STREAM:
         import hashlib
         with open(os.path.join(ROOT, "tests", "golden", "streams.json")) as fh:
             gold = json.load(fh)
@@ -685,7 +735,7 @@ def main():
         if per_gpu is not None:
             out["per_gpu"] = per_gpu
             out["dist_backend"] = dist_backend + (f" ({dist_note})" if dist_note else "")
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
+        if args.cpu_baseline and world == 1:  # reported at N = 1 only
             # the GPU figures are complete here: show them (stderr) before the CPU legs take their ~25 s; the ONE JSON
             # line on stdout follows with `cpu_baseline` in it
             print("bench.py: GPU part done, CPU baseline legs running: " + json.dumps(out), file=sys.stderr, flush=True)

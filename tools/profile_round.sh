@@ -17,11 +17,11 @@ export GPU_FORCE_BLIT_COPY_SIZE=0
 step() { echo "[profile_round] $*" | tee -a $OUT/progress.log; }
 
 step "1/9 default bench line"
-timeout -k 10 400 python3 $ROOT/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 400 python3 $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 400 $OUT/bench_default.json | tee -a $OUT/progress.log
 
 step "2/9 rocprofv3 --kernel-trace --stats of the same command"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu-baseline --live-traffic 0 > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --no-cpu-baseline --live-traffic 0 > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
 python3 $ROOT/tools/profile_collect.py stats $OUT/trace $OUT | tee -a $OUT/progress.log
 
 step "3/9 SQ counters (own run)"
@@ -61,7 +61,7 @@ timeout -k 10 200 python3 $ROOT/tools/results_cost.py > $OUT/results_cost.txt 2>
 cat $OUT/results_cost.txt | tee -a $OUT/progress.log
 
 step "8b/9 host-fed leg and the one-launch tail's phase stamps"
-timeout -k 10 300 python3 $ROOT/bench.py --no-cpu-baseline --live-traffic 0 --sustain 0 --host-fed > $OUT/host_fed.json 2> $OUT/host_fed.err
+timeout -k 10 300 python3 $ROOT/bench.py --full --no-cpu-baseline --live-traffic 0 --sustain 0 --host-fed > $OUT/host_fed.json 2> $OUT/host_fed.err
 tail -c 500 $OUT/host_fed.json | tee -a $OUT/progress.log
 RTLDAVIS_HIP_LIB=$ROOT/rtldavis_amd/librtldavis_hip_diag.so RD_FT_STAMPS=1 timeout -k 10 300 python3 $ROOT/tools/tail_stamps.py > $OUT/tail_stamps.txt 2>&1
 cat $OUT/tail_stamps.txt | tee -a $OUT/progress.log
@@ -69,6 +69,6 @@ RTLDAVIS_HIP_LIB=$ROOT/rtldavis_amd/librtldavis_hip_diag.so RD_SB_STAMPS=1 timeo
 cat $OUT/stream_stamps.txt | tee -a $OUT/progress.log
 
 step "9/9 N = 2 rehearsal on one GPU (code path only, not a measurement)"
-timeout -k 10 400 python3 $ROOT/bench.py --gpus 2 --steps 6 --warmup 2 --rehearse-shared-gpu --streams 1024 --sustain 0 > $OUT/rehearse_shared_gpu.txt 2>&1
+timeout -k 10 400 python3 $ROOT/bench.py --full --gpus 2 --steps 6 --warmup 2 --rehearse-shared-gpu --streams 1024 --sustain 0 > $OUT/rehearse_shared_gpu.txt 2>&1
 tail -c 600 $OUT/rehearse_shared_gpu.txt | tee -a $OUT/progress.log
 step "done"
