@@ -297,6 +297,39 @@ int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_stream_strid
 int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, size_t nbytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * Wideband receiver (rtldavis_amd/csrc/rd_wideband.hip): one capture that never ends, fed in
+ * chunks of decim * block_size wideband samples, channelized into every channel and demodulated
+ * with the state of both carried across chunks.  Owns one rd_chan configuration and one
+ * multi-stream rd_demod with n_streams = n_channels.  For any capture split into chunks, the
+ * channelized bytes equal rd_chan_run on the whole capture, byte for byte.  Parity: unpinned, as
+ * for the channelizer.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rd_wideband rd_wideband;
+/* no device work (safe before fork), like rd_create / rd_chan_create; block_size % 128 == 0 */
+int rd_wideband_create(const rd_config *cfg, const rd_chan_config *ccfg, const double *taps,
+                       const int64_t *shift_hz, rd_wideband **out);
+void rd_wideband_destroy(rd_wideband *w);
+/* clock to 0, history to zero, demod state as rd_reset (waits for the chunks in flight) */
+int rd_wideband_reset(rd_wideband *w);
+/* one chunk: uint8 I,Q of decim * block_size wideband samples (else RD_ERR_ARG "Incompatible array
+ * sizes"); host->device copy, channelize (streaming form), one demod launch - all queued on the
+ * handle's own non-blocking streams, returns at once.  At most two chunks in flight (a third:
+ * RD_ERR_STATE); the copy of chunk k+1 overlaps chunk k's kernels.  The clock and the history
+ * advance here, so a fetch that times out loses only that chunk's packets. */
+int rd_wideband_submit(rd_wideband *w, const uint8_t *wide_iq, size_t nbytes);
+/* as rd_demod_fetch / rd_demod_refetch: packets of the oldest chunk in flight, stream = channel, call = chunk */
+int rd_wideband_fetch(rd_wideband *w, rd_packet *out, int cap, int *n);
+int rd_wideband_refetch(rd_wideband *w, rd_packet *out, int cap, int *n);
+/* chunks in flight whose packets can still be fetched */
+int rd_wideband_inflight(rd_wideband *w);
+/* the channelized bytes uint8 [n_channels][2 * block_size] of the chunk the last fetch returned (valid until
+ * the next submit), and one channel's discriminator output as rd_copy_discriminated_stream */
+int rd_wideband_copy_channelized(rd_wideband *w, uint8_t *out, size_t nbytes);
+int rd_wideband_copy_discriminated(rd_wideband *w, int channel, double *out, size_t n);
+/* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
+int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Test hooks of the fused demod kernel (rtldavis_amd/csrc/rd_demod_mfma.hip).  Not part of the
  * drop-in surface: tests/test_mfma_model.py and tests/test_gpu_mfma.py use them to check the tap
  * matrix and the raw matrix-pipe outputs against an integer model.

@@ -1,9 +1,11 @@
 """rtldavis_amd - MI355X (gfx950) implementation of rtldavis's IQ -> bits -> packets path.
 
 ``rtldavis_amd.dsp`` mirrors ``rtldavis.dsp`` (drop-in for protocol.Parser / worker);
-``rtldavis_amd.batch.BatchDemodulator`` demodulates many independent streams per launch.
+``rtldavis_amd.batch.BatchDemodulator`` demodulates many independent streams per launch;
+``rtldavis_amd.WidebandReceiver`` (``rtldavis_amd.wideband``) channelizes and demodulates a live wideband
+capture chunk by chunk.
 """
-__all__ = ["dsp", "batch", "synth"]
+__all__ = ["dsp", "batch", "synth", "wideband", "WidebandReceiver"]
 
 import os as _os
 
@@ -29,3 +31,11 @@ if "GPU_FORCE_BLIT_COPY_SIZE" not in _os.environ:
                        "effect: device-to-host copies of the packet records will run as blit kernels beside the demod "
                        "kernel (about 10 % less batch throughput).  Import rtldavis_amd first, or export "
                        "GPU_FORCE_BLIT_COPY_SIZE=0 in the environment.", RuntimeWarning, stacklevel=2)
+
+
+def __getattr__(name):
+    # (lazy: importing the package loads no submodule, so the environment above is set before anything else runs)
+    if name == "WidebandReceiver":
+        from .wideband import WidebandReceiver
+        return WidebandReceiver
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

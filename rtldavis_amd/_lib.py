@@ -100,6 +100,16 @@ SIGNATURES = {
     "rd_chan_input_ptr": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "rd_chan_run": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "rd_chan_run_host": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
+    "rd_wideband_create": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), _P, _P, C.POINTER(_P)]),
+    "rd_wideband_destroy": (None, [_P]),
+    "rd_wideband_reset": (C.c_int, [_P]),
+    "rd_wideband_submit": (C.c_int, [_P, _P, C.c_size_t]),
+    "rd_wideband_fetch": (C.c_int, [_P, C.POINTER(RdPacket), C.c_int, C.POINTER(C.c_int)]),
+    "rd_wideband_refetch": (C.c_int, [_P, C.POINTER(RdPacket), C.c_int, C.POINTER(C.c_int)]),
+    "rd_wideband_inflight": (C.c_int, [_P]),
+    "rd_wideband_copy_channelized": (C.c_int, [_P, _P, C.c_size_t]),
+    "rd_wideband_copy_discriminated": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),
     "rd_debug_mfma_taps8s": (None, [_P, _P]),

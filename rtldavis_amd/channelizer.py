@@ -38,6 +38,31 @@ def design_taps(n_taps: int = 512, cutoff_hz: float = 110e3, wide_rate: float = 
     return h / h.sum()
 
 
+def plan_channels(obj, channels_hz: Sequence[int], centre_hz: int, decim: int, taps: Optional[np.ndarray], gain: float,
+                  out_rate: int, if_hz: Optional[int] = None) -> None:
+    """The channel plan shared by Channelizer and wideband.WidebandReceiver: sets out_rate, decim, wide_rate, if_hz,
+    taps (float64), gain, shift_hz (int64: the wideband frequency that lands on 0 Hz of each channel's output) and
+    n_channels on ``obj``; ValueError for a decimation or rate below 1 and for a channel outside the captured band."""
+    obj.out_rate = int(out_rate)
+    obj.decim = int(decim)
+    if obj.decim < 1 or obj.out_rate < 1:
+        raise ValueError("decim and out_rate must be positive")
+    obj.wide_rate = obj.out_rate * obj.decim
+    obj.if_hz = -obj.out_rate // 4 if if_hz is None else int(if_hz)
+    obj.taps = np.ascontiguousarray(design_taps(wide_rate=obj.wide_rate) if taps is None else taps, np.float64)
+    obj.gain = float(gain)
+    # the wideband frequency that lands on 0 Hz of the output: channel offset minus the IF
+    obj.shift_hz = np.ascontiguousarray([int(f) - int(centre_hz) - obj.if_hz for f in channels_hz], np.int64)
+    obj.n_channels = obj.shift_hz.size
+    if obj.n_channels and np.abs(obj.shift_hz).max() > obj.wide_rate // 2:
+        raise ValueError("a channel lies outside the captured band")
+
+
+def chan_config(plan) -> _lib.RdChanConfig:
+    """rd_chan_config of a plan made by plan_channels."""
+    return _lib.RdChanConfig(plan.out_rate, plan.decim, int(plan.taps.size), int(plan.n_channels), plan.gain)
+
+
 class Channelizer:
     """``Channelizer(channels_hz, centre_hz)`` moves each channel's centre to -out_rate/4, where the
     demodulator's Fs/4 rotation (dsp.py:42-49) expects the carrier, low-passes, decimates by
@@ -46,22 +71,9 @@ class Channelizer:
     def __init__(self, channels_hz: Sequence[int] = US_CHANNELS_HZ, centre_hz: int = DEFAULT_CENTRE_HZ,
                  decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0,
                  out_rate: int = OUT_RATE, if_hz: Optional[int] = None) -> None:
-        self.out_rate = int(out_rate)
-        self.decim = int(decim)
-        if self.decim < 1 or self.out_rate < 1:
-            raise ValueError("decim and out_rate must be positive")
-        self.wide_rate = self.out_rate * self.decim
-        self.if_hz = -self.out_rate // 4 if if_hz is None else int(if_hz)
-        self.taps = np.ascontiguousarray(design_taps(wide_rate=self.wide_rate) if taps is None else taps, np.float64)
-        self.gain = float(gain)
-        # the wideband frequency that lands on 0 Hz of the output: channel offset minus the IF
-        self.shift_hz = np.ascontiguousarray([int(f) - int(centre_hz) - self.if_hz for f in channels_hz], np.int64)
-        self.n_channels = self.shift_hz.size
-        if self.n_channels and np.abs(self.shift_hz).max() > self.wide_rate // 2:
-            raise ValueError("a channel lies outside the captured band")
+        plan_channels(self, channels_hz, centre_hz, decim, taps, gain, out_rate, if_hz)
         self._h = C.c_void_p()
-        cfg = _lib.RdChanConfig(self.out_rate, self.decim, int(self.taps.size), int(self.n_channels), self.gain)
-        _lib.check(_lib.lib().rd_chan_create(C.byref(cfg), self.taps.ctypes.data, self.shift_hz.ctypes.data,
+        _lib.check(_lib.lib().rd_chan_create(C.byref(chan_config(self)), self.taps.ctypes.data, self.shift_hz.ctypes.data,
                                              C.byref(self._h)))
         self.n_wide = 0
 

@@ -1265,7 +1265,9 @@ static int demod_enter_cplx(rd_demod *h) {
 // copy to the device on the copy stream, everything else behind it on the compute stream.  Returns at
 // once; at most two blocks may be in flight.
 // `ext_off` >= 0: the block lies at that offset of the registered producer buffer (no copy: the kernels read it there)
-static int demod_submit(rd_demod *h, const void *samples, int is_complex, long ext_off = -1) {
+// `dev_block`: the block lies in device memory, written by work queued on h->st before this call (rd_demod_submit_device)
+static int demod_submit(rd_demod *h, const void *samples, int is_complex, long ext_off = -1,
+                        const uint8_t *dev_block = nullptr) {
     const size_t B = (size_t)h->dc.B, L = (size_t)h->dc.L, NS = (size_t)h->NS;
     const size_t bw = (B + 31) / 32, lw = (L + 31) / 32;
     int rc = demod_alloc(h);
@@ -1278,7 +1280,9 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
     const uint8_t *in_host = sl.h_in, *in_dev = sl.d_in_map;   // where this block's bytes are, host and device address
     const bool will_one = h->one_ok && (is_complex || h->cplx_mode ? (NS == 1 && h->dc.B <= 8192) : true);
     bool pushed = false;
-    if (ext_off >= 0) {
+    if (dev_block) {
+        in_dev = dev_block;
+    } else if (ext_off >= 0) {
         in_host = h->ext_host + ext_off;
         in_dev = h->ext_dev + ext_off;
     } else if (will_one && sl.d_push) {
@@ -1354,9 +1358,13 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
         --h->seq;
     }
     if (pushed) memcpy(sl.h_in, samples, nbytes);   // (the one-launch form declined: the multi-launch form copies from the pinned slot)
-    HIPCHK(hipMemcpyAsync(sl.d_in, in_host, nbytes, hipMemcpyHostToDevice, h->st_copy));
-    HIPCHK(hipEventRecord(sl.e_in, h->st_copy));
-    HIPCHK(hipStreamWaitEvent(st, sl.e_in, 0));
+    if (dev_block) {
+        HIPCHK(hipMemcpyAsync(sl.d_in, dev_block, nbytes, hipMemcpyDeviceToDevice, st));  // (its producer ran on st)
+    } else {
+        HIPCHK(hipMemcpyAsync(sl.d_in, in_host, nbytes, hipMemcpyHostToDevice, h->st_copy));
+        HIPCHK(hipEventRecord(sl.e_in, h->st_copy));
+        HIPCHK(hipStreamWaitEvent(st, sl.e_in, 0));
+    }
     if (is_complex && !h->cplx_mode) {
         rc = demod_enter_cplx(h);
         if (rc) return rc;
@@ -1535,6 +1543,35 @@ extern "C" int rd_demod_refetch(rd_demod *h, rd_packet *out, int cap, int *n) {
 }
 
 extern "C" int rd_demod_inflight(rd_demod *h) { return h ? h->nflight : 0; }
+
+// ------------------------------------------------------------------------------------------
+// internal entry points of the wideband receiver (rd_internal.h, rd_wideband.hip)
+// ------------------------------------------------------------------------------------------
+int rd_demod_prepare(rd_demod *h, hipStream_t *st, hipStream_t *st_copy) {
+    if (!h || !st || !st_copy) return fail(RD_ERR_ARG, "null argument");
+    int rc = demod_alloc(h);
+    if (rc) return rc;
+    *st = h->st;
+    *st_copy = h->st_copy;
+    return RD_OK;
+}
+
+int rd_demod_check_room(rd_demod *h) {
+    if (!h) return fail(RD_ERR_ARG, "null handle");
+    int rc = demod_alloc(h);
+    if (rc) return rc;
+    if (h->stale && (rc = demod_drop_stale(h))) return rc;
+    if (h->nflight >= 2) return fail(RD_ERR_STATE, "two blocks in flight: fetch one first");
+    return RD_OK;
+}
+
+int rd_demod_submit_device(rd_demod *h, const uint8_t *dev_block) {
+    if (!h || !dev_block) return fail(RD_ERR_ARG, "null argument");
+    if (h->cplx_mode) return fail(RD_ERR_STATE, "handle is in complex mode: reset() first");
+    return demod_submit(h, nullptr, 0, -1, dev_block);
+}
+
+int rd_demod_pending(const rd_demod *h) { return h ? h->nflight - h->stale : 0; }
 
 static int demod_blocks(rd_demod *h, const void *samples, int is_complex, rd_packet *out, int cap, int *n) {
     int rc = demod_quiet(h);

@@ -54,9 +54,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/rtldavis_hip.h"
+#include "rd_internal.h"
 
 extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-extern int rd_ensure_device_public(void);
 
 #define RD_CHAN_TB 4                        // 32-time blocks per wave
 #define RD_CHAN_TT (32 * RD_CHAN_TB)        // output times per workgroup
@@ -112,11 +112,20 @@ __device__ __forceinline__ double rd_chan_mod(double x, double m) {
 // the staging, and the 127.4 offset of the LUT as a per-channel constant (-127.4 sum of the taps an output sees).  The
 // window starts one sample early, at n0 = D t0 - T, a multiple of 8 samples: 16-byte loads, 16-byte LDS writes and
 // 8-byte fragment reads are all aligned; the price is one more K step (the leading tap of it is zero).
+//
+// STREAM (rd_wideband.hip): `wide` is one chunk of a capture that never ends, `prev` the chunk before it (null for the
+// first chunk after create / reset: zero history, as the one-shot form stages for n < 0), and output time 0 of the launch
+// is the absolute time t_base; the kernel gets t_base mod out_rate (reduced exactly on the host) and an n_early of 0
+// unless t_base is 0.  A chunk is a whole number of workgroups (block_size % RD_CHAN_TT == 0, so n_wide and every window
+// start are multiples of 8 samples): an 8-sample vector lies wholly in `prev`, in `wide` or past the chunk, where the
+// taps are zero - the streamed bytes equal the one-shot form's on the whole capture.
+template <bool STREAM>
 __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint8_t *__restrict__ wide, long n_wide,
                                                     const uint4 *__restrict__ amat, const float2 *__restrict__ dc,
                                                     const int64_t *shifts, int T, int D, int n_ch, int n_early,
                                                     long out_rate, float gain, float tap_unscale, long n_out,
-                                                    uint8_t *out, size_t out_stride, int xs_bytes) {
+                                                    uint8_t *out, size_t out_stride, int xs_bytes,
+                                                    const uint8_t *__restrict__ prev, long t_base_mod) {
     extern __shared__ uint8_t lds[];
     uint8_t *xs = lds;                            // window samples 0 .. span-1, two bytes each (I, Q)
     const int lane = threadIdx.x & 63;
@@ -135,7 +144,10 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
             const int q = q0 + u * blockDim.x;
             const long n = n0 + 8L * q;
             v[u] = uint4{0u, 0u, 0u, 0u};
-            if (q < n_vec) {
+            if constexpr (STREAM) {
+                const uint8_t *src = n >= 0 ? wide + 2 * n : (prev ? prev + 2 * (n + n_wide) : nullptr);
+                if (q < n_vec && src && n >= -n_wide && n + 8 <= n_wide) v[u] = *(const uint4 *)src;
+            } else if (q < n_vec) {
                 if (n >= 0 && n + 8 <= n_wide) {
                     v[u] = *(const uint4 *)(wide + 2 * n);
                 } else {
@@ -220,6 +232,7 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
     const double fo = (double)out_rate, inv_fo = 1.0 / fo;
     // (t0 + r) mod Fo once per lane: a float estimate of the quotient is off by one at most
     long tm = t0 + r;
+    if constexpr (STREAM) tm += t_base_mod;
     {
         const long qe = (long)floorf((float)tm * (float)inv_fo);
         tm -= qe * out_rate;
@@ -435,12 +448,12 @@ extern "C" int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_s
     const size_t span = (size_t)(RD_CHAN_TT - 1) * D + T + RD_CHAN_KC;
     const size_t xs_bytes = (2 * span + 15 + 16) & ~(size_t)15;
     const size_t lds = xs_bytes;
-    CHK(hipFuncSetAttribute((const void *)k_channelize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CHK(hipFuncSetAttribute((const void *)k_channelize<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned gx = (unsigned)((n_out + RD_CHAN_TT - 1) / RD_CHAN_TT);
-    hipLaunchKernelGGL(k_channelize, dim3(gx, (unsigned)h->n_groups), dim3(256), lds, (hipStream_t)hip_stream, h->d_wide,
+    hipLaunchKernelGGL(k_channelize<false>, dim3(gx, (unsigned)h->n_groups), dim3(256), lds, (hipStream_t)hip_stream, h->d_wide,
                        (long)h->wide_n, (const uint4 *)h->d_amat, (const float2 *)h->d_dc, h->d_shifts, T, D,
                        h->cfg.n_channels, h->n_early, (long)h->cfg.out_rate, (float)h->cfg.gain, h->tap_unscale, (long)n_out,
-                       (uint8_t *)dst_dev, dst_stream_stride, (int)xs_bytes);
+                       (uint8_t *)dst_dev, dst_stream_stride, (int)xs_bytes, (const uint8_t *)nullptr, 0L);
     CHK(hipGetLastError());
     return RD_OK;
 }
@@ -460,3 +473,44 @@ extern "C" int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, siz
     hipFree(d);
     return rc;
 }
+
+// ------------------------------------------------------------------------------------------
+// Streaming form (rd_internal.h; used by rd_wideband.hip)
+// ------------------------------------------------------------------------------------------
+// the device tables, on the current device (no capture buffer: the caller owns its chunk buffers)
+int rd_chan_stream_prepare(rd_chan *h) {
+    if (!h) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    int rc = chan_alloc(h, 0);
+    if (rc) return rc;
+    const size_t span = (size_t)(RD_CHAN_TT - 1) * h->cfg.decim + h->t_pad + RD_CHAN_KC;
+    const size_t lds = (2 * span + 15 + 16) & ~(size_t)15;
+    CHK(hipFuncSetAttribute((const void *)k_channelize<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return RD_OK;
+}
+
+// Channelize one chunk of n_out * decim samples at `wide` (device) whose predecessor lies at `prev` (null: zero history)
+// into dst (channel c at dst + c * dst_stride); t_base = the absolute output time of the chunk's first output.
+int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, size_t n_out, uint64_t t_base, void *dst,
+                          size_t dst_stride, hipStream_t st) {
+    if (!h || !wide || !dst) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (!h->dev_ready) return rd_fail_msg(RD_ERR_STATE, "rd_chan_stream_prepare first");
+    if (n_out == 0 || n_out % RD_CHAN_TT || n_out > 0x7FFFFFFFull / (size_t)h->cfg.decim || t_base % RD_CHAN_TT ||
+        dst_stride < 2 * n_out || (dst_stride & 1))
+        return rd_fail_msg(RD_ERR_ARG, "streamed chunk: n_out and t_base must be multiples of %d", RD_CHAN_TT);
+    const int T = h->t_pad, D = h->cfg.decim;
+    const long n_wide = (long)(n_out * (size_t)D);
+    if (T > n_wide) return rd_fail_msg(RD_ERR_ARG, "the taps reach further back than one chunk");
+    const size_t span = (size_t)(RD_CHAN_TT - 1) * D + T + RD_CHAN_KC;
+    const size_t xs_bytes = (2 * span + 15 + 16) & ~(size_t)15;
+    const long t_base_mod = (long)(t_base % (uint64_t)h->cfg.out_rate);
+    const int n_early = t_base == 0 ? h->n_early : 0;   // the early DC table: absolute t < n_early only
+    const unsigned gx = (unsigned)(n_out / RD_CHAN_TT);
+    hipLaunchKernelGGL(k_channelize<true>, dim3(gx, (unsigned)h->n_groups), dim3(256), xs_bytes, st, wide, n_wide,
+                       (const uint4 *)h->d_amat, (const float2 *)h->d_dc, h->d_shifts, T, D, h->cfg.n_channels, n_early,
+                       (long)h->cfg.out_rate, (float)h->cfg.gain, h->tap_unscale, (long)n_out, (uint8_t *)dst, dst_stride,
+                       (int)xs_bytes, prev, t_base_mod);
+    CHK(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_chan_n_channels(const rd_chan *h) { return h ? h->cfg.n_channels : 0; }

@@ -185,3 +185,20 @@ void rd_launch_fir9(const double *in, double *out, size_t n_out, hipStream_t st)
 void rd_launch_discriminate(const double *in, double *out, size_t n_out, hipStream_t st);
 void rd_launch_quantize(const double *in, uint8_t *out, size_t n, hipStream_t st);
 void rd_launch_pack_bytes(const uint8_t *in01, uint32_t *words, size_t n, hipStream_t st);
+
+// --- wideband receiver (rd_wideband.hip): the streaming channelizer and a multi-stream demodulator fed from device memory ---
+// rd_channelizer.hip: device tables of the handle on the current device; one streamed chunk (n_out a multiple of 128 output
+// times, t_base its first output's absolute time, a multiple of 128; prev = the chunk before, null = zero history)
+int rd_chan_stream_prepare(rd_chan *h);
+int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, size_t n_out, uint64_t t_base, void *dst,
+                          size_t dst_stride, hipStream_t st);
+int rd_chan_n_channels(const rd_chan *h);
+// rd_api.hip: the handle's device state and its two non-blocking streams (compute, copy)
+int rd_demod_prepare(rd_demod *h, hipStream_t *st, hipStream_t *st_copy);
+// drop the blocks a timed-out fetch gave up on, then RD_ERR_STATE if two blocks are in flight
+int rd_demod_check_room(rd_demod *h);
+// rd_demod_submit for a multi-stream uint8 handle whose block ([n_streams][2 * block_size]) already lies in device
+// memory, written by work queued on the handle's compute stream
+int rd_demod_submit_device(rd_demod *h, const uint8_t *dev_block);
+// blocks in flight whose packets can still be fetched (rd_demod_inflight less those a timed-out fetch gave up on)
+int rd_demod_pending(const rd_demod *h);

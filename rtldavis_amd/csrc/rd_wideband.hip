@@ -1,0 +1,184 @@
+// rd_wideband.hip - live wideband receiver (include/rtldavis_hip.h: rd_wideband_*): a capture that never ends, fed in
+// chunks of decim x block_size samples, channelized into every hop channel and demodulated, all on the GPU.
+//
+// One handle owns one rd_chan configuration and one multi-stream rd_demod (n_streams = n_channels).  Per chunk, queued by
+// rd_wideband_submit and returning at once:
+//   copy stream:    pinned slot -> device chunk buffer (overlaps the previous chunk's kernels)
+//   compute stream: k_channelize<true> (streaming form: the previous chunk's buffer is the history, the output clock is
+//                   absolute) into a channelized buffer [n_channels][2 block_size], then the demodulator's one launch
+//                   reading that buffer where it lies (rd_demod_submit_device)
+// Two chunk buffers and two channelized buffers, indexed by the chunk's parity: chunk k reads chunk k-1's buffer as its
+// history, so the copy of chunk k+1 into that buffer waits for chunk k's channelizer (an event); chunk k's channelized
+// bytes stay valid until chunk k+2 is submitted.  At most two chunks are in flight (the demodulator's two slots).
+// The output clock is a 64-bit count kept here; the kernel gets it mod out_rate, so the mixer phase stays exact however
+// long the receiver runs.  A fetch that times out loses the chunk's packets, not the clock or the history: both advance
+// at submit.
+#include <cstring>
+#include <unistd.h>
+
+#include <hip/hip_runtime.h>
+
+#include "rd_internal.h"
+
+extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
+
+#define WCHK(x)                                                                                             \
+    do {                                                                                                    \
+        hipError_t e_ = (x);                                                                                \
+        if (e_ != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));      \
+    } while (0)
+
+struct rd_wideband {
+    rd_chan *chan = nullptr;
+    rd_demod *dem = nullptr;
+    int n_ch = 0;
+    size_t B = 0;                 // output samples per channel and chunk (the demodulator's block size)
+    size_t chunk_bytes = 0;       // 2 * decim * B
+    uint64_t clock = 0;           // absolute output time of the next chunk's first output
+    long n_sub = 0;               // chunks submitted since create / reset (chunk k uses buffers k & 1)
+    long last = -1;               // chunk the last fetch returned
+    bool dev_ready = false;
+    pid_t pid = 0;
+    hipStream_t st = nullptr, st_copy = nullptr;   // the demodulator's streams
+    uint8_t *h_in[2] = {nullptr, nullptr};         // pinned staging of the host's chunk
+    uint8_t *d_wide[2] = {nullptr, nullptr};       // device chunk buffers
+    uint8_t *d_out[2] = {nullptr, nullptr};        // channelized chunks [n_channels][2 B]
+    hipEvent_t e_in[2] = {nullptr, nullptr};       // chunk buffer k & 1 copied
+    hipEvent_t e_chan[2] = {nullptr, nullptr};     // chunk k's channelizer done
+};
+
+extern "C" int rd_wideband_create(const rd_config *cfg, const rd_chan_config *ccfg, const double *taps,
+                                  const int64_t *shift_hz, rd_wideband **out) {
+    if (!cfg || !ccfg || !taps || !shift_hz || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (cfg->block_size < 128 || cfg->block_size % 128)
+        return rd_fail_msg(RD_ERR_ARG, "block_size %d is not a positive multiple of 128", cfg->block_size);
+    rd_chan *ch = nullptr;
+    int rc = rd_chan_create(ccfg, taps, shift_hz, &ch);
+    if (rc) return rc;
+    rd_demod *dem = nullptr;
+    rc = rd_create_multi(cfg, ccfg->n_channels, &dem);
+    if (rc) {
+        rd_chan_destroy(ch);
+        return rc;
+    }
+    rd_wideband *w = new rd_wideband();
+    w->chan = ch;
+    w->dem = dem;
+    w->n_ch = ccfg->n_channels;
+    w->B = (size_t)cfg->block_size;
+    w->chunk_bytes = 2 * (size_t)ccfg->decim * w->B;
+    *out = w;
+    return RD_OK;
+}
+
+extern "C" void rd_wideband_destroy(rd_wideband *w) {
+    if (!w) return;
+    rd_destroy(w->dem);   // (waits for its streams, which carry all of this handle's work)
+    if (w->dev_ready && w->pid == getpid()) {
+        for (int i = 0; i < 2; i++) {
+            hipHostFree(w->h_in[i]); hipFree(w->d_wide[i]); hipFree(w->d_out[i]);
+            if (w->e_in[i]) hipEventDestroy(w->e_in[i]);
+            if (w->e_chan[i]) hipEventDestroy(w->e_chan[i]);
+        }
+    }
+    rd_chan_destroy(w->chan);
+    delete w;
+}
+
+// device state on the first submit (create does no device work: safe before fork)
+static int wb_alloc(rd_wideband *w) {
+    int rc = rd_demod_prepare(w->dem, &w->st, &w->st_copy);   // (makes the demodulator's device current)
+    if (rc || w->dev_ready) return rc;
+    rc = rd_chan_stream_prepare(w->chan);
+    if (rc) return rc;
+    w->pid = getpid();
+    const size_t out_bytes = (size_t)w->n_ch * 2 * w->B + RD_INPUT_PAD;
+    for (int i = 0; i < 2; i++) {
+        WCHK(hipHostMalloc((void **)&w->h_in[i], w->chunk_bytes, hipHostMallocDefault));
+        WCHK(hipMalloc(&w->d_wide[i], w->chunk_bytes + 16));
+        WCHK(hipMalloc(&w->d_out[i], out_bytes));
+        WCHK(hipEventCreateWithFlags(&w->e_in[i], hipEventDisableTiming));
+        WCHK(hipEventCreateWithFlags(&w->e_chan[i], hipEventDisableTiming));
+    }
+    w->dev_ready = true;
+    return RD_OK;
+}
+
+extern "C" int rd_wideband_reset(rd_wideband *w) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
+    if (rc) return rc;
+    w->clock = 0;
+    w->n_sub = 0;                // (no previous chunk: zero history)
+    w->last = -1;
+    return RD_OK;
+}
+
+extern "C" int rd_wideband_submit(rd_wideband *w, const uint8_t *wide_iq, size_t nbytes) {
+    if (!w || !wide_iq) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (nbytes != w->chunk_bytes)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: got %zu bytes, expected %zu", nbytes, w->chunk_bytes);
+    int rc = wb_alloc(w);
+    if (rc) return rc;
+    rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
+    if (rc) return rc;
+    const int s = (int)(w->n_sub & 1);
+    // the pinned slot's previous copy (chunk k-2) has completed: its demod block has been fetched or dropped
+    if (w->n_sub >= 2) WCHK(hipEventSynchronize(w->e_in[s]));
+    memcpy(w->h_in[s], wide_iq, nbytes);
+    // buffer s holds chunk k-2, the history chunk k-1's channelizer reads: overwrite it once that has run
+    if (w->n_sub >= 1) WCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s ^ 1], 0));
+    WCHK(hipMemcpyAsync(w->d_wide[s], w->h_in[s], nbytes, hipMemcpyHostToDevice, w->st_copy));
+    WCHK(hipEventRecord(w->e_in[s], w->st_copy));
+    WCHK(hipStreamWaitEvent(w->st, w->e_in[s], 0));
+    rc = rd_chan_stream_launch(w->chan, w->d_wide[s], w->n_sub >= 1 ? w->d_wide[s ^ 1] : nullptr, w->B, w->clock,
+                               w->d_out[s], 2 * w->B, w->st);
+    if (rc) return rc;
+    WCHK(hipEventRecord(w->e_chan[s], w->st));
+    w->clock += w->B;
+    w->n_sub++;
+    return rd_demod_submit_device(w->dem, w->d_out[s]);
+}
+
+static int wb_fetched(rd_wideband *w, int rc) {
+    if (rc == RD_OK || rc == RD_ERR_CAPACITY) w->last = w->n_sub - 1 - rd_demod_pending(w->dem);  // (the oldest in flight)
+    return rc;
+}
+
+extern "C" int rd_wideband_fetch(rd_wideband *w, rd_packet *out, int cap, int *n) {
+    if (!w || !n) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    return wb_fetched(w, rd_demod_fetch(w->dem, out, cap, n));
+}
+
+extern "C" int rd_wideband_refetch(rd_wideband *w, rd_packet *out, int cap, int *n) {
+    if (!w || !n) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    return rd_demod_refetch(w->dem, out, cap, n);
+}
+
+extern "C" int rd_wideband_inflight(rd_wideband *w) { return w ? rd_demod_pending(w->dem) : 0; }
+
+extern "C" int rd_wideband_copy_channelized(rd_wideband *w, uint8_t *out, size_t nbytes) {
+    if (!w || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    const size_t need = (size_t)w->n_ch * 2 * w->B;
+    if (nbytes != need) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: got %zu bytes, expected %zu", nbytes, need);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (w->n_sub - w->last > 2) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk's buffer has been reused by a later submit");
+    const int s = (int)(w->last & 1);
+    WCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s], 0));
+    WCHK(hipMemcpyAsync(out, w->d_out[s], need, hipMemcpyDeviceToHost, w->st_copy));
+    WCHK(hipStreamSynchronize(w->st_copy));
+    return RD_OK;
+}
+
+extern "C" int rd_wideband_copy_discriminated(rd_wideband *w, int channel, double *out, size_t n) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    return rd_copy_discriminated_stream(w->dem, channel, out, n);
+}
+
+extern "C" int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (n_out % 128) return rd_fail_msg(RD_ERR_ARG, "the clock moves in multiples of 128 output times");
+    if (rd_demod_inflight(w->dem)) return rd_fail_msg(RD_ERR_STATE, "chunks in flight: fetch them first");
+    w->clock += n_out;
+    return RD_OK;
+}

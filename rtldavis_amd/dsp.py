@@ -137,6 +137,21 @@ def _packets_from(recs, n: int) -> List[Packet]:
     return out
 
 
+def _packets_per_stream(recs, n: int, n_streams: int) -> List[List[Packet]]:
+    """One ``List[Packet]`` per stream from the records of one lock-step round."""
+    out: List[List[Packet]] = [[] for _ in range(n_streams)]
+    for i in range(n):
+        r = recs[i]
+        data = np.frombuffer(bytes(r.data[: r.nbytes]), dtype=np.uint8)
+        snr = float(r.snr)
+        if snr == -math.inf:
+            # as Demodulator._packets_from: the reference's math.log10(0) raises out of that stream's
+            # demodulate() (dsp.py:231-236).  One exception for the whole round: the streams run in lock step.
+            raise ValueError("math domain error")
+        out[r.stream].append(Packet(int(r.index), data, float(r.rssi), snr))
+    return out
+
+
 class Demodulator:
     """dsp.Demodulator (dsp.py:128-253) on the GPU.
 
@@ -310,17 +325,7 @@ class MultiDemodulator:
             self._recs = (_lib.RdPacket * self._cap)()
             rc = _lib.lib().rd_demod_refetch(self._h, self._recs, self._cap, C.byref(n))
         _lib.check(rc)
-        out: List[List[Packet]] = [[] for _ in range(self.n_streams)]
-        for i in range(n.value):
-            r = self._recs[i]
-            data = np.frombuffer(bytes(r.data[: r.nbytes]), dtype=np.uint8)
-            snr = float(r.snr)
-            if snr == -math.inf:
-                # as Demodulator._packets_from: the reference's math.log10(0) raises out of that stream's
-                # demodulate() (dsp.py:231-236).  One exception for the whole round: the streams run in lock step.
-                raise ValueError("math domain error")
-            out[r.stream].append(Packet(int(r.index), data, float(r.rssi), snr))
-        return out
+        return _packets_per_stream(self._recs, n.value, self.n_streams)
 
     def demodulate(self, blocks: np.ndarray) -> List[List[Packet]]:
         """blocks: uint8 [n_streams, 2*block_size].  Returns one ``List[Packet]`` per stream."""

@@ -1,0 +1,112 @@
+"""Live wideband receiver: one capture that never ends, fed chunk by chunk, channelized into every hop
+channel and demodulated on the GPU with the state of both carried from chunk to chunk
+(csrc/rd_wideband.hip).
+
+``Channelizer`` + ``BatchDemodulator`` handle one self-contained capture: zero history before it, output
+time counted from its start.  Fed a live SDR's chunks one at a time they would restart the filter history
+and the mixer phase at every boundary and damage every packet that crosses one.  ``WidebandReceiver``
+carries both: its channelized bytes equal ``Channelizer.run_host()`` on the whole capture, byte for byte,
+and its packets equal ``BatchDemodulator`` on those bytes.  Parity with the reference is unpinned, as for
+the channelizer (rtldavis retunes one narrow-band dongle per hop).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .channelizer import DEFAULT_CENTRE_HZ, DEFAULT_DECIM, US_CHANNELS_HZ, chan_config, plan_channels
+from .dsp import Packet, _cfg_struct, _packets_per_stream
+
+logger = logging.getLogger(__name__)
+
+
+class WidebandReceiver:
+    """``WidebandReceiver(cfg, channels_hz, centre_hz)``: chunks of ``chunk_bytes`` (uint8 I,Q of
+    ``decim * cfg.block_size`` wideband samples at ``decim * cfg.bit_rate * cfg.symbol_length``) in,
+    one ``List[Packet]`` per channel and chunk out - each channel behaves like its own ``Demodulator``
+    fed the channel's stream.  ``submit`` / ``fetch`` keep up to two chunks in flight (the copy of
+    one beside the kernels of the other); ``demodulate`` is both in one call."""
+
+    def __init__(self, cfg, channels_hz: Sequence[int] = US_CHANNELS_HZ, centre_hz: int = DEFAULT_CENTRE_HZ,
+                 decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0) -> None:
+        self.cfg = cfg
+        if int(cfg.block_size) % 128 or int(cfg.block_size) < 128:
+            raise ValueError(f"block_size {cfg.block_size} is not a positive multiple of 128")
+        plan_channels(self, channels_hz, centre_hz, decim, taps, gain, int(cfg.bit_rate) * int(cfg.symbol_length))
+        self.block_size = int(cfg.block_size)
+        self.chunk_bytes = 2 * self.decim * self.block_size
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().rd_wideband_create(C.byref(_cfg_struct(cfg)), C.byref(chan_config(self)),
+                                                 self.taps.ctypes.data, self.shift_hz.ctypes.data, C.byref(self._h)))
+        self._cap = 64 * max(1, self.n_channels)
+        self._recs = (_lib.RdPacket * self._cap)()
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().rd_wideband_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def _check_chunk(self, chunk: np.ndarray) -> np.ndarray:
+        a = np.ascontiguousarray(chunk, dtype=np.uint8).reshape(-1)
+        if a.size != self.chunk_bytes:
+            logger.error(f"Incompatible array sizes: chunk.size={a.size}")
+            raise ValueError("Incompatible array sizes")
+        return a
+
+    def _take(self, rc: int, n: "C.c_int") -> List[List[Packet]]:
+        if rc == _lib.RD_ERR_CAPACITY:  # nothing is lost: the handle keeps the chunk's packets
+            self._cap = max(2 * self._cap, n.value)
+            self._recs = (_lib.RdPacket * self._cap)()
+            rc = _lib.lib().rd_wideband_refetch(self._h, self._recs, self._cap, C.byref(n))
+        _lib.check(rc)
+        return _packets_per_stream(self._recs, n.value, self.n_channels)
+
+    def submit(self, chunk: np.ndarray) -> None:
+        """Queue one chunk (asynchronous copy, channelizer and demodulator; at most two chunks in flight)."""
+        a = self._check_chunk(chunk)
+        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.size))
+
+    def fetch(self) -> List[List[Packet]]:
+        """Packets of the oldest chunk in flight, one list per channel."""
+        n = C.c_int(0)
+        rc = _lib.lib().rd_wideband_fetch(self._h, self._recs, self._cap, C.byref(n))
+        return self._take(rc, n)
+
+    def demodulate(self, chunk: np.ndarray) -> List[List[Packet]]:
+        """submit + fetch of one chunk on a quiet receiver."""
+        a = self._check_chunk(chunk)
+        if self.inflight:
+            raise RuntimeError(f"{self.inflight} chunk(s) in flight: fetch them first")
+        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.size))
+        return self.fetch()
+
+    @property
+    def inflight(self) -> int:
+        return int(_lib.lib().rd_wideband_inflight(self._h))
+
+    def reset(self) -> None:
+        """Back to the state after construction: clock at 0, zero history, demodulators reset."""
+        _lib.check(_lib.lib().rd_wideband_reset(self._h))
+
+    def channelized(self) -> np.ndarray:
+        """uint8 [n_channels, 2*block_size]: the channelized chunk the last fetch returned (until the next submit)."""
+        out = np.empty((self.n_channels, 2 * self.block_size), np.uint8)
+        _lib.check(_lib.lib().rd_wideband_copy_channelized(self._h, out.ctypes.data, out.size))
+        return out
+
+    def discriminated(self, channel: int) -> np.ndarray:
+        """``Demodulator.discriminated`` of one channel (for the reference's frequency-error step)."""
+        out = np.empty(2 * self.block_size, dtype=np.float64)
+        _lib.check(_lib.lib().rd_wideband_copy_discriminated(self._h, int(channel), out.ctypes.data, out.size))
+        return out
+
+    def _debug_advance_clock(self, n_out: int) -> None:
+        """Test hook (quiet receiver): move the output clock on by n_out (a multiple of 128), history kept."""
+        _lib.check(_lib.lib().rd_wideband_debug_advance_clock(self._h, int(n_out)))

@@ -1,0 +1,102 @@
+"""Sustained rate of the live wideband receiver (rtldavis_amd.WidebandReceiver): 51 hop channels out of one
+capture, fed chunk by chunk through submit / fetch with two chunks in flight.
+
+A capture of a few chunks is synthesised once (one burst per channel; synth_wideband over hundreds of chunks would
+need gigabytes of host memory) and its chunks are fed round and round, after a warm-up.  Reports, from a host clock
+around work that ends in a fetch:
+  - per-chunk latency (submit call to the return of its fetch) and sustained chunks per second,
+  - wideband MS/s and the real-time factor (air time of the chunks over wall time),
+  - how many injected packets came back on the first pass over the capture.
+Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
+
+    python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--json OUT]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+import rtldavis_amd  # noqa: E402,F401  (sets the environment before HIP initialises)
+from rtldavis_amd import channelizer as CZ  # noqa: E402
+from rtldavis_amd import dsp, synth, wideband  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--chunks", type=int, default=2000, help="timed chunks per repeat (>= 200)")
+    ap.add_argument("--repeats", type=int, default=3, help="timed windows (each after a reset); the median is reported")
+    ap.add_argument("--capture-chunks", type=int, default=6, help="chunks in the synthesised capture")
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--json", default=None, help="also write the result as JSON here")
+    args = ap.parse_args()
+    if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
+        raise SystemExit("--chunks >= 1, --repeats >= 1 and --capture-chunks >= 3")
+    cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
+    B, nk = cfg.block_size, args.capture_chunks
+    off = [f - CZ.DEFAULT_CENTRE_HZ for f in CZ.US_CHANNELS_HZ]
+    raw, info = synth.synth_wideband(range(200, 200 + len(off)), off, nk * B, amplitude=0.05)
+    rx = wideband.WidebandReceiver(cfg)
+    step = rx.chunk_bytes
+    chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
+
+    def run(n):
+        """n chunks round and round through submit / fetch, two in flight; per-chunk latency and packets."""
+        lat, pk = [], []
+        t_sub = []
+        t0 = time.perf_counter()
+        for k in range(n):
+            if rx.inflight == 2:
+                pk.append(rx.fetch())
+                lat.append(time.perf_counter() - t_sub[len(pk) - 1])
+            t_sub.append(time.perf_counter())
+            rx.submit(chunks[k % nk])
+        while rx.inflight:
+            pk.append(rx.fetch())
+            lat.append(time.perf_counter() - t_sub[len(pk) - 1])
+        return time.perf_counter() - t0, np.array(lat), pk
+
+    run(args.warmup)
+    runs = []
+    for _ in range(args.repeats):
+        rx.reset()
+        runs.append(run(args.chunks))
+    walls = [r[0] for r in runs]
+    wall, lat, pk = sorted(runs, key=lambda r: r[0])[len(runs) // 2]   # the median window
+    # the first pass over the capture (chunks 0 .. nk-1 after the reset): every channel's burst where it was injected
+    found = 0
+    for c, (payload, start) in enumerate(info):
+        hits = [(k, p.index) for k in range(min(nk, len(pk))) for p in pk[k][c] if bytes(p.data).hex() == payload]
+        found += any(0 <= (k - 1) * B + i - (start + 32 * 14) <= 30 for k, i in hits)
+    out_rate = rx.out_rate
+    air = args.chunks * B / out_rate
+    res = {
+        "chunks": args.chunks, "capture_chunks": nk, "warmup": args.warmup, "channels": rx.n_channels,
+        "block_size": B, "decim": rx.decim, "chunk_bytes": step, "chunk_air_ms": 1e3 * B / out_rate,
+        "repeats": args.repeats, "wall_s": wall, "wall_s_all": walls, "chunks_per_s": args.chunks / wall,
+        "latency_ms": {"median": float(np.median(lat) * 1e3), "p99": float(np.percentile(lat, 99) * 1e3),
+                       "max": float(lat.max() * 1e3), "min": float(lat.min() * 1e3)},
+        "wideband_msps": args.chunks * rx.decim * B / wall / 1e6,
+        "realtime_factor": air / wall,
+        "injected_packets": len(info), "recovered_first_pass": int(found),
+        "packets_total": int(sum(len(x) for ch in pk for x in ch)),
+    }
+    print(f"{args.chunks} chunks of {1e3 * B / out_rate:.1f} ms air x {rx.n_channels} channels in {wall:.3f} s: "
+          f"{res['chunks_per_s']:.0f} chunks/s, {res['wideband_msps']:.0f} wideband MS/s, real-time factor "
+          f"{res['realtime_factor']:.0f}x")
+    print(f"latency submit -> fetch: median {res['latency_ms']['median']:.3f} ms, p99 {res['latency_ms']['p99']:.3f} ms, "
+          f"max {res['latency_ms']['max']:.3f} ms")
+    print(f"first pass: {found} of {len(info)} injected packets recovered")
+    print(json.dumps(res))
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(res, fh, indent=1)
+    if found != len(info):
+        raise SystemExit(f"only {found} of {len(info)} injected packets recovered")
+
+
+if __name__ == "__main__":
+    main()
