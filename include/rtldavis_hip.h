@@ -266,8 +266,12 @@ int rd_search(const rd_config *cfg, const uint8_t *quantized, size_t n, int32_t 
  * The reference has no channelizer (it retunes one dongle per hop, runners/rtlsdr.py:51,72):
  * parity is unpinned; the definition is in rtldavis_amd/csrc/rd_channelizer.hip and restated in
  * float64 by oracle/channelizer_oracle.py.  It runs on the matrix cores (f16 MFMA with the taps split
- * into two f16 digits, 2^-22 relative; the 8-bit samples are exact in f16, accumulation is fp32): output
- * bytes may differ from the float64 model by one LSB where the sum lands on a rounding boundary.
+ * into two f16 digits, 2^-22 relative; the 8-bit samples are exact in f16, accumulation is fp32).
+ * Contract: with Z the float64 model's value in front of the quantiser (channelize_z), every output byte
+ * is within one step of clip(rint(Z), 0, 255), and equals it wherever Z lies more than delta from every
+ * rounding boundary k + 1/2; delta, a few hundredths of a step at 512 taps, is derived from the kernel's
+ * arithmetic in tests/chan_bound.py:error_bound (its one unmeasured input: the hardware sine's accuracy,
+ * assumed 2^-16).  Measured: the bytes that differ lie within 1/50 of delta of a boundary.
  * ------------------------------------------------------------------------------------------- */
 typedef struct rd_chan_config {
     int32_t out_rate;   /* Hz per channel (19200 * symbol_length = 268800, protocol.py:309) */

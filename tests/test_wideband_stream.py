@@ -248,3 +248,56 @@ def test_timed_out_fetch_loses_the_packets_not_the_stream(six):
             continue
         assert _key(w.demodulate(chunk)) == _key(six["got"][k]), k
         assert np.array_equal(w.channelized(), six["bytes"][k]), k
+
+
+# name: (n_channels, decim, taps (T, or None for the default design), block_size, symbol_length, chunks)
+STREAM_CONFIGS = {
+    "70ch_two_groups": (70, 100, None, 1024, 14, 4),
+    "d4_t256_block128": (3, 4, 256, 128, 14, 6),       # one workgroup per group and chunk; taps reach into the last chunk
+    "sym8_t255": (4, 100, 255, 1024, 8, 4),            # out_rate 153600
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(STREAM_CONFIGS))
+def test_streamed_form_at_other_configs(name):
+    """The streamed bytes equal Channelizer.run_host on the whole capture, byte for byte, and stay within the bound of
+    the float64 model; after reset() in mid-stream the chunks equal the one-shot form on the capture from there on."""
+    import chan_bound as CB
+    from oracle import channelizer_oracle as CHO
+    from rtldavis_amd import channelizer as CZ
+    from rtldavis_amd import dsp, wideband
+    n_ch, decim, T, bs, sl, nk = STREAM_CONFIGS[name]
+    seed = sum(map(ord, name))
+    cfg = dsp.PacketConfig(19200, sl, 16, 80, "1100101110001001", bs)
+    fo = 19200 * sl
+    fw = fo * decim
+    taps = None if T is None else CB.random_taps(T, seed)
+    rng = np.random.default_rng(seed)
+    centre = CZ.DEFAULT_CENTRE_HZ
+    chans = [int(centre + f) for f in rng.integers(-fw // 2 + fo, fw // 2 - fo, n_ch)]
+    w = wideband.WidebandReceiver(cfg, chans, centre, decim=decim, taps=taps)
+    cz = CZ.Channelizer(chans, centre, decim=decim, taps=taps, out_rate=fo)
+    assert w.out_rate == fo and np.array_equal(w.shift_hz, cz.shift_hz)
+    raw = CB.capture(nk * bs * decim, seed, fw)
+    step = w.chunk_bytes
+    streamed = []
+    for k in range(nk):
+        w.demodulate(raw[step * k: step * (k + 1)])
+        streamed.append(w.channelized())
+    streamed = np.concatenate(streamed, axis=1)
+    cz.upload(raw)
+    assert np.array_equal(streamed, cz.run_host())
+    Z = CHO.channelize_z(raw, cz.shift_hz, cz.taps, decim, fo, cz.gain)
+    s = CB.assert_matches_model(streamed, Z, CB.error_bound(cz, cz.taps, Z, raw))
+    print(f"\n[chan-stream] {name}: exempt {s['exempt']:.2%}, mismatches {s['mismatches']}/{streamed.size}, "
+          f"worst distance {s['worst_dist']:.2e} ({s['worst_ratio']:.2f} of delta)")
+    # reset() after chunk 1: chunks 2.. are a new capture
+    k0 = 2
+    w.reset()
+    again = []
+    for k in range(k0, nk):
+        w.demodulate(raw[step * k: step * (k + 1)])
+        again.append(w.channelized())
+    cz.upload(raw[step * k0:])
+    assert np.array_equal(np.concatenate(again, axis=1), cz.run_host())
