@@ -290,7 +290,7 @@ static int batch_alloc(rd_batch *b) {
         // of the one-launch tail (A/B; also what every shape other than the Davis one takes).  RD_TEST_BUCKET_CAP makes
         // the per-stream match lists short so that the fallback runs on ordinary inputs (test hook)
         const char *ti = getenv("RD_TAIL_IMPL");
-        const bool legacy = (ti && ti[0] == 'l') || getenv("RD_SLICE_IMPL");  // (an explicit slice form means the separate kernels)
+        const bool legacy = ti && ti[0] == 'l';
         b->ft_ok = !legacy && b->fast_ok && b->dc.S == 14 && b->dc.P == 16 && b->dc.K == 80 && b->dc.pre_mask == 0x91D3ull &&
                    b->n_samples < (1l << 30) && b->dc.B < (1 << 24) && b->bits_stride % 4 == 0 && b->dc.L >= b->dc.B &&
                    (long)(b->n_blocks + 1) * b->dc.B - b->dc.L >= 0 &&   // (a batch shorter than a packet has no position to report)

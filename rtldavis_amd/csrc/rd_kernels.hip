@@ -6,13 +6,13 @@
 //                    listed groups, Demodulator._search py:171-188, ._slice py:190-246 incl. order, dedupe, RSSI / SNR
 //   k_fixup        : exact integer re-evaluation of the listed groups (every other shape, the streaming legacy path)
 //   k_search       : Demodulator._search py:171-188 (go:115-131) on packed bits, bit-parallel
-//   k_classify + k_rssi_u8, k_slice_rssi : Demodulator._slice py:190-246 without the final order (the host orders)
+//   k_classify + k_rssi_u8 : Demodulator._slice py:190-246 without the final order (the host orders), batch path, Davis shape
+//   k_slice_rssi   : the same in one kernel everywhere else (other shapes, streaming multi-launch form, complex input)
 //   k_stream_block : one Demodulator.demodulate() call py:139-246 in one launch (streaming handle)
 //   k_parse_select / k_freq_err : Parser.parse front half, protocol.py:290-311 (opt-in)
 //   k_disc/k_filt  : float64 discriminate / fir9 values for the state mirrors py:133-134
 //   k_cplx_*       : the complex-input branch py:144-150 in float64
 //   stage kernels  : one float64 kernel per reference stage function
-//   k_demod_bits   : the round-1 demod kernel (FIR on the VALU), diagnostic library only (RD_K1_IMPL=valu)
 #include <algorithm>
 #include <cstdlib>
 
@@ -22,251 +22,8 @@
 #include "rd_math.h"
 #include "rd_mfma.h"
 
-#ifdef RD_DIAG   // the round-1 demod kernel: A/B runs only
-#define RD_WG 256
-#define RD_WAVES (RD_WG / 64)
-#define RD_LDS_WAVE (32 + RD_TILE_BYTES)  // 32 B halo + one 4 KiB tile, private to a wave
-#define RD_PEND 128                       // guard-band run ids staged per wave before one atomic
-
-// Window bytes of one lane held in six dwordx4 registers: byte i of the window
-// (sample t0-10 is byte 0) is byte 12+i of the 96-byte chunk starting 32 B before the run.
-// The conversion is inline asm so that LLVM cannot rewrite "float(a) + float(b)" into an
-// integer SDWA add followed by a conversion (it does: twice the instructions, all on the
-// slow issue pipe).  Not volatile: it may be scheduled and CSE'd freely.
-struct rd_reg_src {
-    uint32_t q[24];
-    __device__ __forceinline__ float f(int i) const {
-        const int b = i + 12;
-        const uint32_t d = q[b >> 2];
-        float r;
-        switch (b & 3) {
-            case 0: asm volatile("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(d)); break;
-            case 1: asm volatile("v_cvt_f32_ubyte1 %0, %1" : "=v"(r) : "v"(d)); break;
-            case 2: asm volatile("v_cvt_f32_ubyte2 %0, %1" : "=v"(r) : "v"(d)); break;
-            default: asm volatile("v_cvt_f32_ubyte3 %0, %1" : "=v"(r) : "v"(d)); break;
-        }
-        return r;
-    }
-};
-
-// Append a wave's staged ids to the global list with one atomic (count is wave-uniform).
-__device__ __forceinline__ void rd_flush_pending(const uint32_t *pend, uint32_t count, uint32_t *fix_list,
-                                                 uint32_t fix_cap, uint32_t *counters, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // staged ids written by other lanes
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&counters[RD_CNT_FIX], count);
-    base = __builtin_amdgcn_readfirstlane(base);
-    for (uint32_t i = lane; i < count; i += 64)
-        if (base + i < fix_cap) fix_list[base + i] = pend[i];
-}
-
-// ------------------------------------------------------------------------------------------
-// k_demod_bits: one wave = one 2048-sample tile per iteration, grid-stride over tiles.
-// LDS is wave-private (no workgroup barrier anywhere): [halo 32 B][tile 4096 B].
-// ------------------------------------------------------------------------------------------
-// LDS image of a tile (wave-private).  One global_load_lds_dwordx4 writes 64 consecutive
-// 16-byte slots (slot = lane), so the *source* chunk of each lane is permuted instead
-// (cdna_hip_programming.md rule 21): slot 64j + l holds chunk 64j + 4(l%16) + l/16 of the
-// tile.  Lane L then finds its four chunks 4L..4L+3 at slots 64(L/16) + 16i + L%16 - for a
-// fixed i, 16 neighbouring lanes read 16 neighbouring slots: ds_read_b128 without bank
-// conflicts (a plain linear image would be a 4-way conflict at the 64-byte lane stride).
-__device__ __forceinline__ void rd_issue_tile_loads(const rd_layout &lay, uint32_t s, uint32_t ti, uint8_t *my,
-                                                    int lane) {
-    const uint8_t *src = lay.iq + (size_t)s * lay.stream_stride + (size_t)ti * RD_TILE_BYTES;
-    const int perm = 4 * (lane & 15) + (lane >> 4);
-    // the instruction offset advances the global and the LDS address alike: one address pair,
-    // four immediates
-    const __attribute__((address_space(1))) void *g0 = (const __attribute__((address_space(1))) void *)(src + perm * 16);
-    __attribute__((address_space(3))) void *l0 = (__attribute__((address_space(3))) void *)(my + 32);
-    __builtin_amdgcn_global_load_lds(g0, l0, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(g0, l0, 16, 1024, 0);
-    __builtin_amdgcn_global_load_lds(g0, l0, 16, 2048, 0);
-    __builtin_amdgcn_global_load_lds(g0, l0, 16, 3072, 0);
-    // halo: the 32 bytes before the tile (previous tile, or the caller's history bytes).
-    // With zero history there is nothing to read: run 0 is always re-evaluated exactly.
-    const bool has_halo = (ti > 0) || lay.hist_mode;
-    if (lane < 2)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void *)(src + (has_halo ? -32 : 0) + lane * 16),
-            (__attribute__((address_space(3))) void *)(my), 16, 0, 0);
-}
-
-// DBG (compile-time, 0 in the shipped instantiation): 1 = no global loads (compute on whatever
-// LDS holds), 2 = loads and LDS reads only, no arithmetic - timing ablations, results are garbage.
-template <int DBG, int NPK>
-__global__ __launch_bounds__(RD_WG, 4) void k_demod_bits(rd_layout lay, uint32_t tiles_per_stream,
-                                                      uint32_t runs_per_stream, uint32_t *fix_list,
-                                                      uint32_t fix_cap, uint32_t *counters) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[RD_WAVES][RD_LDS_WAVE];
-    // Guard-band run ids are staged per wave and appended to the global list RD_PEND at a
-    // time: one returning atomic per ~100 ids instead of one per tile (a single counter
-    // word sustains only ~90 atomics/us, MI355X_MICROARCH.md "dequeue").
-    __shared__ uint32_t pend[RD_WAVES][RD_PEND];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar: tile bookkeeping stays on the SALU
-    uint8_t *my = lds[wave];
-    uint32_t *mypend = pend[wave];
-    uint32_t npend = 0;  // wave-uniform
-    const uint32_t nwaves = gridDim.x * RD_WAVES;
-    // tile = s * tiles_per_stream + ti advances by nwaves per iteration: (s, ti) += (dq, dr) with carry
-    const uint32_t dq = nwaves / tiles_per_stream, dr = nwaves % tiles_per_stream;
-    // per-lane LDS addresses: own chunks i = 0..3 at own + 256 i; the previous lane's chunks
-    // 2, 3 (this lane's halo) at prev + 512, prev + 768; lane 0 takes the halo region.
-    const uint8_t *own = my + 32 + 16 * (64 * (lane >> 4) + (lane & 15));
-    const int pl = lane - 1;
-    const uint8_t *h0 = lane ? my + 32 + 16 * (64 * (pl >> 4) + 32 + (pl & 15)) : my;
-    const uint8_t *h1 = lane ? h0 + 256 : my + 16;
-
-    // The packed word of tile i is stored at the start of iteration i+1, BEFORE the next
-    // tile's loads are issued: stores count in vmcnt too, and a store issued after the loads
-    // would make every `s_waitcnt vmcnt(0)` wait for its write latency as well (-20 % measured).
-    uint32_t st_word = 0;
-    uint32_t *st_ptr = nullptr;
-    const uint32_t first = blockIdx.x * RD_WAVES + wave;
-    uint32_t s = first / tiles_per_stream, ti = first % tiles_per_stream;
-    if (DBG != 1 && s < (uint32_t)lay.n_streams) rd_issue_tile_loads(lay, s, ti, my, lane);
-    while (s < (uint32_t)lay.n_streams) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile has landed in LDS
-        rd_reg_src win;
-        {
-            const uint4 a = *(const uint4 *)h0, b = *(const uint4 *)h1;
-            win.q[0] = a.x; win.q[1] = a.y; win.q[2] = a.z; win.q[3] = a.w;
-            win.q[4] = b.x; win.q[5] = b.y; win.q[6] = b.z; win.q[7] = b.w;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint4 v = *(const uint4 *)(own + 256 * i);
-                win.q[8 + 4 * i] = v.x; win.q[9 + 4 * i] = v.y; win.q[10 + 4 * i] = v.z; win.q[11 + 4 * i] = v.w;
-            }
-        }
-        // The window is in registers: the same LDS buffer can take the next tile while this
-        // one is computed (~2000 VALU instructions cover the HBM latency).
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (st_ptr) *st_ptr = st_word;  // previous tile's output
-        st_ptr = nullptr;
-        uint32_t ns = s + dq, nti = ti + dr;
-        if (nti >= tiles_per_stream) { nti -= tiles_per_stream; ns++; }
-        if (DBG != 1 && ns < (uint32_t)lay.n_streams) rd_issue_tile_loads(lay, ns, nti, my, lane);
-
-        rd_run_result r;
-        if (DBG == 2) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int j = 0; j < 24; j++) x ^= win.q[j];
-            r.word = x; r.fmax = 1.0f;
-#pragma unroll
-            for (int g = 0; g < RD_GROUPS; g++) r.nmin[g] = 1.0e30f;
-        } else {
-            r = rd_fast_run<NPK>(win);
-        }
-
-        const uint32_t run = ti * 64 + lane;
-        const uint32_t t0 = run * RD_RUN;
-        uint32_t gmask = 0;  // groups of 8 samples inside the guard band
-        // only a stream's last tile can be ragged (wave-uniform test): everywhere else the whole
-        // run is valid and none of the tail masking below is executed
-        const bool ragged = (ti + 1 == tiles_per_stream) && (lay.n_samples % RD_TILE_SAMPLES) != 0;
-        if (!ragged) {
-            st_word = r.word;
-            st_ptr = &lay.bits[(size_t)s * lay.bits_stride + run];
-            gmask = (run == 0 && !lay.hist_mode) ? 0xFu : rd_guard_mask(r);
-        } else if (t0 < lay.n_samples) {
-            uint32_t word = r.word;
-            const uint32_t left = lay.n_samples - t0;
-            if (left < RD_RUN) word &= (1u << left) - 1u;
-            st_word = word;
-            st_ptr = &lay.bits[(size_t)s * lay.bits_stride + run];
-            gmask = (run == 0 && !lay.hist_mode) ? 0xFu : rd_guard_mask(r);
-            if (left < RD_RUN) gmask &= (1u << ((left + RD_GROUP - 1) / RD_GROUP)) - 1u;
-        }
-        const uint64_t fm = __ballot(gmask != 0);
-        if (fm) {  // wave-uniform, ~60 % of the tiles on noise
-            // one list entry per flagged run: (word index in the bits array) << 4 | group mask
-            const uint32_t nf = (uint32_t)__popcll(fm);
-            if (npend + nf > RD_PEND) {
-                rd_flush_pending(mypend, npend, fix_list, fix_cap, counters, lane);
-                npend = 0;
-            }
-            if (gmask)
-                mypend[npend + __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0))] =
-                    ((uint32_t)((size_t)s * lay.bits_stride + run) << 4) | gmask;
-            npend += nf;
-        }
-        s = ns;
-        ti = nti;
-    }
-    if (st_ptr) *st_ptr = st_word;
-    if (npend) rd_flush_pending(mypend, npend, fix_list, fix_cap, counters, lane);
-}
-
-#endif  // RD_DIAG (k_demod_bits)
-
-// Environment switches of this file, read once per process (function-local static: thread-safe first use).
-struct rd_k_params {
-    int impl_mfma = 1, per_cu_valu = 7, dbg = 0, npk = RD_NPK_DEFAULT, slice_two = 1, search_cap = 32 / 4;
-    rd_k_params() {
-        const char *e = getenv("RD_SLICE_IMPL");  // "wave": the one-kernel slice on the batch path as well (A/B)
-        slice_two = (e && e[0] == 'w') ? 0 : 1;
-        e = getenv("RD_K2_WGS_PER_CU");  // tuning knob of k_search
-        search_cap = e ? atoi(e) : 32 / 4;
-        if (search_cap < 1 || search_cap > 64) search_cap = 32 / 4;
-#ifdef RD_DIAG
-        e = getenv("RD_K1_IMPL");  // "valu": the round-1 demod kernel (FIR on the VALU) for A/B runs
-        impl_mfma = (e && e[0] == 'v') ? 0 : 1;
-        e = getenv("RD_K1_WGS_PER_CU");
-        per_cu_valu = e ? atoi(e) : 7;
-        if (per_cu_valu < 1 || per_cu_valu > 8) per_cu_valu = 7;
-        e = getenv("RD_K1_DEBUG");  // timing ablations with garbage results
-        dbg = e ? atoi(e) : 0;
-        npk = RD_NPK_DEFAULT;
-        e = getenv("RD_K1_NPK");    // packed FIR steps per output, for tuning sweeps
-        if (e) npk = atoi(e);
-#endif
-    }
-};
-static const rd_k_params &rd_k_get_params() {
-    static const rd_k_params p;
-    return p;
-}
-
 uint32_t rd_launch_demod(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                          hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t flags, uint32_t *chunk_out, uint32_t *bucket_cnt) {
-#ifdef RD_DIAG
-    const rd_k_params &P = rd_k_get_params();
-    if (!P.impl_mfma) {
-        const uint32_t tps = (lay.n_samples + RD_TILE_SAMPLES - 1) / RD_TILE_SAMPLES;
-        const uint32_t rps = (lay.n_samples + RD_RUN - 1) / RD_RUN;
-        const uint64_t total = (uint64_t)lay.n_streams * tps;
-        uint64_t wgs = (total + RD_WAVES - 1) / RD_WAVES;
-        // persistent grid: workgroups per CU (72 VGPRs and 18.5 KiB LDS admit 7); RD_K1_WGS_PER_CU overrides
-        const uint64_t max_wgs = 256ull * P.per_cu_valu;
-        if (wgs > max_wgs) wgs = max_wgs;
-        if (wgs == 0) return 0;
-
-    // With events given, the dispatch itself carries them (hipExtLaunchKernelGGL): its begin / end
-    // timestamps, without the marker packets of hipEventRecord that idle the GPU for ~6 us each.
-#define RD_LAUNCH_K1(D, N)                                                                                          \
-    do {                                                                                                            \
-        if (ev_start || ev_stop)                                                                                    \
-            hipExtLaunchKernelGGL((k_demod_bits<D, N>), dim3((unsigned)wgs), dim3(RD_WG), 0, st, ev_start, ev_stop, \
-                                  0, lay, tps, rps, fix_list, fix_cap, counters);                                   \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_demod_bits<D, N>), dim3((unsigned)wgs), dim3(RD_WG), 0, st, lay, tps, rps,        \
-                               fix_list, fix_cap, counters);                                                        \
-    } while (0)
-        if (P.dbg == 1) { RD_LAUNCH_K1(1, RD_NPK_DEFAULT); return 0; }
-        if (P.dbg == 2) { RD_LAUNCH_K1(2, RD_NPK_DEFAULT); return 0; }
-        if (P.npk == 0) { RD_LAUNCH_K1(0, 0); return 0; }
-        if (P.npk == 2) { RD_LAUNCH_K1(0, 2); return 0; }
-        if (P.npk == 4) { RD_LAUNCH_K1(0, 4); return 0; }
-        if (P.npk == 6) { RD_LAUNCH_K1(0, 6); return 0; }
-        if (P.npk == 7) { RD_LAUNCH_K1(0, 7); return 0; }
-        if (P.npk == 9) { RD_LAUNCH_K1(0, 9); return 0; }
-        RD_LAUNCH_K1(0, RD_NPK_DEFAULT);
-#undef RD_LAUNCH_K1
-        return 0;
-    }
-#endif
     if (!bucket_cnt) flags &= ~RD_DEMOD_FIX_BUCKETS;
     const bool bucketed = rd_launch_demod_mfma(lay, fix_list, fix_cap, counters, st, ev_start, ev_stop, nullptr, flags, chunk_out, bucket_cnt);
     return bucketed ? RD_DEMOD_FIX_BUCKETS : 0u;
@@ -377,6 +134,36 @@ __device__ __forceinline__ uint32_t rd_bits32_at_i(const uint32_t *w, int nwords
     const uint32_t lo = (wi >= 0 && wi < nwords) ? w[wi] : 0u;
     const uint32_t hi = (wi + 1 >= 0 && wi + 1 < nwords) ? w[wi + 1] : 0u;
     return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(o & 31));
+}
+
+// the same from a window in LDS (the streaming kernels): bits o .. o+31, zeros outside
+__device__ __forceinline__ uint32_t rd_lds_bits32(const uint32_t *w, int nwords, int o) {
+    if (o < 0) return o <= -32 ? 0u : (w[0] << (-o));
+    const int wi = o >> 5;
+    const uint32_t lo = wi < nwords ? w[wi] : 0u, hi = wi + 1 < nwords ? w[wi + 1] : 0u;
+    return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(o & 31));
+}
+
+// Preamble search over a streaming window in LDS (py:171-188), one 32-position word per thread; positions 0 .. B
+// (q <= B: py:194).  The matches go to s_match, counted by *s_nm (at most B + 1 of them).
+template <int S_, int P_, uint64_t PRE_>
+__device__ __forceinline__ void rd_window_search(const uint32_t *s_win, int nwin, int nbw, int tid, int nthreads,
+                                                 uint32_t *s_nm, int32_t *s_match) {
+    for (int o = tid; o <= nbw; o += nthreads) {
+        uint32_t m = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < P_; k++) {
+            const uint32_t v = rd_lds_bits32(s_win, nwin, 32 * o + k * S_);
+            m &= ((PRE_ >> k) & 1) ? v : ~v;
+        }
+        if (o == nbw) m &= 1u;  // position B only
+        while (m) {
+            const int bpos = __builtin_ctz(m);
+            m &= m - 1;
+            const uint32_t slot = atomicAdd(s_nm, 1u);
+            s_match[slot] = 32 * o + bpos;
+        }
+    }
 }
 
 #ifndef RD_SEARCH_OUT
@@ -571,6 +358,17 @@ __global__ __launch_bounds__(64 * RD_SEARCH_WAVES) void k_search(const uint32_t 
     }
 }
 
+// k_search's workgroups per CU: 8 waves per SIMD unless the tuning knob RD_K2_WGS_PER_CU (1 - 64) says otherwise.
+// Read once per process (function-local static: thread-safe first use).
+static int rd_search_wgs_per_cu() {
+    static const int cap = [] {
+        const char *e = getenv("RD_K2_WGS_PER_CU");
+        const int v = e ? atoi(e) : 32 / 4;
+        return (v < 1 || v > 64) ? 32 / 4 : v;
+    }();
+    return cap;
+}
+
 void rd_launch_search(const uint32_t *bits, size_t bits_stride, int n_streams, long n_bits, long p_lo, long p_hi,
                       const rd_devcfg &cfg, rd_match *matches, uint32_t match_cap, uint32_t *counters,
                       hipStream_t st) {
@@ -580,7 +378,7 @@ void rd_launch_search(const uint32_t *bits, size_t bits_stride, int n_streams, l
     const long groups = (p_hi - base) / (32 * RD_SEARCH_OUT) + 1;
     const uint64_t total = (uint64_t)n_streams * groups;
     uint64_t wgs = (total + 64 * RD_SEARCH_WAVES - 1) / (64 * RD_SEARCH_WAVES);
-    const int cap = rd_k_get_params().search_cap;  // 8 waves per SIMD unless RD_K2_WGS_PER_CU says otherwise
+    const int cap = rd_search_wgs_per_cu();
     if (wgs > 256ull * cap) wgs = 256ull * cap;
     // the Davis configuration (protocol.py:68-76): 14 samples/symbol, preamble 1100101110001001
     // (bit m of the mask = symbol m -> 0x91D3)
@@ -602,10 +400,6 @@ void rd_launch_search(const uint32_t *bits, size_t bits_stride, int n_streams, l
 // RD_CNT_REC.  A match that no call reports leaves stream = -1.  Per-call duplicates (py:203-205)
 // are dropped by the host when it puts the records in the reference's order.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rd_bit_at(const uint32_t *w, long nwords, long o) {
-    return (rd_word_at(w, nwords, o >> 5) >> (o & 31)) & 1u;
-}
-
 __device__ __forceinline__ double rd_wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -684,12 +478,6 @@ __device__ __forceinline__ void rd_rssi_pass(const rd_stream_view &v, int n0, in
         const int j = j0 + r;
         if (j < pe) { if (j < q) noise += pw; else sig += pw; }
     }
-}
-
-__device__ __forceinline__ float rd_wave_sum_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;  // valid in lane 0
 }
 
 // The RSSI windows on the matrix pipe: the 448 filter outputs of a packet's two windows are ONE 16-output block of
@@ -1815,9 +1603,8 @@ int rd_launch_slice(const rd_layout &lay, const uint32_t *bits, size_t bits_stri
                     void *tasks) {
     rd_u8_src src;
     src.lay = lay;
-    const int two = rd_k_get_params().slice_two;  // RD_SLICE_IMPL=wave: the one-kernel form (A/B)
     // the Davis shape in the batch path: lane-per-match classification, then one wave per surviving packet
-    if (two && tasks && batch_mode && recs && !recs_host && cfg.S == 14 && cfg.K == 80 && n_bits < (1l << 30)) {
+    if (tasks && batch_mode && recs && !recs_host && cfg.S == 14 && cfg.K == 80 && n_bits < (1l << 30)) {
         const uint32_t cg = std::min<uint32_t>((match_cap + 255) / 256, 1024);
         hipLaunchKernelGGL((k_classify<14, 80>), dim3(cg ? cg : 1), dim3(256), 0, st, bits, bits_stride,
                            (int)((n_bits + 31) / 32), cfg, matches, match_cap, n_calls, recs, (rd_task *)tasks, counters);
@@ -2037,13 +1824,6 @@ void rd_launch_window_update(uint32_t *win_out, const uint32_t *win_in, long n_w
 // 16384): everything else keeps the multi-launch form.  Every position 0 .. B can be a match (a degenerate input makes
 // it so): the match list in LDS and the stream's region of the mapped record array hold B + 1 entries.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rd_lds_bits32(const uint32_t *w, int nwords, int o) {  // bits o .. o+31 (zeros outside)
-    if (o < 0) return o <= -32 ? 0u : (w[0] << (-o));
-    const int wi = o >> 5;
-    const uint32_t lo = wi < nwords ? w[wi] : 0u, hi = wi + 1 < nwords ? w[wi + 1] : 0u;
-    return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(o & 31));
-}
-
 #ifdef RD_DIAG
 // diagnostic library: s_memrealtime stamps of the streaming blocks' phases (stream 0's workgroup), RD_SB_STAMPS=1
 #define RD_SB_STAMP(k) do { if (a.stamps && threadIdx.x == 0 && blockIdx.x == 0) { uint64_t t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
@@ -2142,21 +1922,7 @@ __global__ __launch_bounds__(RD_SB_THREADS) void k_stream_block(rd_sb_args a) {
     // ---- 2: the window goes out for the state mirrors (rd_copy_quantized) and the next call ----
     for (int i = tid; i < nwin; i += RD_SB_THREADS) win_out[i] = s_win[i];
     // ---- 3: search, one 32-position word per thread; positions 0 .. B ----
-    for (int o = tid; o <= nbw; o += RD_SB_THREADS) {
-        uint32_t m = 0xFFFFFFFFu;
-#pragma unroll
-        for (int k = 0; k < P_; k++) {
-            const uint32_t v = rd_lds_bits32(s_win, nwin, 32 * o + k * S_);
-            m &= ((PRE_ >> k) & 1) ? v : ~v;
-        }
-        if (o == nbw) m &= 1u;  // position B only
-        while (m) {
-            const int bpos = __builtin_ctz(m);
-            m &= m - 1;
-            const uint32_t slot = atomicAdd(&s_nm, 1u);
-            s_match[slot] = 32 * o + bpos;  // (at most B + 1 of them)
-        }
-    }
+    rd_window_search<S_, P_, PRE_>(s_win, nwin, nbw, tid, RD_SB_THREADS, &s_nm, s_match);
     __syncthreads();
     RD_SB_STAMP(4);
     const uint32_t nm = s_nm;
@@ -2401,21 +2167,7 @@ __global__ __launch_bounds__(RD_SBC_THREADS) void k_stream_block_cplx(rd_sbc_arg
     __syncthreads();
     RD_SBL_STAMP(4);
     // ---- search, one 32-position word per thread; positions 0 .. B ----
-    for (int o = tid; o <= nbw; o += T) {
-        uint32_t m = 0xFFFFFFFFu;
-#pragma unroll
-        for (int k = 0; k < P_; k++) {
-            const uint32_t x = rd_lds_bits32(s_win, nwin, 32 * o + k * S_);
-            m &= ((PRE_ >> k) & 1) ? x : ~x;
-        }
-        if (o == nbw) m &= 1u;  // position B only
-        while (m) {
-            const int bpos = __builtin_ctz(m);
-            m &= m - 1;
-            const uint32_t slot = atomicAdd(&s_nm, 1u);
-            s_match[slot] = 32 * o + bpos;  // (at most B + 1 of them)
-        }
-    }
+    rd_window_search<S_, P_, PRE_>(s_win, nwin, nbw, tid, T, &s_nm, s_match);
     __syncthreads();
     RD_SBL_STAMP(5);
     const uint32_t nm = s_nm;

@@ -102,58 +102,28 @@ RD_HD uint32_t rd_guard_mask(const rd_run_result &r);
 // Fast fp32 evaluation of one run.  `win` holds the raw bytes of samples t0-10 .. t0+30
 // (2*RD_WIN bytes, I then Q); t0 % 4 == 0 in absolute stream time.  Fully unrolled by the
 // compiler: every phase / tap / sign below is a compile-time constant per unrolled step.
-// `Src::f(i)` returns byte i of that window converted to float (on the device: one
-// v_cvt_f32_ubyteN on a register dword, kept opaque to the optimiser - see rd_kernels.hip).
+// `Src::f(i)` returns byte i of that window converted to float.  No kernel runs this fp32 form
+// (the demod kernel is rd_demod_mfma.hip); tests/host_harness.cpp runs it on the CPU.
 struct rd_ptr_src {
     const uint8_t *p;
     RD_HDM float f(int i) const { return (float)p[i]; }
 };
 
-// Issue model measured on MI355X (tools/ubench/valu_*.hip, profiles/): a SIMD issues one VALU
-// instruction per 2 cycles whatever its class; the "slow" class (conversions, min/max,
-// alignbit, packed fp32 ...) additionally needs 4 cycles between two of its own.  So the
-// instruction COUNT is what matters as long as slow-class ops stay below half of the mix:
-// RD_NPK of the nine FIR steps per output (4 pair sums, 5 multiply-adds) are issued as packed
-// fp32 (one instruction for re and im), the rest as scalar pairs.  Results are identical
-// either way (same IEEE operations per component).
 #ifndef RD_FENCE_EVERY
 #define RD_FENCE_EVERY 1
 #endif
-#ifndef RD_NPK_DEFAULT
-#define RD_NPK_DEFAULT 0
-#endif
 
 // s = a + b or a - b (exact: small integers)
-template <bool SUB, bool PACKED>
+template <bool SUB>
 RD_HD rd_f2 rd_pair(rd_f2 a, rd_f2 b) {
     rd_f2 s;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (PACKED) {
-        if (SUB) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(s) : "v"(a), "v"(b));
-        else asm("v_pk_add_f32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
-        return s;
-    }
-#endif
     if (SUB) { s.x = a.x - b.x; s.y = a.y - b.y; } else { s.x = a.x + b.x; s.y = a.y + b.y; }
     return s;
 }
 
 // acc + (NX ? -c : c) * s.x, acc + (NY ? -c : c) * s.y   (one rounding per component)
-// The packed form writes a fresh register pair (separate output operand) so that a constant
-// `acc` (the DC term of the first tap) needs no copy.
-template <bool NX, bool NY, bool PACKED>
+template <bool NX, bool NY>
 RD_HD rd_f2 rd_tap(float c, rd_f2 s, rd_f2 acc) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (PACKED) {
-        rd_f2 cc = {c, c};
-        rd_f2 r;
-        if (NX && NY) asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "s"(cc), "v"(s), "v"(acc));
-        else if (NX) asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[1,0,0]" : "=v"(r) : "s"(cc), "v"(s), "v"(acc));
-        else if (NY) asm("v_pk_fma_f32 %0, %1, %2, %3 neg_hi:[1,0,0]" : "=v"(r) : "s"(cc), "v"(s), "v"(acc));
-        else asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "s"(cc), "v"(s), "v"(acc));
-        return r;
-    }
-#endif
     acc.x = __builtin_fmaf(NX ? -c : c, s.x, acc.x);
     acc.y = __builtin_fmaf(NY ? -c : c, s.y, acc.y);
     return acc;
@@ -161,7 +131,7 @@ RD_HD rd_f2 rd_tap(float c, rd_f2 s, rd_f2 acc) {
 
 // One FIR output f[t0+R] (R = -1..31) from the converted window w[]: compile-time R so that
 // every phase, sign and tap is a constant.
-template <int R, int RD_NPK>
+template <int R>
 RD_HD rd_f2 rd_fir_out(const rd_f2 *w) {
     // f[t0+R] = sum_m c_m y[t0+R-9+m]; window index of tap m is i = R+1+m
     constexpr int q = (R + 3 + 4) & 3;  // (t-9) mod 4 for the DC term
@@ -173,16 +143,15 @@ RD_HD rd_f2 rd_fir_out(const rd_f2 *w) {
 #define RD_PH(i) (((i) + 2) & 3)
 #define RD_NX(i) (RD_PH(i) == 1 || RD_PH(i) == 2)
 #define RD_NY(i) (RD_PH(i) == 2 || RD_PH(i) == 3)
-    // packed steps are spread over the nine: pair sums first (0..3), then taps 0..4
-    const rd_f2 s0 = rd_pair<false, (RD_NPK > 0)>(w[R + 1], w[R + 9]);
-    const rd_f2 s1 = rd_pair<true, (RD_NPK > 1)>(w[R + 2], w[R + 8]);
-    const rd_f2 s2 = rd_pair<false, (RD_NPK > 2)>(w[R + 3], w[R + 7]);
-    const rd_f2 s3 = rd_pair<true, (RD_NPK > 3)>(w[R + 4], w[R + 6]);
-    acc = rd_tap<RD_NX(R + 1), RD_NY(R + 1), (RD_NPK > 4)>((float)RD_C0, s0, acc);
-    acc = rd_tap<RD_NX(R + 2), RD_NY(R + 2), (RD_NPK > 5)>((float)RD_C1, s1, acc);
-    acc = rd_tap<RD_NX(R + 3), RD_NY(R + 3), (RD_NPK > 6)>((float)RD_C2, s2, acc);
-    acc = rd_tap<RD_NX(R + 4), RD_NY(R + 4), (RD_NPK > 7)>((float)RD_C3, s3, acc);
-    acc = rd_tap<RD_NX(R + 5), RD_NY(R + 5), (RD_NPK > 8)>((float)RD_C4, w[R + 5], acc);
+    const rd_f2 s0 = rd_pair<false>(w[R + 1], w[R + 9]);
+    const rd_f2 s1 = rd_pair<true>(w[R + 2], w[R + 8]);
+    const rd_f2 s2 = rd_pair<false>(w[R + 3], w[R + 7]);
+    const rd_f2 s3 = rd_pair<true>(w[R + 4], w[R + 6]);
+    acc = rd_tap<RD_NX(R + 1), RD_NY(R + 1)>((float)RD_C0, s0, acc);
+    acc = rd_tap<RD_NX(R + 2), RD_NY(R + 2)>((float)RD_C1, s1, acc);
+    acc = rd_tap<RD_NX(R + 3), RD_NY(R + 3)>((float)RD_C2, s2, acc);
+    acc = rd_tap<RD_NX(R + 4), RD_NY(R + 4)>((float)RD_C3, s3, acc);
+    acc = rd_tap<RD_NX(R + 5), RD_NY(R + 5)>((float)RD_C4, w[R + 5], acc);
 #undef RD_PH
 #undef RD_NX
 #undef RD_NY
@@ -202,14 +171,14 @@ struct rd_run_state {
 };
 
 // output R of the run: FIR, guard statistics, sign bit
-template <int R, int NPK, class Src>
+template <int R, class Src>
 RD_HD void rd_fast_step(const Src &win, rd_f2 *w, rd_run_state &st) {
     {   // sample R+9 of the window is converted right before its first use
         constexpr int i = R + 9;
         const float kI = win.f(2 * i), kQ = win.f(2 * i + 1);
         if ((i + 2) & 1) { w[i].x = kQ; w[i].y = kI; } else { w[i].x = kI; w[i].y = kQ; }
     }
-    const rd_f2 acc = rd_fir_out<R, NPK>(w);
+    const rd_f2 acc = rd_fir_out<R>(w);
     st.fmaxv = rd_max3abs(st.fmaxv, acc.x, acc.y);
     if (R >= 0) {
         // numerator of py:89: imag_n*real_np - real_n*imag_np, n = f[t-1], np = f[t]
@@ -224,21 +193,21 @@ RD_HD void rd_fast_step(const Src &win, rd_f2 *w, rd_run_state &st) {
     if ((R & (RD_FENCE_EVERY - 1)) == RD_FENCE_EVERY - 1) RD_SCHED_FENCE();
 }
 
-template <int R, int NPK, class Src>
+template <int R, class Src>
 struct rd_fast_unroll {
     static RD_HDM void run(const Src &win, rd_f2 *w, rd_run_state &st) {
-        rd_fast_step<R, NPK>(win, w, st);
-        rd_fast_unroll<R + 1, NPK, Src>::run(win, w, st);
+        rd_fast_step<R>(win, w, st);
+        rd_fast_unroll<R + 1, Src>::run(win, w, st);
     }
 };
-template <int NPK, class Src>
-struct rd_fast_unroll<RD_RUN, NPK, Src> {
+template <class Src>
+struct rd_fast_unroll<RD_RUN, Src> {
     static RD_HDM void run(const Src &, rd_f2 *, rd_run_state &) {}
 };
 
 // Fast fp32 evaluation of one run.  `win` holds the raw bytes of samples t0-10 .. t0+30
 // (2*RD_WIN bytes, I then Q); t0 % 4 == 0 in absolute stream time.
-template <int NPK = RD_NPK_DEFAULT, class Src>
+template <class Src>
 RD_HD rd_run_result rd_fast_run(const Src &win) {
     rd_f2 w[RD_WIN];
 #pragma unroll
@@ -251,7 +220,7 @@ RD_HD rd_run_result rd_fast_run(const Src &win) {
     st.fmaxv = 0.0f; st.num_even = 0.0f; st.word = 0;
 #pragma unroll
     for (int g = 0; g < RD_GROUPS; g++) st.nminv[g] = 3.0e38f;
-    rd_fast_unroll<-1, NPK, Src>::run(win, w, st);
+    rd_fast_unroll<-1, Src>::run(win, w, st);
     rd_run_result out;
     out.word = rd_bitrev32(st.word);  // bit r = sign of num[t0+r]
     out.fmax = st.fmaxv;

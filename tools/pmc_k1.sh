@@ -1,5 +1,5 @@
 # SQ counters of the fused demod kernel under the bench load (own run: counters only).
-# usage: pmc_k1.sh [tag]   (environment such as RD_K1_IMPL / RD_K1_DEBUG is passed through)
+# usage: pmc_k1.sh [tag]   (environment such as RD_K1_DEBUG / RD_K1_STFLAGS is passed through)
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-sq}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG

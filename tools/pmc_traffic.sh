@@ -1,4 +1,4 @@
-# HBM traffic of k_demod_bits from PMC counters, separate passes (MI355X_MICROARCH.md, HBM section)
+# HBM traffic of the bench load's kernels (k_demod_mfma, k_tail) from PMC counters, separate passes (MI355X_MICROARCH.md, HBM section)
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$C
