@@ -260,13 +260,14 @@ int rd_quantize(const double *in, uint8_t *out, size_t n);
 int rd_search(const rd_config *cfg, const uint8_t *quantized, size_t n, int32_t *indices, int cap, int *count);
 
 /* ---------------------------------------------------------------------------------------------
- * Wideband front end: one uint8 IQ capture at decim * out_rate samples/s ->
+ * Wideband front end: one IQ capture (uint8, int8 or int16) at decim * out_rate samples/s ->
  * one out_rate uint8 IQ stream per channel, e.g. the 51 US hop channels (protocol.py:119-171) out
  * of one 26.88 MS/s capture, written straight into a batch demodulator's input buffer.
  * The reference has no channelizer (it retunes one dongle per hop, runners/rtlsdr.py:51,72):
  * parity is unpinned; the definition is in rtldavis_amd/csrc/rd_channelizer.hip and restated in
  * float64 by oracle/channelizer_oracle.py.  It runs on the matrix cores (f16 MFMA with the taps split
- * into two f16 digits, 2^-22 relative; the 8-bit samples are exact in f16, accumulation is fp32).
+ * into two f16 digits, 2^-22 relative; the samples are exact in f16 - a 16-bit one as two 8-bit sign-magnitude
+ * digits -, accumulation is fp32).
  * Contract: with Z the float64 model's value in front of the quantiser (channelize_z), every output byte
  * is within one step of clip(rint(Z), 0, 255), and equals it wherever Z lies more than delta from every
  * rounding boundary k + 1/2; delta, a few hundredths of a step at 512 taps, is derived from the kernel's
@@ -282,15 +283,33 @@ typedef struct rd_chan_config {
 } rd_chan_config;
 typedef struct rd_chan rd_chan;
 
+/* Sample format of the wideband capture (the output is uint8 whatever the input):
+ *   RD_IQ_U8   uint8 I, Q                    x = (I - 127.4) / 127.6 + j (Q - 127.4) / 127.6   (RTL-SDR; dsp.py:20-39)
+ *   RD_IQ_S8   int8 I, Q                     x = I / 128 + j Q / 128                           (sc8 / CS8)
+ *   RD_IQ_S16  int16 I, Q, host byte order   x = I / 32768 + j Q / 32768                       (sc16 / CS16)
+ * Everything behind x - filter, mixer, gain, output quantiser, the contract above - is the same; the bound of a
+ * format is tests/chan_bound_fmt.py:error_bound_fmt. */
+#define RD_IQ_U8 0
+#define RD_IQ_S8 1
+#define RD_IQ_S16 2
+
 /* taps: n_taps doubles; shift_hz[c]: the wideband frequency (Hz, relative to the capture's centre)
  * that channel c moves to 0 Hz of its output - for rtldavis the channel centre plus out_rate / 4,
  * because the demodulator's Fs/4 rotation (dsp.py:42-49) expects the carrier at -Fs/4.  No device
- * work (safe before fork). */
+ * work (safe before fork).  rd_chan_create is rd_chan_create_fmt with RD_IQ_U8. */
 int rd_chan_create(const rd_chan_config *cfg, const double *taps, const int64_t *shift_hz, rd_chan **out);
+/* The same for a capture in sample_format (another value: RD_ERR_ARG).  Limits, all formats: decim a multiple of 4
+ * in 4 .. 4096, 1 .. 8192 taps, 1 .. 4096 channels, out_rate < 2^26; with t_pad = n_taps rounded up to 8:
+ *   RD_IQ_U8, RD_IQ_S8  2 (127 decim + t_pad + 8) + 16 <= 160 KiB of LDS, and ceil((t_pad - 1) / decim) <= 64
+ *   RD_IQ_S16           8 (127 decim + t_pad + 4) + 16 <= 160 KiB of LDS (a sample is staged as four 16-bit lanes)
+ *                       and no limit on n_taps / decim (there is no DC term to tabulate). */
+int rd_chan_create_fmt(const rd_chan_config *cfg, int sample_format, const double *taps, const int64_t *shift_hz,
+                       rd_chan **out);
 void rd_chan_destroy(rd_chan *h);
-/* Host -> device copy of a capture (uint8 I,Q interleaved), or the device address of the resident
- * capture buffer (at least n_wide_samples) for a producer on the GPU. */
-int rd_chan_upload(rd_chan *h, const uint8_t *wide_iq, size_t nbytes);
+/* Host -> device copy of a capture (I,Q interleaved, in the handle's format; nbytes a whole number of its IQ
+ * pairs, else RD_ERR_ARG "Incompatible array sizes"), or the device address of the resident capture buffer (at
+ * least n_wide_samples IQ pairs of that format) for a producer on the GPU. */
+int rd_chan_upload(rd_chan *h, const void *wide_iq, size_t nbytes);
 int rd_chan_input_ptr(rd_chan *h, size_t n_wide_samples, void **dev_ptr);
 /* Channelize output samples 0 .. n_out-1 (n_out <= capture length / decim; zero history before
  * the capture) of every channel into device memory: channel c at dst_dev + c * dst_stream_stride,
@@ -309,18 +328,22 @@ int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, size_t nbytes)
  * for the channelizer.
  * ------------------------------------------------------------------------------------------- */
 typedef struct rd_wideband rd_wideband;
-/* no device work (safe before fork), like rd_create / rd_chan_create; block_size % 128 == 0 */
+/* no device work (safe before fork), like rd_create / rd_chan_create; block_size % 128 == 0.  rd_wideband_create is
+ * rd_wb_create_fmt with RD_IQ_U8; rd_wb_create_fmt takes chunks in sample_format (limits: rd_chan_create_fmt) and
+ * returns the same handle type, which every rd_wideband_* call below takes. */
 int rd_wideband_create(const rd_config *cfg, const rd_chan_config *ccfg, const double *taps,
                        const int64_t *shift_hz, rd_wideband **out);
+int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg, int sample_format, const double *taps,
+                     const int64_t *shift_hz, rd_wideband **out);
 void rd_wideband_destroy(rd_wideband *w);
 /* clock to 0, history to zero, demod state as rd_reset (waits for the chunks in flight) */
 int rd_wideband_reset(rd_wideband *w);
-/* one chunk: uint8 I,Q of decim * block_size wideband samples (else RD_ERR_ARG "Incompatible array
- * sizes"); host->device copy, channelize (streaming form), one demod launch - all queued on the
+/* one chunk: I,Q of decim * block_size wideband samples in the handle's format, i.e. (2 or, for RD_IQ_S16, 4)
+ * * decim * block_size bytes (else RD_ERR_ARG "Incompatible array sizes"); host->device copy, channelize (streaming form), one demod launch - all queued on the
  * handle's own non-blocking streams, returns at once.  At most two chunks in flight (a third:
  * RD_ERR_STATE); the copy of chunk k+1 overlaps chunk k's kernels.  The clock and the history
  * advance here, so a fetch that times out loses only that chunk's packets. */
-int rd_wideband_submit(rd_wideband *w, const uint8_t *wide_iq, size_t nbytes);
+int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nbytes);
 /* as rd_demod_fetch / rd_demod_refetch: packets of the oldest chunk in flight, stream = channel, call = chunk */
 int rd_wideband_fetch(rd_wideband *w, rd_packet *out, int cap, int *n);
 int rd_wideband_refetch(rd_wideband *w, rd_packet *out, int cap, int *n);

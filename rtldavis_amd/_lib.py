@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RTLDAVIS_HIP_LIB overrides the path (A/B builds of the kernels); the default is the in-tree build
 LIB_PATH = os.environ.get("RTLDAVIS_HIP_LIB") or os.path.join(HERE, "librtldavis_hip.so")
@@ -45,6 +47,34 @@ class RdTiming(C.Structure):
 class RdChanConfig(C.Structure):
     _fields_ = [("out_rate", C.c_int32), ("decim", C.c_int32), ("n_taps", C.c_int32), ("n_channels", C.c_int32),
                 ("gain", C.c_double)]
+
+
+# rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
+RD_IQ_U8, RD_IQ_S8, RD_IQ_S16 = 0, 1, 2
+SAMPLE_FORMATS = {"u8": (RD_IQ_U8, np.uint8), "s8": (RD_IQ_S8, np.int8), "s16": (RD_IQ_S16, np.int16)}
+
+
+def sample_format(name):
+    """(code, dtype) of a sample format name; ValueError for an unknown one."""
+    try:
+        return SAMPLE_FORMATS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown sample format {name!r}: one of {sorted(SAMPLE_FORMATS)}") from None
+
+
+def iq_array(a, dtype):
+    """A capture as a flat contiguous array of ``dtype`` (I,Q interleaved; [n, 2] or flat in).  Integer arrays of
+    another width whose values fit are converted; anything else (complex, float, out of range) is a ValueError -
+    never a silent cast.  (uint8 keeps the conversion it always had: numpy's cast.)"""
+    if np.dtype(dtype) == np.uint8:
+        return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        info = np.iinfo(dtype)
+        if a.dtype.kind not in "iu" or (a.size and (a.min() < info.min or a.max() > info.max)):
+            raise ValueError(f"a {a.dtype} array is not a capture of {np.dtype(dtype).name} samples")
+        a = a.astype(dtype)
+    return np.ascontiguousarray(a).reshape(-1)
 
 
 # name -> (restype, argtypes); exactly the functions include/rtldavis_hip.h declares
@@ -95,12 +125,14 @@ SIGNATURES = {
     "rd_quantize": (C.c_int, [_P, _P, C.c_size_t]),
     "rd_search": (C.c_int, [C.POINTER(RdConfig), _P, C.c_size_t, _P, C.c_int, C.POINTER(C.c_int)]),
     "rd_chan_create": (C.c_int, [C.POINTER(RdChanConfig), _P, _P, C.POINTER(_P)]),
+    "rd_chan_create_fmt": (C.c_int, [C.POINTER(RdChanConfig), C.c_int, _P, _P, C.POINTER(_P)]),
     "rd_chan_destroy": (None, [_P]),
     "rd_chan_upload": (C.c_int, [_P, _P, C.c_size_t]),
     "rd_chan_input_ptr": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "rd_chan_run": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "rd_chan_run_host": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
     "rd_wideband_create": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), _P, _P, C.POINTER(_P)]),
+    "rd_wb_create_fmt": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), C.c_int, _P, _P, C.POINTER(_P)]),
     "rd_wideband_destroy": (None, [_P]),
     "rd_wideband_reset": (C.c_int, [_P]),
     "rd_wideband_submit": (C.c_int, [_P, _P, C.c_size_t]),

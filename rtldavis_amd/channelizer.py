@@ -1,4 +1,4 @@
-"""Wideband front end: one uint8 IQ capture -> one 268.8 kSPS uint8 IQ stream
+"""Wideband front end: one IQ capture (uint8, int8 or int16) -> one 268.8 kSPS uint8 IQ stream
 per hop channel, channelized on the GPU straight into a BatchDemodulator's input buffer.
 
 rtldavis itself has no channelizer: it retunes one narrow-band dongle per hop
@@ -66,15 +66,18 @@ def chan_config(plan) -> _lib.RdChanConfig:
 class Channelizer:
     """``Channelizer(channels_hz, centre_hz)`` moves each channel's centre to -out_rate/4, where the
     demodulator's Fs/4 rotation (dsp.py:42-49) expects the carrier, low-passes, decimates by
-    ``decim`` and re-quantises to uint8 with ``gain``."""
+    ``decim`` and re-quantises to uint8 with ``gain``.  ``sample_format`` is the capture's: ``"u8"`` (RTL-SDR offset
+    bytes, x = (k - 127.4) / 127.6), ``"s8"`` (int8, x = k / 128) or ``"s16"`` (int16, x = k / 32768)."""
 
     def __init__(self, channels_hz: Sequence[int] = US_CHANNELS_HZ, centre_hz: int = DEFAULT_CENTRE_HZ,
                  decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0,
-                 out_rate: int = OUT_RATE, if_hz: Optional[int] = None) -> None:
-        plan_channels(self, channels_hz, centre_hz, decim, taps, gain, out_rate, if_hz)
+                 out_rate: int = OUT_RATE, if_hz: Optional[int] = None, sample_format: str = "u8") -> None:
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rd_chan_create(C.byref(chan_config(self)), self.taps.ctypes.data, self.shift_hz.ctypes.data,
-                                             C.byref(self._h)))
+        self.sample_format = sample_format
+        self._fmt, self.dtype = _lib.sample_format(sample_format)
+        plan_channels(self, channels_hz, centre_hz, decim, taps, gain, out_rate, if_hz)
+        _lib.check(_lib.lib().rd_chan_create_fmt(C.byref(chan_config(self)), self._fmt, self.taps.ctypes.data,
+                                                 self.shift_hz.ctypes.data, C.byref(self._h)))
         self.n_wide = 0
 
     def __del__(self):
@@ -86,9 +89,9 @@ class Channelizer:
             pass
 
     def upload(self, wide_iq: np.ndarray) -> None:
-        """Copy a capture (uint8, I,Q interleaved) to the device."""
-        a = np.ascontiguousarray(wide_iq, dtype=np.uint8).reshape(-1)
-        _lib.check(_lib.lib().rd_chan_upload(self._h, a.ctypes.data, a.size))
+        """Copy a capture (``self.dtype``, I,Q interleaved: flat or [n, 2]) to the device."""
+        a = _lib.iq_array(wide_iq, self.dtype)
+        _lib.check(_lib.lib().rd_chan_upload(self._h, a.ctypes.data, a.nbytes))
         self.n_wide = a.size // 2
 
     def run_host(self, n_out: Optional[int] = None) -> np.ndarray:

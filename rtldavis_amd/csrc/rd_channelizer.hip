@@ -1,4 +1,4 @@
-// rd_channelizer.hip - wideband front end: one uint8 IQ capture at
+// rd_channelizer.hip - wideband front end: one IQ capture (uint8, int8 or int16) at
 // decim x 268.8 kSPS -> one 268.8 kSPS uint8 IQ stream per hop channel, written straight into a
 // batch demodulator's resident input buffer.
 //
@@ -7,7 +7,9 @@
 // repo's own, restated in float64 by oracle/channelizer_oracle.py, and the tests tie it to the
 // reference through the packets the reference demodulator recovers from its output.
 //
-//   x[n]   = lut(I[n]) + j lut(Q[n]),  lut(k) = (k - 127.4) / 127.6        (dsp.py:20-39)
+//   x[n]   = lut(I[n]) + j lut(Q[n]),  lut(k) = (k - 127.4) / 127.6        (RD_IQ_U8: uint8, dsp.py:20-39)
+//                                       lut(k) = k / 128                    (RD_IQ_S8: int8)
+//                                       lut(k) = k / 32768                  (RD_IQ_S16: int16, host byte order)
 //   z_c[t] = sum_{k<T} h[k] x[D t - k] e^{-j 2 pi shift_c (D t - k) / Fw}    (x[n<0] = 0)
 //          = e^{-j 2 pi frac(shift_c t / Fo)} sum_k g_c[k] x[D t - k],   g_c[k] = h[k] e^{+j 2 pi shift_c k / Fw}
 //   out_c[t] = clip(rint(gain z 127.6 + 127.4), 0, 255) per component       (the synth's quantiser)
@@ -49,11 +51,37 @@
 // through a shared LDS chunk two steps ahead instead of one 0.55 -> 0.46, samples pre-converted in
 // LDS 0.36, 128 instead of 256 output times per workgroup 0.27, A per wave from L2 without LDS or
 // barriers 0.25 (three bf16 tap terms); two f16 tap terms: see DESIGN.
+//
+// The signed formats (template parameter FMT).  RD_IQ_S8: bit 7 of every byte is flipped while the window is staged (one
+// v_xor per dword of the 16-byte vectors), which makes it offset-binary uint8; the loop is the uint8 one, the DC term
+// -128 (1 + j) sum g, the scale 1/128.  A sample outside the capture is staged as 0x80, the value 0, so the table of early
+// DC terms holds the steady one throughout.  Measured equal to uint8 (0.151 ms both, profiles/channelizer_formats.txt).
+// RD_IQ_S16 stays an f16 MFMA GEMM on exact operands: an int16 is no f16, so a component s = sg (256 mh + ml) enters as
+// two SIGN-MAGNITUDE digits, the f16 patterns sg | ml and sg | mh - the subnormals -+ m 2^-24, so the raw-pattern trick
+// survives - and K doubles: kappa = 4 i + 2 comp + digit, four window samples per K = 16 step.  The conversion happens
+// once per staged sample (abs, and, shift, or); LDS holds the four 16-bit lanes Ilo Ihi Qlo Qhi of a sample, 8 bytes, in
+// fragment order, so a B fragment is one aligned ds_read_b128 and no VALU work at all.  The low digit's taps are scaled
+// 2^-8 against the high digit's (a second power-of-two scale; 256 x the taps would overflow f16), both in two f16 terms.
+// There is no DC term: zero history is the digit 0.  -32768 is mh = 128, ml = 0.
+// Why signed digits: with offset binary (s + 32768 = 256 (hi ^ 0x80) + lo, both bytes subnormals as for uint8) the fp32
+// accumulator carries 32768 sum g while a real signal is a few hundred counts, and the accumulation term of the bound
+// scales with full scale: on the weak default-plan capture (437 counts, gain 300) it exempts a third of the bytes;
+// signed digits keep every partial sum at signal size (derived bound there: median 2e-4, max 7e-3 LSB, 0.13 % exempt,
+// tests/chan_bound_fmt.py).  Rejected: offset binary (above); two's-complement bytes (hi signed, lo unsigned: the low
+// digit alone swings by 255 per sample, and a signed byte needs a conversion per fragment); balanced signed bytes
+// converted per fragment (32767 = 256 x 128 - 1 does not fit a signed hi byte, and the per-fragment VALU work is what
+// round 3 removed from the uint8 loop); sign-magnitude kept as 4 bytes with the lanes rebuilt per fragment (three VALU
+// ops per dword, and -32768 has no 16-bit sign-magnitude form).  The price of 8 bytes per sample: the default plan's
+// window is 106 KiB, one workgroup per CU, and decim <= 160.  Lane stride 2 D dwords (D = 100: 200 = 8 mod 64): the
+// b128 reads are 2-way bank conflicted by the bank rule (not measured).  Measured: 0.40 ms per second of capture,
+// 2.66 x uint8 - twice the MFMAs on twice the bytes, the rest at one wave per SIMD; 2480 x real time.  Not tried: a
+// 64-output tile (two workgroups per CU, but twice the A traffic from L2).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include <unistd.h>
 
@@ -67,7 +95,7 @@ extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_
 #define RD_CHAN_TB 4                        // 32-time blocks per wave
 #define RD_CHAN_TT (32 * RD_CHAN_TB)        // output times per workgroup
 #define RD_CHAN_RBG 4                       // row blocks (32 rows = 16 channels) per workgroup: one per wave
-#define RD_CHAN_KC 8                        // window samples per K step (taps are padded to a multiple)
+#define RD_CHAN_KC 8                        // window samples per K step of the 8-bit formats (taps are padded to a multiple)
 #define RD_CHAN_TERMS 2                     // f16 digits per tap
 #define RD_CHAN_Q_BYTES (RD_CHAN_TERMS * RD_CHAN_RBG * 64 * 16)  // A bytes per K step: terms x 4 row blocks x 64 lanes x 16 B
 #ifndef RD_CHAN_NPF
@@ -80,12 +108,18 @@ extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_
 #define RD_CHAN_DCN (RD_CHAN_EARLY + 2)     // table entries per channel: the early DC terms, the steady one, and the
                                             // phasor of 32 output times e^{-j 2 pi frac(32 shift / Fo)} (cos, sin)
 
+// per sample format (rtldavis_hip.h: RD_IQ_*): bytes of an IQ pair in memory and staged in LDS, window samples per K step
+__host__ __device__ constexpr int rd_fmt_in_bps(int f) { return f == RD_IQ_S16 ? 4 : 2; }
+__host__ __device__ constexpr int rd_fmt_lds_bps(int f) { return f == RD_IQ_S16 ? 8 : 2; }
+__host__ __device__ constexpr int rd_fmt_kc(int f) { return f == RD_IQ_S16 ? RD_CHAN_KC / 2 : RD_CHAN_KC; }
+
 typedef float rd_f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 rd_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 rd_f16x2 __attribute__((ext_vector_type(2)));
 
 struct rd_chan {
     rd_chan_config cfg;
+    int fmt = RD_IQ_U8;            // sample format of the capture
     int n_groups = 0;              // groups of 64 channels
     int t_pad = 0;                 // taps rounded up to RD_CHAN_KC (zero taps appended)
     int n_early = 0;               // outputs whose window reaches before the capture: ceil((t_pad - 1) / D)
@@ -96,7 +130,7 @@ struct rd_chan {
     uint16_t *d_amat = nullptr;
     float *d_dc = nullptr;
     int64_t *d_shifts = nullptr;
-    uint8_t *d_wide = nullptr;     // resident capture, 2 bytes per sample
+    uint8_t *d_wide = nullptr;     // resident capture, rd_fmt_in_bps bytes per sample
     size_t wide_cap = 0, wide_n = 0;
     bool dev_ready = false;
     int device = -1;               // the device the buffers live on
@@ -125,7 +159,21 @@ __device__ __forceinline__ double rd_chan_mod(double x, double m) {
 // unless t_base is 0.  A chunk is a whole number of workgroups (block_size % RD_CHAN_TT == 0, so n_wide and every window
 // start are multiples of 8 samples): an 8-sample vector lies wholly in `prev`, in `wide` or past the chunk, where the
 // taps are zero - the streamed bytes equal the one-shot form's on the whole capture.
-template <bool STREAM>
+//
+// FMT (header: the formats): RD_IQ_S8 flips bit 7 of every byte while staging - the window is then offset-binary uint8
+// (a sample outside the capture becomes 0x80 = the value 0, so the DC table holds the steady term throughout) and the
+// main loop is the uint8 one.  RD_IQ_S16 stages a sample as four 16-bit lanes Ilo Ihi Qlo Qhi, each the f16 pattern
+// sign | digit of the component's sign-magnitude form, converted once per staged sample: a B fragment is then one
+// aligned ds_read_b128 (two samples) and nothing else, a K step covers 4 window samples, there is no DC term.
+// The sample dword of an int16 pair -> the two LDS dwords (lo | hi << 16 of I, of Q)
+__device__ __forceinline__ uint2 rd_chan_sm16(uint32_t w) {
+    const int si = (int)(int16_t)(w & 0xFFFFu), sq = (int)w >> 16;
+    const uint32_t mi = (uint32_t)(si < 0 ? -si : si), mq = (uint32_t)(sq < 0 ? -sq : sq);   // 0 .. 32768
+    return uint2{(si < 0 ? 0x80008000u : 0u) | (mi & 0xFFu) | ((mi >> 8) << 16),
+                 (sq < 0 ? 0x80008000u : 0u) | (mq & 0xFFu) | ((mq >> 8) << 16)};
+}
+
+template <bool STREAM, int FMT>
 __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint8_t *__restrict__ wide, long n_wide,
                                                     const uint4 *__restrict__ amat, const float2 *__restrict__ dc,
                                                     const int64_t *shifts, int T, int D, int n_ch, int n_early,
@@ -133,7 +181,9 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
                                                     uint8_t *out, size_t out_stride, int xs_bytes,
                                                     const uint8_t *__restrict__ prev, long t_base_mod) {
     extern __shared__ uint8_t lds[];
-    uint8_t *xs = lds;                            // window samples 0 .. span-1, two bytes each (I, Q)
+    uint8_t *xs = lds;                            // window samples 0 .. span-1, LB bytes each
+    constexpr int IB = rd_fmt_in_bps(FMT), LB = rd_fmt_lds_bps(FMT), KC = rd_fmt_kc(FMT);
+    constexpr int VS = 16 / IB;                   // samples per 16-byte vector of the capture
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // = row block
     const int r = lane & 31, h = lane >> 5;
@@ -141,21 +191,26 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
     const int grp = blockIdx.y;
     // stage samples n0 .. n0 + span - 1; a sample before the capture (or after it) is the byte 0 = no contribution
     const long n0 = (long)D * t0 - T;
-    const int span = (RD_CHAN_TT - 1) * D + T + RD_CHAN_KC;
-    const int n_vec = (span + 7) / 8;
+    const int span = (RD_CHAN_TT - 1) * D + T + KC;
+    const int n_vec = (span + VS - 1) / VS;
     for (int q0 = threadIdx.x; q0 < n_vec; q0 += 4 * blockDim.x) {
         uint4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int q = q0 + u * blockDim.x;
-            const long n = n0 + 8L * q;
+            const long n = n0 + (long)VS * q;
             v[u] = uint4{0u, 0u, 0u, 0u};
             if constexpr (STREAM) {
-                const uint8_t *src = n >= 0 ? wide + 2 * n : (prev ? prev + 2 * (n + n_wide) : nullptr);
-                if (q < n_vec && src && n >= -n_wide && n + 8 <= n_wide) v[u] = *(const uint4 *)src;
+                const uint8_t *src = n >= 0 ? wide + IB * n : (prev ? prev + IB * (n + n_wide) : nullptr);
+                if (q < n_vec && src && n >= -n_wide && n + VS <= n_wide) v[u] = *(const uint4 *)src;
             } else if (q < n_vec) {
-                if (n >= 0 && n + 8 <= n_wide) {
-                    v[u] = *(const uint4 *)(wide + 2 * n);
+                if (n >= 0 && n + VS <= n_wide) {
+                    v[u] = *(const uint4 *)(wide + IB * n);
+                } else if constexpr (FMT == RD_IQ_S16) {
+                    uint32_t e[4];
+#pragma unroll
+                    for (int w = 0; w < 4; w++) e[w] = (n + w >= 0 && n + w < n_wide) ? *(const uint32_t *)(wide + 4 * (n + w)) : 0u;
+                    v[u] = uint4{e[0], e[1], e[2], e[3]};
                 } else {
                     uint16_t e[8];
 #pragma unroll
@@ -168,10 +223,20 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int q = q0 + u * blockDim.x;
-            if (q < n_vec) *(uint4 *)(xs + 16 * q) = v[u];
+            if (q >= n_vec) continue;
+            if constexpr (FMT == RD_IQ_S16) {
+                const uint2 a = rd_chan_sm16(v[u].x), b = rd_chan_sm16(v[u].y), c = rd_chan_sm16(v[u].z), d = rd_chan_sm16(v[u].w);
+                *(uint4 *)(xs + 32 * q) = uint4{a.x, a.y, b.x, b.y};
+                *(uint4 *)(xs + 32 * q + 16) = uint4{c.x, c.y, d.x, d.y};
+            } else {
+                if constexpr (FMT == RD_IQ_S8) {
+                    v[u].x ^= 0x80808080u; v[u].y ^= 0x80808080u; v[u].z ^= 0x80808080u; v[u].w ^= 0x80808080u;
+                }
+                *(uint4 *)(xs + 16 * q) = v[u];
+            }
         }
     }
-    const int n_chunks = T / RD_CHAN_KC + 1;
+    const int n_chunks = T / KC + 1;
     const uint4 *asrc = amat + (size_t)grp * n_chunks * (RD_CHAN_Q_BYTES / 16);
     // A wave only ever needs ITS row block's A fragments (RD_CHAN_TERMS x 16 bytes per lane and K step):
     // they come straight from L2 into registers, NPF steps ahead - no LDS, no barrier in the loop.
@@ -192,7 +257,8 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         for (int e = 0; e < 16; e++) acc[b][e] = 0.0f;
     // B fragment of (time block tb, K step q): window samples 8q + 4h .. +3 of column 32 tb + r = eight bytes
     // (I0 Q0 I1 Q1 | I2 Q2 I3 Q3) -> eight 16-bit lanes
-    const uint8_t *xl = xs + 2 * (D * r + 4 * h);
+    // (RD_IQ_S16: window samples 4q + 2h, + 1 = sixteen bytes = the eight 16-bit lanes as they are)
+    const uint8_t *xl = xs + LB * (D * r + (KC / 2) * h);
     for (int c0 = 0; c0 < n_chunks; c0 += NPF) {
 #pragma unroll
         for (int s = 0; s < NPF; s++) {
@@ -208,18 +274,23 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
                 for (int term = 0; term < RD_CHAN_TERMS; term++)
                     pre[s][term] = amine[(size_t)(qn * RD_CHAN_TERMS + term) * (RD_CHAN_RBG * 64)];
             }
-            uint2 raw[RD_CHAN_TB];
+            using raw_t = typename std::conditional<FMT == RD_IQ_S16, uint4, uint2>::type;
+            raw_t raw[RD_CHAN_TB];
 #pragma unroll
-            for (int tb = 0; tb < RD_CHAN_TB; tb++) raw[tb] = *(const uint2 *)(xl + 2 * (D * 32 * tb + 8 * q));
+            for (int tb = 0; tb < RD_CHAN_TB; tb++) raw[tb] = *(const raw_t *)(xl + LB * (D * 32 * tb + KC * q));
 #pragma unroll
             for (int tb = 0; tb < RD_CHAN_TB; tb++) {
                 uint4 f;
-                // element order (I0 I1 Q0 Q1 | I2 I3 Q2 Q3) - the A fragments are laid out to match: the even bytes of a
-                // dword by one v_and, the odd ones by one v_perm (selector 0x0c = a zero byte), as in rd_mf_frag
-                f.x = raw[tb].x & 0x00FF00FFu;
-                f.y = __builtin_amdgcn_perm(0u, raw[tb].x, 0x0c030c01u);
-                f.z = raw[tb].y & 0x00FF00FFu;
-                f.w = __builtin_amdgcn_perm(0u, raw[tb].y, 0x0c030c01u);
+                if constexpr (FMT == RD_IQ_S16) {
+                    f = raw[tb];
+                } else {
+                    // element order (I0 I1 Q0 Q1 | I2 I3 Q2 Q3) - the A fragments are laid out to match: the even bytes of
+                    // a dword by one v_and, the odd ones by one v_perm (selector 0x0c = a zero byte), as in rd_mf_frag
+                    f.x = raw[tb].x & 0x00FF00FFu;
+                    f.y = __builtin_amdgcn_perm(0u, raw[tb].x, 0x0c030c01u);
+                    f.z = raw[tb].y & 0x00FF00FFu;
+                    f.w = __builtin_amdgcn_perm(0u, raw[tb].y, 0x0c030c01u);
+                }
                 const rd_f16x8 bfrag = __builtin_bit_cast(rd_f16x8, f);
 #pragma unroll
                 for (int term = 0; term < RD_CHAN_TERMS; term++)
@@ -229,7 +300,7 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
     }
     // epilogue: register e of tile tb holds row (e & 3) + 8 (e >> 2) + 4 h, column r; rows 2i, 2i+1 =
     // (re, im) of channel 16 (4 grp + wave) + i
-    const float scale = gain * (1.0f / 127.6f);
+    const float scale = gain * (FMT == RD_IQ_U8 ? 1.0f / 127.6f : FMT == RD_IQ_S8 ? 1.0f / 128.0f : 1.0f / 32768.0f);
     // The output phasor e^{-j 2 pi frac(shift t / Fo)}: the exact remainder once per channel and lane, for the lane's
     // first time block (one float64 product, a quotient by multiplication, the hardware sine and cosine); the three
     // blocks behind it are 32 output times further on each - a rotation by the channel's constant from the table.
@@ -266,7 +337,8 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         for (int tb = 0; tb < RD_CHAN_TB; tb++) {
             const long t = t0 + 32 * tb + r;
             if (t < n_out) {
-                const float2 d0 = dcc[t < n_early ? (int)t : RD_CHAN_EARLY];
+                float2 d0 = float2{0.0f, 0.0f};   // (RD_IQ_S16: signed digits, no DC term)
+                if constexpr (FMT != RD_IQ_S16) d0 = dcc[t < n_early ? (int)t : RD_CHAN_EARLY];
                 const float re = __builtin_fmaf(acc[tb][e], tap_unscale, d0.x), im = __builtin_fmaf(acc[tb][e + 1], tap_unscale, d0.y);
                 const float zr = (re * cs - im * sn) * scale, zi = (re * sn + im * cs) * scale;
                 const float qr = fminf(fmaxf(rintf(zr * 127.6f + 127.4f), 0.0f), 255.0f);
@@ -300,25 +372,40 @@ static double f16_val(uint16_t b) {
     return (double)h;
 }
 
+// LDS bytes of a workgroup's staged window (a multiple of 16, one spare vector)
+static size_t chan_lds_bytes(int fmt, int decim, int t_pad) {
+    const size_t span = (size_t)(RD_CHAN_TT - 1) * decim + t_pad + rd_fmt_kc(fmt);
+    return (rd_fmt_lds_bps(fmt) * span + 15 + 16) & ~(size_t)15;
+}
+
 extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, const int64_t *shift_hz, rd_chan **out) {
+    return rd_chan_create_fmt(cfg, RD_IQ_U8, taps, shift_hz, out);
+}
+
+extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const double *taps, const int64_t *shift_hz,
+                                  rd_chan **out) {
     if (!cfg || !taps || !shift_hz || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (fmt != RD_IQ_U8 && fmt != RD_IQ_S8 && fmt != RD_IQ_S16) return rd_fail_msg(RD_ERR_ARG, "unknown sample format %d", fmt);
     if (cfg->decim < 4 || cfg->decim > 4096 || cfg->decim % 4 || cfg->n_taps < 1 || cfg->n_taps > 8192 ||
         cfg->n_channels < 1 || cfg->n_channels > 4096 || cfg->out_rate < 1 || cfg->out_rate >= (1 << 26) ||
         !(cfg->gain > 0.0))
         return rd_fail_msg(RD_ERR_ARG, "channelizer config out of range (decim: a multiple of 4)");
     const int t_pad = (cfg->n_taps + RD_CHAN_KC - 1) / RD_CHAN_KC * RD_CHAN_KC;
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * cfg->decim + t_pad + RD_CHAN_KC;
-    if (2 * span + 16 > 160 * 1024)
-        return rd_fail_msg(RD_ERR_ARG, "decim x 255 + n_taps samples do not fit the 160 KiB LDS");
-    const int n_early = (t_pad - 1 + cfg->decim - 1) / cfg->decim;
+    const int kc = rd_fmt_kc(fmt);
+    const size_t span = (size_t)(RD_CHAN_TT - 1) * cfg->decim + t_pad + kc;
+    if (rd_fmt_lds_bps(fmt) * span + 16 > 160 * 1024)
+        return rd_fail_msg(RD_ERR_ARG, "decim x 127 + n_taps samples of %d bytes do not fit the 160 KiB LDS", rd_fmt_lds_bps(fmt));
+    // (RD_IQ_S16 has no DC term, hence no table of early ones and no limit from it)
+    const int n_early = fmt == RD_IQ_S16 ? 0 : (t_pad - 1 + cfg->decim - 1) / cfg->decim;
     if (n_early > RD_CHAN_EARLY) return rd_fail_msg(RD_ERR_ARG, "n_taps / decim too large");
     rd_chan *h = new rd_chan();
     h->cfg = *cfg;
+    h->fmt = fmt;
     const int T = cfg->n_taps;
     h->t_pad = t_pad;
     h->n_early = n_early;
     h->n_groups = (cfg->n_channels + 16 * RD_CHAN_RBG - 1) / (16 * RD_CHAN_RBG);
-    const int n_q = t_pad / 8 + 1;  // the window starts one sample early (aligned): one more K step
+    const int n_q = t_pad / kc + 1;  // the window starts one sample early (aligned): one more K step
     h->h_amat.assign((size_t)h->n_groups * n_q * (RD_CHAN_Q_BYTES / 2), 0);
     h->h_dc.assign((size_t)cfg->n_channels * RD_CHAN_DCN * 2, 0.0f);
     h->shifts.resize(cfg->n_channels);  // shift mod Fo in [0, Fo): all the output phasor needs
@@ -333,7 +420,10 @@ extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, con
     if (sexp > 60) sexp = 60;
     if (sexp < -60) sexp = -60;
     const double tap_scale = std::ldexp(1.0, sexp);
-    h->tap_unscale = (float)std::ldexp(1.0, -sexp + 24);  // (+24: the samples enter as k 2^-24)
+    // (+24: the samples enter as k 2^-24; RD_IQ_S16: the low digit's taps carry 2^-8 more, so that the high digit's
+    // factor 256 stays inside f16)
+    h->tap_unscale = (float)std::ldexp(1.0, -sexp + 24 + (fmt == RD_IQ_S16 ? 8 : 0));
+    const double dc_level = fmt == RD_IQ_U8 ? 127.4 : fmt == RD_IQ_S8 ? 128.0 : 0.0;
     std::vector<double> gr(t_pad), gi(t_pad);
     for (int c = 0; c < cfg->n_channels; c++) {
         for (int k = 0; k < t_pad; k++) {
@@ -352,11 +442,13 @@ extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, con
         double sr = 0.0, si = 0.0;
         int kdone = 0;
         for (int t = 0; t <= RD_CHAN_EARLY; t++) {
-            const long kmax = t < RD_CHAN_EARLY ? (long)cfg->decim * t : (long)t_pad - 1;
+            // (RD_IQ_S8 stages 0x80 = the value 0 before the capture: every output sees all the taps)
+            const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)cfg->decim * t : (long)t_pad - 1;
             for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += gr[kdone]; si += gi[kdone]; }
             // lut(b) = (b - 127.4) / 127.6 and the kernel sums g b: the constant is -127.4 (1 + j)(sr + j si)
-            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2] = (float)(-127.4 * (sr - si));
-            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2 + 1] = (float)(-127.4 * (sr + si));
+            // (128 for the offset-binary bytes of RD_IQ_S8, nothing for RD_IQ_S16)
+            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2] = (float)(-dc_level * (sr - si));
+            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2 + 1] = (float)(-dc_level * (sr + si));
         }
         {   // the rotation that takes the output phasor 32 output times on (exact remainder, float64 sin / cos)
             const long inc = (long)(((__int128)h->shifts[c] * 32) % cfg->out_rate);
@@ -366,23 +458,29 @@ extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, con
         }
         // rows 2c (re) and 2c+1 (im); kappa = 2 i + comp, window sample i = t_pad - 1 - k
         const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
-        for (int i = 0; i < 8 * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
+        // RD_IQ_S16: kappa = 4 i + 2 comp + digit, a lane holds two samples (Ilo Ihi Qlo Qhi each); the low digit's taps
+        // are scaled by 2^-8 against the high digit's
+        const int per_lane = kc / 2, n_dig = fmt == RD_IQ_S16 ? 2 : 1;
+        for (int i = 0; i < kc * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
             const int k = t_pad - i;
             if (k < 0 || k >= t_pad) continue;  // (zero taps: the entries stay 0)
-            const int q = i / 8, hh = (i % 8) / 4, s4 = i % 4;  // K step, lane half, sample within the lane's four
+            const int q = i / kc, hh = (i % kc) / per_lane, sl = i % per_lane;  // K step, lane half, sample within the lane's
             for (int part = 0; part < 2; part++)
-                for (int comp = 0; comp < 2; comp++) {
-                    const double a = part == 0 ? (comp == 0 ? gr[k] : -gi[k]) : (comp == 0 ? gi[k] : gr[k]);
-                    const double as = a * tap_scale;
-                    const uint16_t hi = f16_rn(as), lo = f16_rn(as - f16_val(hi));
-                    const uint16_t term[RD_CHAN_TERMS] = {hi, lo};
-                    const int lane = 32 * hh + r0 + part;
-                    for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
-                        // element position inside the fragment: (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), see the kernel's B fragments
-                        const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + 4 * (s4 / 2) + 2 * comp + (s4 % 2);
-                        h->h_amat[at] = term[tm];
+                for (int comp = 0; comp < 2; comp++)
+                    for (int dig = 0; dig < n_dig; dig++) {
+                        const double a = part == 0 ? (comp == 0 ? gr[k] : -gi[k]) : (comp == 0 ? gi[k] : gr[k]);
+                        const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
+                        const uint16_t hi = f16_rn(as), lo = f16_rn(as - f16_val(hi));
+                        const uint16_t term[RD_CHAN_TERMS] = {hi, lo};
+                        const int lane = 32 * hh + r0 + part;
+                        // element position inside the fragment, see the kernel's B fragments:
+                        // (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi | the same of the second sample)
+                        const int el = fmt == RD_IQ_S16 ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
+                        for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
+                            const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + el;
+                            h->h_amat[at] = term[tm];
+                        }
                     }
-                }
         }
     }
     *out = h;
@@ -417,7 +515,7 @@ static int chan_alloc(rd_chan *h, size_t n_wide) {
     if (n_wide > h->wide_cap) {
         if (h->d_wide) hipFree(h->d_wide);
         h->d_wide = nullptr;
-        CHK(hipMalloc(&h->d_wide, 2 * n_wide + 16));
+        CHK(hipMalloc(&h->d_wide, rd_fmt_in_bps(h->fmt) * n_wide + 16));
         h->wide_cap = n_wide;
     }
     return RD_OK;
@@ -432,13 +530,42 @@ extern "C" int rd_chan_input_ptr(rd_chan *h, size_t n_wide_samples, void **dev_p
     return RD_OK;
 }
 
-extern "C" int rd_chan_upload(rd_chan *h, const uint8_t *wide_iq, size_t nbytes) {
+extern "C" int rd_chan_upload(rd_chan *h, const void *wide_iq, size_t nbytes) {
     if (!h || !wide_iq) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (nbytes % 2) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %zu bytes is not a whole number of IQ pairs", nbytes);
-    int rc = chan_alloc(h, nbytes / 2);
+    const size_t bps = (size_t)rd_fmt_in_bps(h->fmt);
+    if (nbytes % bps)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %zu bytes is not a whole number of %zu-byte IQ pairs", nbytes, bps);
+    int rc = chan_alloc(h, nbytes / bps);
     if (rc) return rc;
     CHK(hipMemcpy(h->d_wide, wide_iq, nbytes, hipMemcpyHostToDevice));
-    h->wide_n = nbytes / 2;
+    h->wide_n = nbytes / bps;
+    return RD_OK;
+}
+
+// the instantiation of a form and a format
+static const void *chan_kernel(bool stream, int fmt) {
+    switch (fmt) {
+    case RD_IQ_S8: return stream ? (const void *)k_channelize<true, RD_IQ_S8> : (const void *)k_channelize<false, RD_IQ_S8>;
+    case RD_IQ_S16: return stream ? (const void *)k_channelize<true, RD_IQ_S16> : (const void *)k_channelize<false, RD_IQ_S16>;
+    default: return stream ? (const void *)k_channelize<true, RD_IQ_U8> : (const void *)k_channelize<false, RD_IQ_U8>;
+    }
+}
+
+static int chan_launch(rd_chan *h, bool stream, const uint8_t *wide, long n_wide, const uint8_t *prev, int n_early,
+                       long t_base_mod, long n_out, unsigned gx, void *dst, size_t dst_stride, hipStream_t st) {
+    int T = h->t_pad, D = h->cfg.decim, n_ch = h->cfg.n_channels;
+    const size_t lds = chan_lds_bytes(h->fmt, D, T);
+    const uint4 *amat = (const uint4 *)h->d_amat;
+    const float2 *dc = (const float2 *)h->d_dc;
+    const int64_t *shifts = h->d_shifts;
+    long out_rate = (long)h->cfg.out_rate;
+    float gain = (float)h->cfg.gain, tap_unscale = h->tap_unscale;
+    uint8_t *out = (uint8_t *)dst;
+    int xs_bytes = (int)lds;
+    void *args[] = {&wide, &n_wide, &amat, &dc, &shifts, &T, &D, &n_ch, &n_early, &out_rate, &gain, &tap_unscale, &n_out,
+                    &out, &dst_stride, &xs_bytes, &prev, &t_base_mod};   // k_channelize's parameters, in order
+    CHK(hipLaunchKernel(chan_kernel(stream, h->fmt), dim3(gx, (unsigned)h->n_groups), dim3(256), args, lds, st));
+    CHK(hipGetLastError());
     return RD_OK;
 }
 
@@ -450,18 +577,11 @@ extern "C" int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_s
         return rd_fail_msg(RD_ERR_ARG, "n_out exceeds capture length / decim");
     if (dst_stream_stride < 2 * n_out || (dst_stream_stride & 1))
         return rd_fail_msg(RD_ERR_ARG, "destination stride too small for n_out samples");
-    const int T = h->t_pad, D = h->cfg.decim;
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * D + T + RD_CHAN_KC;
-    const size_t xs_bytes = (2 * span + 15 + 16) & ~(size_t)15;
-    const size_t lds = xs_bytes;
-    CHK(hipFuncSetAttribute((const void *)k_channelize<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
+    CHK(hipFuncSetAttribute(chan_kernel(false, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned gx = (unsigned)((n_out + RD_CHAN_TT - 1) / RD_CHAN_TT);
-    hipLaunchKernelGGL(k_channelize<false>, dim3(gx, (unsigned)h->n_groups), dim3(256), lds, (hipStream_t)hip_stream, h->d_wide,
-                       (long)h->wide_n, (const uint4 *)h->d_amat, (const float2 *)h->d_dc, h->d_shifts, T, D,
-                       h->cfg.n_channels, h->n_early, (long)h->cfg.out_rate, (float)h->cfg.gain, h->tap_unscale, (long)n_out,
-                       (uint8_t *)dst_dev, dst_stream_stride, (int)xs_bytes, (const uint8_t *)nullptr, 0L);
-    CHK(hipGetLastError());
-    return RD_OK;
+    return chan_launch(h, false, h->d_wide, (long)h->wide_n, nullptr, h->n_early, 0L, (long)n_out, gx, dst_dev,
+                       dst_stream_stride, (hipStream_t)hip_stream);
 }
 
 extern "C" int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, size_t nbytes) {
@@ -488,13 +608,12 @@ int rd_chan_stream_prepare(rd_chan *h) {
     if (!h) return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = chan_alloc(h, 0);
     if (rc) return rc;
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * h->cfg.decim + h->t_pad + RD_CHAN_KC;
-    const size_t lds = (2 * span + 15 + 16) & ~(size_t)15;
-    CHK(hipFuncSetAttribute((const void *)k_channelize<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
+    CHK(hipFuncSetAttribute(chan_kernel(true, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return RD_OK;
 }
 
-// Channelize one chunk of n_out * decim samples at `wide` (device) whose predecessor lies at `prev` (null: zero history)
+// Channelize one chunk of n_out * decim samples (of the handle's format) at `wide` (device) whose predecessor lies at `prev` (null: zero history)
 // into dst (channel c at dst + c * dst_stride); t_base = the absolute output time of the chunk's first output.
 int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, size_t n_out, uint64_t t_base, void *dst,
                           size_t dst_stride, hipStream_t st) {
@@ -506,17 +625,11 @@ int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, 
     const int T = h->t_pad, D = h->cfg.decim;
     const long n_wide = (long)(n_out * (size_t)D);
     if (T > n_wide) return rd_fail_msg(RD_ERR_ARG, "the taps reach further back than one chunk");
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * D + T + RD_CHAN_KC;
-    const size_t xs_bytes = (2 * span + 15 + 16) & ~(size_t)15;
     const long t_base_mod = (long)(t_base % (uint64_t)h->cfg.out_rate);
     const int n_early = t_base == 0 ? h->n_early : 0;   // the early DC table: absolute t < n_early only
     const unsigned gx = (unsigned)(n_out / RD_CHAN_TT);
-    hipLaunchKernelGGL(k_channelize<true>, dim3(gx, (unsigned)h->n_groups), dim3(256), xs_bytes, st, wide, n_wide,
-                       (const uint4 *)h->d_amat, (const float2 *)h->d_dc, h->d_shifts, T, D, h->cfg.n_channels, n_early,
-                       (long)h->cfg.out_rate, (float)h->cfg.gain, h->tap_unscale, (long)n_out, (uint8_t *)dst, dst_stride,
-                       (int)xs_bytes, prev, t_base_mod);
-    CHK(hipGetLastError());
-    return RD_OK;
+    return chan_launch(h, true, wide, n_wide, prev, n_early, t_base_mod, (long)n_out, gx, dst, dst_stride, st);
 }
 
 int rd_chan_n_channels(const rd_chan *h) { return h ? h->cfg.n_channels : 0; }
+int rd_chan_bytes_per_sample(const rd_chan *h) { return h ? rd_fmt_in_bps(h->fmt) : 0; }

@@ -193,6 +193,7 @@ int rd_chan_stream_prepare(rd_chan *h);
 int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, size_t n_out, uint64_t t_base, void *dst,
                           size_t dst_stride, hipStream_t st);
 int rd_chan_n_channels(const rd_chan *h);
+int rd_chan_bytes_per_sample(const rd_chan *h);   // of an IQ pair in the handle's sample format
 // rd_api.hip: the handle's device state and its two non-blocking streams (compute, copy)
 int rd_demod_prepare(rd_demod *h, hipStream_t *st, hipStream_t *st_copy);
 // drop the blocks a timed-out fetch gave up on, then RD_ERR_STATE if two blocks are in flight

@@ -1,5 +1,5 @@
 // rd_wideband.hip - live wideband receiver (include/rtldavis_hip.h: rd_wideband_*): a capture that never ends, fed in
-// chunks of decim x block_size samples, channelized into every hop channel and demodulated, all on the GPU.
+// chunks of decim x block_size samples (uint8, int8 or int16 IQ: rd_wb_create_fmt), channelized into every hop channel and demodulated, all on the GPU.
 //
 // One handle owns one rd_chan configuration and one multi-stream rd_demod (n_streams = n_channels).  Per chunk, queued by
 // rd_wideband_submit and returning at once:
@@ -33,7 +33,7 @@ struct rd_wideband {
     rd_demod *dem = nullptr;
     int n_ch = 0;
     size_t B = 0;                 // output samples per channel and chunk (the demodulator's block size)
-    size_t chunk_bytes = 0;       // 2 * decim * B
+    size_t chunk_bytes = 0;       // bytes of an IQ pair in the handle's format * decim * B
     uint64_t clock = 0;           // absolute output time of the next chunk's first output
     long n_sub = 0;               // chunks submitted since create / reset (chunk k uses buffers k & 1)
     long last = -1;               // chunk the last fetch returned
@@ -49,11 +49,16 @@ struct rd_wideband {
 
 extern "C" int rd_wideband_create(const rd_config *cfg, const rd_chan_config *ccfg, const double *taps,
                                   const int64_t *shift_hz, rd_wideband **out) {
+    return rd_wb_create_fmt(cfg, ccfg, RD_IQ_U8, taps, shift_hz, out);
+}
+
+extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg, int sample_format, const double *taps,
+                                const int64_t *shift_hz, rd_wideband **out) {
     if (!cfg || !ccfg || !taps || !shift_hz || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (cfg->block_size < 128 || cfg->block_size % 128)
         return rd_fail_msg(RD_ERR_ARG, "block_size %d is not a positive multiple of 128", cfg->block_size);
     rd_chan *ch = nullptr;
-    int rc = rd_chan_create(ccfg, taps, shift_hz, &ch);
+    int rc = rd_chan_create_fmt(ccfg, sample_format, taps, shift_hz, &ch);
     if (rc) return rc;
     rd_demod *dem = nullptr;
     rc = rd_create_multi(cfg, ccfg->n_channels, &dem);
@@ -66,7 +71,7 @@ extern "C" int rd_wideband_create(const rd_config *cfg, const rd_chan_config *cc
     w->dem = dem;
     w->n_ch = ccfg->n_channels;
     w->B = (size_t)cfg->block_size;
-    w->chunk_bytes = 2 * (size_t)ccfg->decim * w->B;
+    w->chunk_bytes = (size_t)rd_chan_bytes_per_sample(ch) * (size_t)ccfg->decim * w->B;
     *out = w;
     return RD_OK;
 }
@@ -114,7 +119,7 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     return RD_OK;
 }
 
-extern "C" int rd_wideband_submit(rd_wideband *w, const uint8_t *wide_iq, size_t nbytes) {
+extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nbytes) {
     if (!w || !wide_iq) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (nbytes != w->chunk_bytes)
         return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: got %zu bytes, expected %zu", nbytes, w->chunk_bytes);

@@ -105,8 +105,9 @@ def synth_streams(seeds, n_samples: int = STREAM_SAMPLES) -> np.ndarray:
 
 
 def synth_wideband(seeds, shifts_hz, n_out: int, decim: int = 100, out_rate: int = SYMBOL_LENGTH * 19200,
-                   amplitude: float = 0.12, noise: float = 0.02, noise_seed: int = 1234):
-    """One wideband capture (uint8 I,Q interleaved, decim*out_rate samples/s, n_out*decim samples)
+                   amplitude: float = 0.12, noise: float = 0.02, noise_seed: int = 1234, sample_format: str = "u8"):
+    """One wideband capture (I,Q interleaved, decim*out_rate samples/s, n_out*decim samples; sample_format "u8":
+    uint8 rint(x 127.6 + 127.4), "s8": int8 rint(x 128), "s16": int16 rint(x 32768), clipped, of the same complex x)
     holding one burst per entry: burst i is the packet synth_stream(seeds[i]) carries, at
     shifts_hz[i] Hz from the capture's centre (+ a random cfo of +-2 kHz), starting somewhere
     between the first and the last 8192 output samples.  Returns (raw, [(payload_hex, start_out)])."""
@@ -129,9 +130,12 @@ def synth_wideband(seeds, shifts_hz, n_out: int, decim: int = 100, out_rate: int
         phase = (float(shift) + cfo) * lo * (2.0 * np.pi / fw) + np.cumsum(freq) * (2.0 * np.pi / fw)
         x[lo:hi] += amplitude * np.exp(1j * phase)
         info.append((payload, start_out))
-    out = np.empty(2 * n, dtype=np.uint8)
-    out[0::2] = np.clip(np.rint(x.real * 127.6 + 127.4), 0, 255).astype(np.uint8)
-    out[1::2] = np.clip(np.rint(x.imag * 127.6 + 127.4), 0, 255).astype(np.uint8)
+    dtype, scale, offset = {"u8": (np.uint8, 127.6, 127.4), "s8": (np.int8, 128.0, 0.0),
+                            "s16": (np.int16, 32768.0, 0.0)}[sample_format]
+    lim = np.iinfo(dtype)
+    out = np.empty(2 * n, dtype=dtype)
+    out[0::2] = np.clip(np.rint(x.real * scale + offset), lim.min, lim.max).astype(dtype)
+    out[1::2] = np.clip(np.rint(x.imag * scale + offset), lim.min, lim.max).astype(dtype)
     return out, info
 
 

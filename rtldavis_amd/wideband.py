@@ -25,23 +25,28 @@ logger = logging.getLogger(__name__)
 
 
 class WidebandReceiver:
-    """``WidebandReceiver(cfg, channels_hz, centre_hz)``: chunks of ``chunk_bytes`` (uint8 I,Q of
-    ``decim * cfg.block_size`` wideband samples at ``decim * cfg.bit_rate * cfg.symbol_length``) in,
+    """``WidebandReceiver(cfg, channels_hz, centre_hz)``: chunks of ``chunk_bytes`` (I,Q of ``chunk_samples`` =
+    ``decim * cfg.block_size`` wideband samples at ``decim * cfg.bit_rate * cfg.symbol_length``, in ``sample_format``:
+    ``"u8"`` offset bytes, ``"s8"`` int8 or ``"s16"`` int16, see ``Channelizer``) in,
     one ``List[Packet]`` per channel and chunk out - each channel behaves like its own ``Demodulator``
     fed the channel's stream.  ``submit`` / ``fetch`` keep up to two chunks in flight (the copy of
     one beside the kernels of the other); ``demodulate`` is both in one call."""
 
     def __init__(self, cfg, channels_hz: Sequence[int] = US_CHANNELS_HZ, centre_hz: int = DEFAULT_CENTRE_HZ,
-                 decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0) -> None:
+                 decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0,
+                 sample_format: str = "u8") -> None:
         self.cfg = cfg
+        self._h = C.c_void_p()
+        self.sample_format = sample_format
+        self._fmt, self.dtype = _lib.sample_format(sample_format)
         if int(cfg.block_size) % 128 or int(cfg.block_size) < 128:
             raise ValueError(f"block_size {cfg.block_size} is not a positive multiple of 128")
         plan_channels(self, channels_hz, centre_hz, decim, taps, gain, int(cfg.bit_rate) * int(cfg.symbol_length))
         self.block_size = int(cfg.block_size)
-        self.chunk_bytes = 2 * self.decim * self.block_size
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().rd_wideband_create(C.byref(_cfg_struct(cfg)), C.byref(chan_config(self)),
-                                                 self.taps.ctypes.data, self.shift_hz.ctypes.data, C.byref(self._h)))
+        self.chunk_samples = self.decim * self.block_size           # IQ pairs per chunk
+        self.chunk_bytes = 2 * np.dtype(self.dtype).itemsize * self.chunk_samples
+        _lib.check(_lib.lib().rd_wb_create_fmt(C.byref(_cfg_struct(cfg)), C.byref(chan_config(self)), self._fmt,
+                                               self.taps.ctypes.data, self.shift_hz.ctypes.data, C.byref(self._h)))
         self._cap = 64 * max(1, self.n_channels)
         self._recs = (_lib.RdPacket * self._cap)()
 
@@ -54,8 +59,8 @@ class WidebandReceiver:
             pass
 
     def _check_chunk(self, chunk: np.ndarray) -> np.ndarray:
-        a = np.ascontiguousarray(chunk, dtype=np.uint8).reshape(-1)
-        if a.size != self.chunk_bytes:
+        a = _lib.iq_array(chunk, self.dtype)
+        if a.nbytes != self.chunk_bytes:
             logger.error(f"Incompatible array sizes: chunk.size={a.size}")
             raise ValueError("Incompatible array sizes")
         return a
@@ -71,7 +76,7 @@ class WidebandReceiver:
     def submit(self, chunk: np.ndarray) -> None:
         """Queue one chunk (asynchronous copy, channelizer and demodulator; at most two chunks in flight)."""
         a = self._check_chunk(chunk)
-        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.size))
+        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.nbytes))
 
     def fetch(self) -> List[List[Packet]]:
         """Packets of the oldest chunk in flight, one list per channel."""
@@ -84,7 +89,7 @@ class WidebandReceiver:
         a = self._check_chunk(chunk)
         if self.inflight:
             raise RuntimeError(f"{self.inflight} chunk(s) in flight: fetch them first")
-        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.size))
+        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.nbytes))
         return self.fetch()
 
     @property

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="timed windows (each after a reset); the median is reported")
     ap.add_argument("--capture-chunks", type=int, default=6, help="chunks in the synthesised capture")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--sample-format", default="u8", choices=["u8", "s8", "s16"], help="the capture's sample format")
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -38,9 +39,10 @@ def main():
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
     off = [f - CZ.DEFAULT_CENTRE_HZ for f in CZ.US_CHANNELS_HZ]
-    raw, info = synth.synth_wideband(range(200, 200 + len(off)), off, nk * B, amplitude=0.05)
-    rx = wideband.WidebandReceiver(cfg)
-    step = rx.chunk_bytes
+    raw, info = synth.synth_wideband(range(200, 200 + len(off)), off, nk * B, amplitude=0.05,
+                                     sample_format=args.sample_format)
+    rx = wideband.WidebandReceiver(cfg, sample_format=args.sample_format)
+    step = 2 * rx.chunk_samples      # array elements per chunk
     chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
 
     def run(n):
@@ -75,7 +77,8 @@ def main():
     air = args.chunks * B / out_rate
     res = {
         "chunks": args.chunks, "capture_chunks": nk, "warmup": args.warmup, "channels": rx.n_channels,
-        "block_size": B, "decim": rx.decim, "chunk_bytes": step, "chunk_air_ms": 1e3 * B / out_rate,
+        "block_size": B, "decim": rx.decim, "chunk_bytes": rx.chunk_bytes,
+        "sample_format": args.sample_format, "chunk_air_ms": 1e3 * B / out_rate,
         "repeats": args.repeats, "wall_s": wall, "wall_s_all": walls, "chunks_per_s": args.chunks / wall,
         "latency_ms": {"median": float(np.median(lat) * 1e3), "p99": float(np.percentile(lat, 99) * 1e3),
                        "max": float(lat.max() * 1e3), "min": float(lat.min() * 1e3)},
