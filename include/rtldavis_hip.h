@@ -137,7 +137,7 @@ int rd_demod_blocks(rd_demod *h, const uint8_t *iq, size_t nbytes, rd_packet *ou
  * waits (polling) for the OLDEST submitted block and returns its packets exactly as rd_demod_block / rd_demod_blocks would.
  * Two blocks may be in flight (RD_ERR_STATE on a third submit): block i+1's copy overlaps block i's
  * kernels.  count: 2 * block_size * n_streams bytes, or block_size complex128 samples (single stream).
- * The state mirrors below need a quiet handle (everything fetched).
+ * The state mirrors below need a quiet handle (everything fetched); rd_demod_parsed does not.
  */
 int rd_demod_submit(rd_demod *h, const void *samples, size_t count, int is_complex);
 /*
@@ -172,6 +172,26 @@ int rd_demod_inflight(rd_demod *h);
  * *n told how many there are - grow the array and fetch them here.  Nothing is lost.
  */
 int rd_demod_refetch(rd_demod *h, rd_packet *out, int cap, int *n);
+/*
+ * Parser.parse's front half (/root/reference/src/rtldavis/protocol.py:282-318, the rd_parsed struct above) for the
+ * streaming forms, computed inside the block's own kernels: the wave that slices a packet also bit-swaps it, checks the
+ * CRC and - for the survivors only - averages the float64 discriminator over the preamble window of the stream's state
+ * as it is right after that block (what rd_copy_discriminated_stream would return on a quiet handle at that moment).
+ * So the receiver loop of /root/reference/src/rtldavis/worker.py:49-50 needs no quiet handle and no state mirror: two
+ * blocks stay in flight and each fetched block brings its messages with their frequency errors.
+ * rd_demod_set_parse: opt-in (default 0), quiet handle only (else RD_ERR_STATE), no device work (safe before fork);
+ * applies to the blocks submitted afterwards.  rd_demod_parsed: the CRC-valid messages of the block the last
+ * rd_demod_fetch / rd_demod_block(s) returned, sorted like its packets, stream and call as in the packet each came from;
+ * may be called any number of times, with later blocks in flight.  RD_ERR_CAPACITY sets *n and loses nothing;
+ * RD_ERR_STATE when nothing has been fetched since create / reset or that block was submitted with parse off.
+ */
+int rd_demod_set_parse(rd_demod *h, int enabled);
+int rd_demod_parsed(rd_demod *h, rd_parsed *out, int cap, int *n);
+/* The same decision for one packet on the host, no device involved: data = the nbytes (<= RD_MAX_PKT_BYTES) on-air bytes
+ * of an rd_packet.  Returns 1 when nbytes > 2 and the CRC-16-CCITT over the bit-swapped bytes [2:] is 0 - then msg
+ * (nbytes - 2 bytes: the swapped message, sync word removed) and *id (msg[0] & 7) are filled -, 0 when not (msg, id
+ * untouched), RD_ERR_ARG for a null pointer or nbytes out of range. */
+int rd_parse_packet(const uint8_t *data, int nbytes, uint8_t *msg, int *id);
 /* discriminated (py:134) of one stream of a multi-stream handle */
 int rd_copy_discriminated_stream(rd_demod *h, int stream, double *out, size_t n);
 /* Lazily materialised mirrors of the reference's state arrays after the last call:
@@ -353,6 +373,11 @@ int rd_wideband_inflight(rd_wideband *w);
  * the next submit), and one channel's discriminator output as rd_copy_discriminated_stream */
 int rd_wideband_copy_channelized(rd_wideband *w, uint8_t *out, size_t nbytes);
 int rd_wideband_copy_discriminated(rd_wideband *w, int channel, double *out, size_t n);
+/* as rd_demod_set_parse / rd_demod_parsed: the CRC-valid messages of the chunk the last fetch returned, stream = channel,
+ * call = chunk, with their frequency errors - chunk k's while chunk k+1 is in flight (rd_wideband_copy_discriminated
+ * shows the state after the NEWEST chunk and needs a quiet receiver) */
+int rd_wb_set_parse(rd_wideband *w, int enabled);
+int rd_wb_parsed(rd_wideband *w, rd_parsed *out, int cap, int *n);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

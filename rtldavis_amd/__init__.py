@@ -3,9 +3,10 @@
 ``rtldavis_amd.dsp`` mirrors ``rtldavis.dsp`` (drop-in for protocol.Parser / worker);
 ``rtldavis_amd.batch.BatchDemodulator`` demodulates many independent streams per launch;
 ``rtldavis_amd.WidebandReceiver`` (``rtldavis_amd.wideband``) channelizes and demodulates a live wideband
-capture chunk by chunk.
+capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s front half in their kernels
+(``set_parse`` / ``parsed``); ``rtldavis_amd.parse_packet`` is the same CRC gate for one packet on the host.
 """
-__all__ = ["dsp", "batch", "synth", "wideband", "WidebandReceiver"]
+__all__ = ["dsp", "batch", "synth", "wideband", "WidebandReceiver", "parse_packet"]
 
 import os as _os
 
@@ -38,4 +39,7 @@ def __getattr__(name):
     if name == "WidebandReceiver":
         from .wideband import WidebandReceiver
         return WidebandReceiver
+    if name == "parse_packet":
+        from .dsp import parse_packet
+        return parse_packet
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -96,6 +96,9 @@ SIGNATURES = {
     "rd_demod_fetch": (C.c_int, [_P, C.POINTER(RdPacket), C.c_int, C.POINTER(C.c_int)]),
     "rd_demod_refetch": (C.c_int, [_P, C.POINTER(RdPacket), C.c_int, C.POINTER(C.c_int)]),
     "rd_demod_inflight": (C.c_int, [_P]),
+    "rd_demod_set_parse": (C.c_int, [_P, C.c_int]),
+    "rd_demod_parsed": (C.c_int, [_P, C.POINTER(RdParsed), C.c_int, C.POINTER(C.c_int)]),
+    "rd_parse_packet": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int)]),
     "rd_destroy": (None, [_P]),
     "rd_reset": (C.c_int, [_P]),
     "rd_demod_block": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(RdPacket), C.c_int, C.POINTER(C.c_int)]),
@@ -141,6 +144,8 @@ SIGNATURES = {
     "rd_wideband_inflight": (C.c_int, [_P]),
     "rd_wideband_copy_channelized": (C.c_int, [_P, _P, C.c_size_t]),
     "rd_wideband_copy_discriminated": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "rd_wb_set_parse": (C.c_int, [_P, C.c_int]),
+    "rd_wb_parsed": (C.c_int, [_P, C.POINTER(RdParsed), C.c_int, C.POINTER(C.c_int)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),

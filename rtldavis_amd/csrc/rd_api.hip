@@ -23,6 +23,7 @@
 #include "rd_host.h"
 #include "rd_internal.h"
 #include "rd_math.h"
+#include "rd_parse.h"
 
 // RD_DEBUG_HOST=1: print host-side phase times of rd_batch_results to stderr (diagnostic)
 static bool dbg_host() {
@@ -979,6 +980,11 @@ struct rd_slot {
     uint32_t *d_sb_map = nullptr;
     uint32_t seq = 0;                // what the flags read once this slot's block is done
     bool one = false;                // this slot's block went through k_stream_block
+    // Parser.parse's front half on the device (rd_demod_set_parse): per record slot of h_recs, RD_FE_NONE or the
+    // packet's frequency error, written by the kernel that writes the record (or by k_stream_parse behind the slice)
+    int32_t *h_fe = nullptr;         // pinned + mapped, rec_cap entries
+    int32_t *d_fe_map = nullptr;
+    bool parse = false;              // this slot's block was submitted with parse on
     hipEvent_t e_in = nullptr, e_done = nullptr;
 };
 
@@ -1018,6 +1024,11 @@ struct rd_demod {
     // that already lie there - a shared-memory ring an SDR process fills - without copying them anywhere
     uint8_t *ext_host = nullptr, *ext_dev = nullptr;
     size_t ext_bytes = 0;
+    bool parse = false;             // rd_demod_set_parse: blocks submitted from now on are parsed on the device
+    bool fetched = false;           // a block has been fetched since create / reset ...
+    bool last_parse = false;        // ... and it had been submitted with parse on: last_parsed holds its messages
+    std::vector<rd_parsed> last_parsed;  // CRC-valid messages of the last fetched block, in the order of `last`
+    std::vector<int32_t> gather_fe; // fe entries of `gather`
     int stale = 0;                  // blocks in flight whose fetch timed out: dropped (waited for, results discarded) by
                                     // the next submit / reset - the caller has already been told (worker.py:56-58)
 };
@@ -1081,6 +1092,8 @@ static int demod_alloc(rd_demod *h) {
         HIPCHK(hipHostMalloc((void **)&sl.h_cnt, RD_CNT_SLOTS * 4, hipHostMallocDefault));
         HIPCHK(hipHostMalloc((void **)&sl.h_recs, (size_t)h->rec_cap * sizeof(rd_packet), hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer((void **)&sl.d_recs_map, sl.h_recs, 0));
+        HIPCHK(hipHostMalloc((void **)&sl.h_fe, (size_t)h->rec_cap * sizeof(int32_t), hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer((void **)&sl.d_fe_map, sl.h_fe, 0));
         HIPCHK(hipEventCreateWithFlags(&sl.e_in, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&sl.e_done, hipEventDisableTiming));
     }
@@ -1135,7 +1148,7 @@ extern "C" void rd_destroy(rd_demod *h) {
         hipHostFree(h->h_tmp);
         for (int i = 0; i < 2; i++) {
             rd_slot &sl = h->slot[i];
-            hipHostFree(sl.h_in); hipFree(sl.d_in); hipFree(sl.d_push); hipHostFree(sl.h_cnt); hipHostFree(sl.h_recs); hipHostFree(sl.h_sb);
+            hipHostFree(sl.h_in); hipFree(sl.d_in); hipFree(sl.d_push); hipHostFree(sl.h_cnt); hipHostFree(sl.h_recs); hipHostFree(sl.h_sb); hipHostFree(sl.h_fe);
             if (sl.e_in) hipEventDestroy(sl.e_in);
             if (sl.e_done) hipEventDestroy(sl.e_done);
         }
@@ -1218,6 +1231,8 @@ extern "C" int rd_reset(rd_demod *h) {
     h->seen = 0;
     h->cplx_mode = false;
     h->last.clear();
+    h->last_parsed.clear();
+    h->fetched = h->last_parse = false;
     return RD_OK;
 }
 
@@ -1297,6 +1312,7 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
         memcpy(sl.h_in, samples, nbytes);
     }
     sl.one = false;
+    sl.parse = h->parse;
     if (h->one_ok && NS == 1 && h->dc.B <= 8192 && (is_complex || h->cplx_mode)) {
         // ONE launch for the complex-input branch as well (py:144-150: what pyrtlsdr's stream() feeds the live receiver,
         // /root/reference/src/rtldavis/runners/rtlsdr.py:100-103); a uint8 block on a handle in complex mode goes through
@@ -1319,6 +1335,8 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
         a.seq = ++h->seq;
         a.seen_before = h->seen;
         a.sync = h->d_sync;
+        a.parse = sl.parse ? 1 : 0;
+        a.fe_host = sl.d_fe_map;
         if (rd_launch_stream_block_cplx(a, st)) {
             HIPCHK(hipGetLastError());
             h->cur_win = nw;
@@ -1346,6 +1364,8 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
         a.flag_host = sl.d_sb_map + NS;
         a.seq = ++h->seq;
         a.seen_before = h->seen;
+        a.parse = sl.parse ? 1 : 0;
+        a.fe_host = sl.d_fe_map;
         if (rd_launch_stream_block(a, h->NS, st)) {
             HIPCHK(hipGetLastError());
             h->cur_win = nw;
@@ -1411,6 +1431,12 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
     else
         rd_launch_cplx_slice(demod_clayout(h, seen_before), h->d_win[nw], (long)L, h->dc, h->d_matches, h->match_cap,
                              (int)seen_before, nullptr, sl.d_recs_map, h->d_cnt, st);
+    if (sl.parse) {   // Parser.parse's front half for the records just sliced (one wave each), into the slot's fe array
+        if (!h->cplx_mode)
+            rd_launch_stream_parse(demod_layout(h, seen_before), h->dc, sl.d_recs_map, h->match_cap, sl.d_fe_map, h->d_cnt, st);
+        else
+            rd_launch_cplx_stream_parse(demod_clayout(h, seen_before), h->dc, sl.d_recs_map, h->match_cap, sl.d_fe_map, h->d_cnt, st);
+    }
     HIPCHK(hipGetLastError());
     // The counters come back with the block; the few records of a block are written by the slice
     // kernel straight into pinned host memory (no copy to wait for; for the thousands of records of
@@ -1433,6 +1459,30 @@ static int demod_give(rd_demod *h, rd_packet *out, int cap, int *n) {
     return RD_OK;
 }
 
+// The messages of the block just fetched (rd_demod_parsed): of the kept records (h->last, h->order.kept: the reference's
+// order, per-call duplicates gone) those the device found CRC-valid - fe[k] is record k's entry of the slot's fe array -
+// with the bytes swapped here (rd_parse.h).  The parser's own dedupe on the swapped bytes (protocol.py:293-295) has
+// nothing left to drop: the swap is a bijection and the per-call dedupe has run.
+static void demod_keep_parsed(rd_demod *h, bool parse, const int32_t *fe) {
+    h->fetched = true;
+    h->last_parse = parse;
+    h->last_parsed.clear();
+    if (!parse) return;
+    for (size_t i = 0; i < h->last.size(); i++) {
+        const int32_t e = fe[h->order.kept[i]];
+        if (e == RD_FE_NONE) continue;
+        const rd_packet &r = h->last[i];
+        rd_parsed m;
+        memset(&m, 0, sizeof m);
+        m.stream = r.stream; m.call = r.call; m.index = r.index; m.freq_err = e;
+        m.nbytes = r.nbytes - 2;
+        for (int k = 2; k < r.nbytes && k < RD_MAX_PKT_BYTES; k++) m.data[k - 2] = (uint8_t)rd_swap_bits8(r.data[k]);
+        m.id = m.data[0] & 7;
+        m.rssi = r.rssi; m.snr = r.snr;
+        h->last_parsed.push_back(m);
+    }
+}
+
 // Wait (polling) for the oldest block in flight and return its packets in the reference's order.
 static int demod_fetch(rd_demod *h, rd_packet *out, int cap, int *n) {
     if (h->nflight == 0) return fail(RD_ERR_STATE, "no block in flight");
@@ -1450,13 +1500,18 @@ static int demod_fetch(rd_demod *h, rd_packet *out, int cap, int *n) {
         h->head ^= 1;
         h->nflight--;
         h->gather.clear();
+        h->gather_fe.clear();
         for (size_t s = 0; s < NS; s++) {
             const uint32_t c = std::min<uint32_t>(sl.h_sb[s], (uint32_t)per);
-            for (uint32_t i = 0; i < c; i++) h->gather.push_back(sl.h_recs[s * per + i]);
+            for (uint32_t i = 0; i < c; i++) {
+                h->gather.push_back(sl.h_recs[s * per + i]);
+                if (sl.parse) h->gather_fe.push_back(sl.h_fe[s * per + i]);
+            }
         }
         order_and_dedupe(h->gather.data(), h->gather.size(), h->dc.S, h->order);
         h->last.clear();
         for (uint32_t k : h->order.kept) h->last.push_back(h->gather[k]);
+        demod_keep_parsed(h, sl.parse, h->gather_fe.data());
         return demod_give(h, out, cap, n);
     }
     h->head ^= 1;
@@ -1465,6 +1520,7 @@ static int demod_fetch(rd_demod *h, rd_packet *out, int cap, int *n) {
     order_and_dedupe(sl.h_recs, nrec, h->dc.S, h->order);
     h->last.clear();
     for (uint32_t k : h->order.kept) h->last.push_back(sl.h_recs[k]);
+    demod_keep_parsed(h, sl.parse, sl.h_fe);
     return demod_give(h, out, cap, n);
 }
 
@@ -1543,6 +1599,28 @@ extern "C" int rd_demod_refetch(rd_demod *h, rd_packet *out, int cap, int *n) {
 }
 
 extern "C" int rd_demod_inflight(rd_demod *h) { return h ? h->nflight : 0; }
+
+// Parser.parse's front half inside the streaming kernels (no device work here: safe before fork)
+extern "C" int rd_demod_set_parse(rd_demod *h, int enabled) {
+    if (!h) return fail(RD_ERR_ARG, "null handle");
+    if (h->nflight) return fail(RD_ERR_STATE, "%d block(s) in flight: rd_demod_fetch them before parse is switched", h->nflight);
+    h->parse = enabled != 0;
+    return RD_OK;
+}
+
+extern "C" int rd_demod_parsed(rd_demod *h, rd_parsed *out, int cap, int *n) {
+    if (!h || !n) return fail(RD_ERR_ARG, "null argument");
+    if (!h->fetched) return fail(RD_ERR_STATE, "no block fetched since create / reset");
+    if (!h->last_parse) return fail(RD_ERR_STATE, "the last fetched block was submitted with parse off (rd_demod_set_parse)");
+    *n = (int)h->last_parsed.size();
+    if ((int)h->last_parsed.size() > cap)
+        return fail(RD_ERR_CAPACITY, "need room for %zu messages", h->last_parsed.size());
+    if (!h->last_parsed.empty()) {
+        if (!out) return fail(RD_ERR_ARG, "null out");
+        memcpy(out, h->last_parsed.data(), h->last_parsed.size() * sizeof(rd_parsed));
+    }
+    return RD_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // internal entry points of the wideband receiver (rd_internal.h, rd_wideband.hip)

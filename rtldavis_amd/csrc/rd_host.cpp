@@ -1,6 +1,7 @@
 // rd_host.cpp - see rd_host.h.  Pure host code: compiled by hipcc into the library and by g++ -fsanitize into
 // tests/_build/host_asan (tests/test_host_sanitizers.py).
 #include "rd_host.h"
+#include "rd_parse.h"
 
 #include <sched.h>
 #include <stdlib.h>
@@ -54,6 +55,21 @@ int rd_check_block_count(int is_complex, size_t count, size_t B, size_t NS, size
     const size_t want = is_complex ? B : NS * 2 * B;
     if (expected) *expected = want;
     return count == want ? RD_OK : RD_ERR_ARG;
+}
+
+// ------------------------------------------------------------------------------------------
+// Parser.parse's front half for one packet (protocol.py:290-318), host only: the arithmetic of rd_parse.h
+// ------------------------------------------------------------------------------------------
+extern "C" int rd_parse_packet(const uint8_t *data, int nbytes, uint8_t *msg, int *id) {
+    if (nbytes < 0 || nbytes > RD_MAX_PKT_BYTES || (nbytes > 0 && !data)) return RD_ERR_ARG;
+    if (nbytes <= 2) return 0;
+    uint32_t crc = 0;
+    for (int k = 2; k < nbytes; k++) crc = rd_crc16_step(crc, rd_swap_bits8(data[k]));
+    if (crc != 0) return 0;
+    if (!msg || !id) return RD_ERR_ARG;
+    for (int k = 2; k < nbytes; k++) msg[k - 2] = (uint8_t)rd_swap_bits8(data[k]);
+    *id = msg[0] & 7;
+    return 1;
 }
 
 uint32_t rd_ord_bucket_cap(long n_samples) {

@@ -115,6 +115,14 @@ int rd_launch_slice(const rd_layout &lay, const uint32_t *bits, size_t bits_stri
 // above): CRC-valid ones are written to `parsed` (RD_CNT_PARSED) with their frequency error.
 void rd_launch_parse(const rd_layout &lay, const rd_devcfg &cfg, const rd_packet *recs, uint32_t match_cap,
                      rd_parsed *parsed, uint32_t *counters, hipStream_t st, int dense = 0);
+// The same front half for the records the streaming handle's multi-launch form has just sliced (rd_launch_slice /
+// rd_launch_cplx_slice with recs_host, batch_mode 0, queued on `st` in front of this): fe[i] = RD_FE_NONE or the
+// frequency error of record i (rd_parse.h), i < RD_CNT_MATCH.  recs and fe: device addresses of mapped host memory.
+void rd_launch_stream_parse(const rd_layout &lay, const rd_devcfg &cfg, const rd_packet *recs, uint32_t match_cap,
+                            int32_t *fe, const uint32_t *counters, hipStream_t st);
+struct rd_cplx_layout;
+void rd_launch_cplx_stream_parse(const rd_cplx_layout &lay, const rd_devcfg &cfg, const rd_packet *recs, uint32_t match_cap,
+                                 int32_t *fe, const uint32_t *counters, hipStream_t st);
 // d[t0 .. t0+n) of stream `stream` in float64
 void rd_launch_disc(const rd_layout &lay, int stream, long t0, long n, double *out, hipStream_t st);
 // f[t0 .. t0+n) (interleaved re,im) of stream `stream` in float64
@@ -143,6 +151,8 @@ struct rd_sb_args {
     uint32_t seq;
     long seen_before;         // blocks since reset
     uint64_t *stamps;         // diagnostic library: phase stamps (else null)
+    int parse;                // also run Parser.parse's front half for every record (rd_kernels.hip: rd_wave_parse) ...
+    int32_t *fe_host;         // ... into mapped host memory laid out like recs_host: RD_FE_NONE or the frequency error
 };
 // 1 when the kernel was launched, 0 when the configuration is not one it is built for
 int rd_launch_stream_block(const rd_sb_args &a, int n_streams, hipStream_t st);
@@ -162,6 +172,8 @@ struct rd_sbc_args {
     long seen_before;
     uint32_t *sync;           // device word, zero between launches: the workgroups count themselves in
     uint64_t *stamps;         // diagnostic library: phase stamps (else null)
+    int parse;                // as rd_sb_args
+    int32_t *fe_host;
 };
 int rd_launch_stream_block_cplx(const rd_sbc_args &a, hipStream_t st);
 

@@ -21,6 +21,7 @@
 #include "rd_internal.h"
 #include "rd_math.h"
 #include "rd_mfma.h"
+#include "rd_parse.h"
 
 uint32_t rd_launch_demod(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                          hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t flags, uint32_t *chunk_out, uint32_t *bucket_cnt) {
@@ -404,6 +405,32 @@ __device__ __forceinline__ double rd_wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;  // valid in lane 0
+}
+
+// The parse of ONE packet by ONE wave, inside the streaming kernels: `byte` is the packet as the slice holds it (lane k
+// = on-air byte k, k < cfg.nbytes), `pos` its window index q, `v` a view whose sample 0 is the newest block's first
+// sample (rd_stream_view, rd_cplx_view or the coherent view of k_stream_block_cplx): discriminated[j] = d[j - B],
+// j in [0, 2 B) (dsp.py:156,162 - the mapping of rd_copy_discriminated_stream), the window clamped at 2 B as k_freq_err
+// does, history before the stream's first block the zero state (the view's valid_from).  The CRC is computed by every
+// lane from the same bytes (readlane), so the decision is wave-uniform and the float64 loop over the preamble window
+// runs for the survivors only, lane-strided and summed like k_freq_err's: the same bits as the batch path.
+// Returns RD_FE_NONE or the frequency error; valid in lane 0.
+template <class View>
+__device__ __forceinline__ int32_t rd_wave_parse(const View &v, const rd_devcfg &cfg, long pos, uint32_t byte, int lane) {
+    const int sw = (int)rd_swap_bits8(byte);
+    uint32_t crc = 0;
+    for (int k = 2; k < cfg.nbytes; k++) crc = rd_crc16_step(crc, (uint32_t)__builtin_amdgcn_readlane(sw, k));
+    if (cfg.nbytes <= 2 || crc != 0) return RD_FE_NONE;
+    const long j0 = pos;
+    long j1 = j0 + cfg.PL;
+    if (j1 > 2L * cfg.B) j1 = 2L * cfg.B;
+    double sum = 0.0;
+    for (long j = j0 + lane; j < j1; j += 64) {
+        const long t = j - cfg.B;
+        sum += rd_disc_f64(rd_f_f64(v, t - 1), rd_f_f64(v, t));
+    }
+    sum = rd_wave_sum(sum);
+    return rd_freq_err_hz(sum, j1 - j0, cfg.fs);
 }
 
 // filtered[j] = f[origin + j - 1], j in [0, B] (py:133,161: newest block only); origin is
@@ -1637,13 +1664,7 @@ int rd_launch_slice(const rd_layout &lay, const uint32_t *bits, size_t bits_stri
 // k_freq_err: one wave per survivor: mean of discriminated[index : index + preamble_length]
 // (:304-311) in float64, where discriminated covers absolute samples [(call-1)B, (call+1)B).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rd_swap_bits8(uint32_t b) {  // protocol.py:79-83
-    b = ((b & 0xF0) >> 4) | ((b & 0x0F) << 4);
-    b = ((b & 0xCC) >> 2) | ((b & 0x33) << 2);
-    b = ((b & 0xAA) >> 1) | ((b & 0x55) << 1);
-    return b;
-}
-
+// (rd_swap_bits8: rd_parse.h)
 __global__ __launch_bounds__(256) void k_parse_select(const rd_packet *recs, uint32_t match_cap, rd_parsed *parsed,
                                                       uint32_t *counters, int dense) {
     // records: [0, matches) one per match (stream < 0: reported by no call) and
@@ -1718,10 +1739,7 @@ __global__ __launch_bounds__(256) void k_freq_err(rd_layout lay, rd_devcfg cfg, 
             sum += rd_disc_f64(rd_f_f64(v, t - 1), rd_f_f64(v, t));
         }
         sum = rd_wave_sum(sum);
-        if (lane == 0) {
-            const double mean = sum / (double)(j1 - j0);
-            o->freq_err = -(int32_t)((mean * cfg.fs) / (2.0 * 3.141592653589793));  // int(): toward zero
-        }
+        if (lane == 0) o->freq_err = rd_freq_err_hz(sum, j1 - j0, cfg.fs);
     }
 }
 
@@ -1733,6 +1751,65 @@ void rd_launch_parse(const rd_layout &lay, const rd_devcfg &cfg, const rd_packet
     uint32_t wgs = (rec_cap + 3) / 4;
     if (wgs > 2048) wgs = 2048;
     hipLaunchKernelGGL(k_freq_err, dim3(wgs), dim3(256), 0, st, lay, cfg, parsed, rec_cap, counters);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_stream_parse: the same front half for the streaming handle's MULTI-LAUNCH form (shapes the one-launch blocks decline):
+// one wave per record of the slice kernel that ran in front of it on the stream, read where that kernel wrote them
+// (mapped host memory: the kernel boundary orders the two), results into the slot's fe array - entry i belongs to
+// record i, RD_FE_NONE for a void record or a failed CRC.  rd_wave_parse is what the one-launch blocks call: the forms
+// give identical results.
+// ------------------------------------------------------------------------------------------
+struct rd_u8_views {
+    rd_layout lay;
+    __device__ __forceinline__ rd_stream_view of(int stream) const {
+        rd_stream_view v;
+        v.base = lay.iq + (size_t)stream * lay.stream_stride;
+        v.valid_from = lay.valid_from;
+        v.n = lay.n_samples;
+        return v;
+    }
+};
+struct rd_cplx_views {
+    rd_cplx_view v;
+    __device__ __forceinline__ rd_cplx_view of(int) const { return v; }
+};
+
+template <class Views>
+__global__ __launch_bounds__(256) void k_stream_parse(Views src, rd_devcfg cfg, const rd_packet *recs, uint32_t match_cap,
+                                                      int32_t *fe, const uint32_t *counters) {
+    const int lane = threadIdx.x & 63;
+    uint32_t count = counters[RD_CNT_MATCH];
+    if (count > match_cap) count = match_cap;
+    const uint32_t nw = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < count; i += nw) {
+        const rd_packet *r = &recs[i];
+        const int stream = __builtin_amdgcn_readfirstlane(r->stream);
+        if (stream < 0) {
+            if (lane == 0) fe[i] = RD_FE_NONE;
+            continue;
+        }
+        const long pos = __builtin_amdgcn_readfirstlane(r->index);
+        const uint32_t byte = lane < RD_MAX_PKT_BYTES ? (uint32_t)r->data[lane] : 0u;
+        const int32_t e = rd_wave_parse(src.of(stream), cfg, pos, byte, lane);
+        if (lane == 0) fe[i] = e;
+    }
+}
+
+void rd_launch_stream_parse(const rd_layout &lay, const rd_devcfg &cfg, const rd_packet *recs, uint32_t match_cap,
+                            int32_t *fe, const uint32_t *counters, hipStream_t st) {
+    rd_u8_views src;
+    src.lay = lay;
+    hipLaunchKernelGGL(k_stream_parse<rd_u8_views>, dim3(rd_slice_grid(match_cap)), dim3(256), 0, st, src, cfg, recs,
+                       match_cap, fe, counters);
+}
+
+void rd_launch_cplx_stream_parse(const rd_cplx_layout &lay, const rd_devcfg &cfg, const rd_packet *recs, uint32_t match_cap,
+                                 int32_t *fe, const uint32_t *counters, hipStream_t st) {
+    rd_cplx_views src;
+    src.v = rd_cplx_view{lay.x, lay.valid_from, lay.n};
+    hipLaunchKernelGGL(k_stream_parse<rd_cplx_views>, dim3(rd_slice_grid(match_cap)), dim3(256), 0, st, src, cfg, recs,
+                       match_cap, fe, counters);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1928,6 +2005,7 @@ __global__ __launch_bounds__(RD_SB_THREADS) void k_stream_block(rd_sb_args a) {
     const uint32_t nm = s_nm;
     // ---- 4: slice + RSSI / SNR, one wave per match (k_slice_rssi's logic for batch_mode = 0) ----
     rd_packet *recs = a.recs_host + (size_t)stream * (size_t)(B + 1);
+    int32_t *fe = a.fe_host + (size_t)stream * (size_t)(B + 1);   // (used with a.parse only)
     rd_stream_view v;
     v.base = ring + 32 + 2 * (size_t)B;
     v.valid_from = a.seen_before <= 0 ? 0 : a.seen_before == 1 ? -(long)B : -(long)(B + 16);
@@ -1956,11 +2034,16 @@ __global__ __launch_bounds__(RD_SB_THREADS) void k_stream_block(rd_sb_args a) {
             const bool superseded = (same_prev && pos >= 1 && prev_first) || (same_next && pos + 1 <= B && next_first);
             if (superseded) {
                 rd_store_void(nullptr, &recs[i], lane);
+                if (a.parse && lane == 0) fe[i] = RD_FE_NONE;
                 continue;
             }
             double rssi = 0.0, snr = 0.0;
             rd_rssi_u8(v, 0, a.cfg, (long)pos, lane, rssi, snr);
             rd_store_record(nullptr, &recs[i], lane, stream, (long)a.seen_before, (long)pos, a.cfg.nbytes, byte, rssi, snr);
+            if (a.parse) {   // Parser.parse's front half for this packet (rd_wave_parse); step 5's release covers the store
+                const int32_t e = rd_wave_parse(v, a.cfg, (long)pos, byte, lane);
+                if (lane == 0) fe[i] = e;
+            }
         }
     }
     // ---- 5: count, fence, flag ----
@@ -2018,6 +2101,18 @@ static int rd_sbc_chunk_host(int slot) { return slot + (slot >> 3); }
 
 __device__ __forceinline__ double rd_load_coh(const double *p) {
     return __builtin_bit_cast(double, __hip_atomic_load((const uint64_t *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// the complex ring as the last workgroup has to read it (rd_sample_f64 of rd_math.h with coherent loads)
+struct rd_cplx_coh_view {
+    const double *base;  // sample 0 of the newest block
+    long valid_from;
+    long n;
+};
+__device__ __forceinline__ rd_d2 rd_sample_f64(const rd_cplx_coh_view &v, long n) {
+    rd_d2 y = {0.0, 0.0};
+    if (n < v.valid_from) return y;
+    return rd_rot_f64(rd_load_coh(v.base + 2 * n), rd_load_coh(v.base + 2 * n + 1), n);
 }
 
 template <int S_, int P_, uint64_t PRE_, int K_>
@@ -2201,6 +2296,7 @@ __global__ __launch_bounds__(RD_SBC_THREADS) void k_stream_block_cplx(rd_sbc_arg
         if (superseded) {
             rd_store_void(nullptr, &recs[i], lane);
             if (lane == 0) s_match[i] = pos | 0x40000000;
+            if (a.parse && lane == 0) a.fe_host[i] = RD_FE_NONE;
         }
     }
     __syncthreads();
@@ -2262,6 +2358,11 @@ __global__ __launch_bounds__(RD_SBC_THREADS) void k_stream_block_cplx(rd_sbc_arg
                 snr = noise_power > 0 ? 10.0 * log10(signal_power / noise_power) : 50.0;
             }
             rd_store_record(nullptr, &recs[i], lane, 0, (long)a.seen_before, q, a.cfg.nbytes, byte, rssi, snr);
+            if (a.parse) {   // Parser.parse's front half (rd_wave_parse), the ring read where the other workgroups' stores went
+                const rd_cplx_coh_view cv = {cur, vfrom, (long)B};
+                const int32_t e = rd_wave_parse(cv, a.cfg, q, byte, lane);
+                if (lane == 0) a.fe_host[i] = e;
+            }
         }
         parity ^= 1u;   // (the next match's partial sums go to the other set: one barrier per match)
     }

@@ -160,6 +160,17 @@ extern "C" int rd_wideband_refetch(rd_wideband *w, rd_packet *out, int cap, int 
     return rd_demod_refetch(w->dem, out, cap, n);
 }
 
+// Parser.parse's front half for every channel's packets, inside the demodulator's kernels (rd_demod_set_parse / rd_demod_parsed)
+extern "C" int rd_wb_set_parse(rd_wideband *w, int enabled) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    return rd_demod_set_parse(w->dem, enabled);
+}
+
+extern "C" int rd_wb_parsed(rd_wideband *w, rd_parsed *out, int cap, int *n) {
+    if (!w || !n) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    return rd_demod_parsed(w->dem, out, cap, n);
+}
+
 extern "C" int rd_wideband_inflight(rd_wideband *w) { return w ? rd_demod_pending(w->dem) : 0; }
 
 extern "C" int rd_wideband_copy_channelized(rd_wideband *w, uint8_t *out, size_t nbytes) {

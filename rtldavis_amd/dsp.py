@@ -17,7 +17,7 @@ import logging
 import math
 import os
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -152,6 +152,41 @@ def _packets_per_stream(recs, n: int, n_streams: int) -> List[List[Packet]]:
     return out
 
 
+def _parsed_array(fn, handle) -> np.ndarray:
+    """The rd_parsed records ``fn(handle, out, cap, n)`` returns (rd_demod_parsed / rd_wb_parsed) as a structured array
+    of ``batch.RD_PARSED_DTYPE``; RD_ERR_CAPACITY loses nothing, so the array simply grows."""
+    from .batch import RD_PARSED_DTYPE
+    cap = 64
+    while True:
+        buf = (_lib.RdParsed * cap)()
+        n = C.c_int(0)
+        rc = fn(handle, buf, cap, C.byref(n))
+        if rc == _lib.RD_ERR_CAPACITY:
+            cap = n.value + 64
+            continue
+        _lib.check(rc)
+        return np.frombuffer(buf, dtype=RD_PARSED_DTYPE, count=n.value).copy()
+
+
+def parse_packet(data) -> Optional[Tuple[int, bytes]]:
+    """The front half of ``protocol.Parser.parse`` for one packet's on-air bytes (``Packet.data``), on the host
+    (rd_parse_packet): ``(transmitter id, bit-swapped message bytes without the sync word)`` when the CRC holds
+    (protocol.py:290-318), else None."""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(bytes(data), dtype=np.uint8)
+    a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if a.size > _lib.RD_MAX_PKT_BYTES:
+        raise ValueError(f"a packet has at most {_lib.RD_MAX_PKT_BYTES} bytes")
+    msg = (C.c_uint8 * _lib.RD_MAX_PKT_BYTES)()
+    ident = C.c_int(0)
+    rc = int(_lib.lib().rd_parse_packet(a.ctypes.data, int(a.size), msg, C.byref(ident)))
+    if rc < 0:
+        raise ValueError("rd_parse_packet: bad argument")
+    if rc == 0:
+        return None
+    return int(ident.value), bytes(msg[: a.size - 2])
+
+
 class Demodulator:
     """dsp.Demodulator (dsp.py:128-253) on the GPU.
 
@@ -257,6 +292,19 @@ class Demodulator:
     def inflight(self) -> int:
         return int(_lib.lib().rd_demod_inflight(self._handle()))
 
+    # --- Parser.parse's front half inside the block's kernels (protocol.py:282-318) ---
+    def set_parse(self, on: bool = True) -> None:
+        """From the next block on, the kernels also bit-swap every packet, check its CRC and compute the survivors'
+        frequency error from the discriminator state right after that block; ``parsed()`` returns them.  Needs a
+        handle with nothing in flight; no device work (safe before fork)."""
+        _lib.check(_lib.lib().rd_demod_set_parse(self._handle(), 1 if on else 0))
+
+    def parsed(self) -> np.ndarray:
+        """CRC-valid messages of the block the last ``fetch()`` / ``demodulate()`` returned (structured array of
+        ``batch.RD_PARSED_DTYPE``, in the order of its packets) - later blocks may be in flight.  RuntimeError when
+        nothing has been fetched yet or that block was submitted with parse off."""
+        return _parsed_array(_lib.lib().rd_demod_parsed, self._handle())
+
     @property
     def input_pushed(self) -> bool:
         """True when this handle's copied blocks are written by the host straight into device memory (PCIe large BAR),
@@ -348,6 +396,15 @@ class MultiDemodulator:
     @property
     def inflight(self) -> int:
         return int(_lib.lib().rd_demod_inflight(self._h))
+
+    def set_parse(self, on: bool = True) -> None:
+        """As ``Demodulator.set_parse``, for every stream."""
+        _lib.check(_lib.lib().rd_demod_set_parse(self._h, 1 if on else 0))
+
+    def parsed(self) -> np.ndarray:
+        """As ``Demodulator.parsed``: the messages of all streams of the round the last fetch returned, sorted by
+        (stream, reference order), ``stream`` saying whose."""
+        return _parsed_array(_lib.lib().rd_demod_parsed, self._h)
 
     def reset(self) -> None:
         _lib.check(_lib.lib().rd_reset(self._h))

@@ -96,6 +96,18 @@ class WidebandReceiver:
     def inflight(self) -> int:
         return int(_lib.lib().rd_wideband_inflight(self._h))
 
+    def set_parse(self, on: bool = True) -> None:
+        """From the next chunk on, the demodulator's kernels also run ``protocol.Parser.parse``'s front half for every
+        channel's packets (``Demodulator.set_parse``).  Needs a receiver with nothing in flight."""
+        _lib.check(_lib.lib().rd_wb_set_parse(self._h, 1 if on else 0))
+
+    def parsed(self) -> np.ndarray:
+        """CRC-valid messages of the chunk the last ``fetch()`` returned, with their frequency errors (structured array
+        of ``batch.RD_PARSED_DTYPE``; ``stream`` = channel, ``call`` = chunk) - the next chunk may be in flight, which
+        ``discriminated(channel)`` does not allow."""
+        from .dsp import _parsed_array
+        return _parsed_array(_lib.lib().rd_wb_parsed, self._h)
+
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset."""
         _lib.check(_lib.lib().rd_wideband_reset(self._h))

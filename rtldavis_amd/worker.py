@@ -16,6 +16,9 @@ the caller:
   fetched AND parsed before block i+1 is submitted: ``Parser.parse`` reads ``demodulator.discriminated`` of the block
   it was given (protocol.py:304-311), which needs a handle with nothing in flight - so there is never more than one
   block on the GPU here, and ``parse()`` itself does not overlap GPU work;
+* ``pipelined_worker_loop`` / ``pipelined_worker_main`` lift that limit: the demodulator's kernels run the front half of
+  ``Parser.parse`` themselves (``Demodulator.set_parse``), so two blocks may be in flight (they are whenever the
+  producer is ahead) and the loop does only the parser's back half per fetched block;
 * ``multi_worker_main`` drains several ``data_queue``s (one per dongle / hop channel) into ONE
   ``MultiDemodulator`` launch per round.
 
@@ -138,6 +141,110 @@ def worker_loop(data_queue, result_queue, parser_factory: Callable[[], object],
         except Exception as e:
             logger.error(f"Error in DSP loop: {e}")
     if pending:
+        finish()
+
+
+def pipelined_worker_main(data_queue, result_queue, station_id: Optional[int], symbol_length: int, log_level: int) -> None:
+    """``worker_main`` on ``pipelined_worker_loop``: the same five positional arguments (worker.py:10-16), the same
+    reference ``protocol.Parser``, up to two blocks on the GPU instead of one."""
+    pipelined_worker_loop(data_queue, result_queue, reference_parser_factory(station_id, symbol_length), log_level)
+
+
+def _note_freq_err(p, transmitter: int, freq_err: int) -> None:
+    """The parser's AFC bookkeeping for one CRC-valid message (protocol.py:321-326): the frequency error goes into the
+    ring of (transmitter, current hop channel), the ring's write position moves on, and the parser remembers whose
+    message it saw last - ``Parser.set_hop`` turns the rings into the next hop's frequency correction."""
+    channel = p.hop_pattern[p.hop_idx]
+    ring, at = p.freq_err_tr_ch_list[transmitter][channel], p.freq_err_tr_ch_ptr[transmitter][channel]
+    ring[at] = freq_err
+    p.freq_err_tr_ch_ptr[transmitter][channel] = (at + 1) % p.max_tr_ch_list
+    p.transmitter = transmitter
+
+
+def messages_from_parsed(p, packets: Sequence, rows) -> list:
+    """The back half of ``Parser.parse`` (protocol.py:318-337) on parser ``p`` for one block whose front half ran on the
+    device: ``packets`` is what ``fetch()`` returned, ``rows`` that block's ``parsed()`` array.  Every row is a CRC-valid
+    message with its frequency error: AFC bookkeeping, the ``station_id`` filter, then the parser's own sensor decoding,
+    handed the ``dsp.Packet`` with the on-air bytes the message came from (as the reference's ``Message.packet``)."""
+    by_index = {int(pk.index): pk for pk in packets}
+    out = []
+    for r in rows:
+        msg_id = int(r["id"])
+        msg_data = bytes(r["data"][: int(r["nbytes"])])
+        _note_freq_err(p, msg_id, int(r["freq_err"]))
+        if p.station_id is not None and msg_id != p.station_id:
+            continue
+        msg = p._parse_sensor_data(by_index[int(r["index"])], msg_id, msg_data)
+        if msg:
+            out.append(msg)
+    return out
+
+
+def pipelined_worker_loop(data_queue, result_queue, parser_factory: Callable[[], object],
+                          log_level: int = logging.INFO, poll_s: float = 1.0) -> None:
+    """``worker_loop`` with up to TWO blocks on the GPU: the demodulator's kernels run the front half of ``Parser.parse``
+    themselves (``Demodulator.set_parse``: bit swap, CRC gate, frequency error from the state right after each block), so
+    nothing reads ``demodulator.discriminated`` and no block has to wait for a quiet handle.  Block i+1 is submitted
+    while block i is still in flight; a block is fetched when a third arrives or the queue runs dry, and its
+    ``parsed()`` rows go through ``messages_from_parsed`` - the back half of ``Parser.parse`` on the parser the factory
+    supplied.  Messages reach ``result_queue`` in block order.  The second block is in flight only while the producer
+    is ahead (blocks waiting in the queue: a backlog, a replayed capture): when the queue is empty the oldest block is
+    fetched and delivered at once rather than held back for company, so a live receiver at one block per 30 ms sees
+    ``worker_loop``'s latency and one block in flight.  Signature, stop sentinel, polling and error handling
+    (log, drop the block, go on: worker.py:56-58) are ``worker_loop``'s; the sentinel drains what is in flight."""
+    logging.basicConfig(level=log_level, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+    logger = logging.getLogger("rtldavis.worker")
+    logger.info("DSP worker process started (two blocks in flight)")
+    try:
+        p = parser_factory()
+        dem = p.demodulator
+        dem.set_parse(True)
+    except Exception as e:  # worker.py:30-32
+        logger.exception(f"Failed to initialize worker: {e}")
+        return
+    flying = 0  # blocks on the GPU whose packets have not been fetched
+
+    def finish() -> None:
+        """Fetch, parse and deliver the oldest block in flight."""
+        nonlocal flying
+        before, flying = flying, flying - 1
+        try:
+            packets = dem.fetch()
+            for msg in messages_from_parsed(p, packets, dem.parsed()):
+                result_queue.put(msg)
+        except Exception as e:  # worker.py:56-58: log, drop the block, go on
+            logger.error(f"Error in DSP loop: {e}")
+            # a fetch that failed on the device side leaves its block (and the one behind it) in flight and unfetchable:
+            # reset the demodulator, or every later fetch would fail the same way
+            left = getattr(dem, "inflight", flying)
+            if left >= before:
+                try:
+                    dem.reset()
+                    left = 0
+                except Exception as e2:
+                    logger.error(f"Error in DSP loop: demodulator reset failed: {e2}")
+            flying = min(left, flying)
+
+    while True:
+        try:
+            samples, stop = _get(data_queue, 0.0 if flying else poll_s)
+        except KeyboardInterrupt:
+            break
+        if samples is None and not stop:
+            if flying:
+                finish()  # nothing new to overlap with: deliver the oldest block
+            continue
+        if stop:
+            logger.info("Worker received stop signal")
+            break
+        if flying >= 2:
+            finish()
+        try:
+            dem.submit(samples)
+            flying += 1
+        except Exception as e:
+            logger.error(f"Error in DSP loop: {e}")
+    while flying:
         finish()
 
 

@@ -1,7 +1,13 @@
 """Latency and throughput of the streaming handle (one 8192-sample block = 30.5 ms of air time):
 the synchronous call (rd_demod_block), the same call split in two with two blocks in flight
 (rd_demod_submit / rd_demod_fetch: block i+1's host-to-device copy beside block i's kernels), and
-sixteen receivers in lock step through one handle."""
+sixteen receivers in lock step through one handle.
+
+    python tools/stream_latency.py [--parse]
+
+--parse: every handle runs Parser.parse's front half in its kernels (Demodulator.set_parse), the pipelined loops also
+read parsed() per block, and two more lines compare the routes to a frequency error: parsed() with two blocks in flight
+against fetch, then .discriminated per CRC-valid packet on a quiet handle."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,7 +16,10 @@ cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
 B = cfg.block_size
 raw = synth.synth_stream(0)
 blocks = [raw[2 * B * b: 2 * B * (b + 1)] for b in range(33)]
+PARSE = "--parse" in sys.argv[1:]
+print(f"device parse: {'on' if PARSE else 'off'}")
 dem = dsp.Demodulator(cfg)
+dem.set_parse(PARSE)
 ts = []
 npk = 0
 for rep in range(6):
@@ -30,6 +39,7 @@ print(f"first .discriminated materialisation {1e3*(t1-t0):.3f} ms")
 # for pyrtlsdr's own scaling
 cblocks = [((b[0::2].astype(np.float64) - 127.5) / 127.5 + 1j * (b[1::2].astype(np.float64) - 127.5) / 127.5) for b in blocks]
 demc = dsp.Demodulator(cfg)
+demc.set_parse(PARSE)
 tc, npc = [], 0
 for rep in range(6):
     demc.reset()
@@ -55,7 +65,7 @@ print(f"complex input, submit()/fetch(), two blocks in flight: {10 * 33 / dt:.0f
 t0 = time.perf_counter(); d = demc.discriminated; t1 = time.perf_counter()
 print(f"complex input, first .discriminated materialisation {1e3*(t1-t0):.3f} ms")
 # pipelined: two blocks in flight
-npk2 = 0
+npk2 = nmsg = 0
 t0 = time.perf_counter()
 reps = 20
 for rep in range(reps):
@@ -64,14 +74,34 @@ for rep in range(reps):
     for blk in blocks[1:]:
         dem.submit(blk)
         npk2 += len(dem.fetch())
+        nmsg += len(dem.parsed()) if PARSE else 0
     npk2 += len(dem.fetch())
+    nmsg += len(dem.parsed()) if PARSE else 0
 dt = time.perf_counter() - t0
 print(f"submit()/fetch(), two blocks in flight: {reps * 33 / dt:.0f} blocks/s = {reps * 33 * B / dt / 1e6:.1f} MS/s "
-      f"({1e3 * dt / (reps * 33):.3f} ms per block); {npk2} packets ({npk2 // reps} per stream)")
+      f"({1e3 * dt / (reps * 33):.3f} ms per block); {npk2} packets ({npk2 // reps} per stream)"
+      + (f"; parsed() per block: {nmsg} messages" if PARSE else ""))
+if PARSE:
+    # the route without device parse: a quiet handle per block, the CRC gate on the host, .discriminated per survivor
+    import math
+    demq = dsp.Demodulator(cfg)
+    demq.demodulate(blocks[0])
+    nq, t0 = 0, time.perf_counter()
+    for rep in range(reps):
+        demq.reset()
+        for blk in blocks:
+            for p in demq.demodulate(blk):
+                if dsp.parse_packet(p.data) is not None:
+                    mean = np.mean(demq.discriminated[p.index: p.index + cfg.preamble_length])
+                    nq += isinstance(-int((mean * float(cfg.sample_rate)) / (2 * math.pi)), int)
+    dt = time.perf_counter() - t0
+    print(f"demodulate(), then .discriminated per CRC-valid packet (quiet handle): {reps * 33 / dt:.0f} blocks/s "
+          f"({1e3 * dt / (reps * 33):.3f} ms per block); {nq} messages")
 # sixteen receivers in lock step
 NS = 16
 raws = synth.synth_streams(range(NS))
 md = dsp.MultiDemodulator(cfg, NS)
+md.set_parse(PARSE)
 md.demodulate(raws[:, : 2 * B])  # device state is allocated by the first call: keep that out of the timing
 for mode in ("demodulate", "submit/fetch"):
     md.reset()

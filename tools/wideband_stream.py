@@ -9,7 +9,11 @@ around work that ends in a fetch:
   - how many injected packets came back on the first pass over the capture.
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
 
-    python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--json OUT]
+    python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse] [--json OUT]
+
+--parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
+after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
+the CRC gate on the host, discriminated(channel) per CRC-valid packet.
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--capture-chunks", type=int, default=6, help="chunks in the synthesised capture")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--sample-format", default="u8", choices=["u8", "s8", "s16"], help="the capture's sample format")
+    ap.add_argument("--parse", action="store_true", help="device parse on, parsed() read per chunk; also time the route without it")
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -42,6 +47,8 @@ def main():
     raw, info = synth.synth_wideband(range(200, 200 + len(off)), off, nk * B, amplitude=0.05,
                                      sample_format=args.sample_format)
     rx = wideband.WidebandReceiver(cfg, sample_format=args.sample_format)
+    rx.set_parse(args.parse)
+    n_msgs = [0]
     step = 2 * rx.chunk_samples      # array elements per chunk
     chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
 
@@ -53,11 +60,15 @@ def main():
         for k in range(n):
             if rx.inflight == 2:
                 pk.append(rx.fetch())
+                if args.parse:
+                    n_msgs[0] += len(rx.parsed())
                 lat.append(time.perf_counter() - t_sub[len(pk) - 1])
             t_sub.append(time.perf_counter())
             rx.submit(chunks[k % nk])
         while rx.inflight:
             pk.append(rx.fetch())
+            if args.parse:
+                n_msgs[0] += len(rx.parsed())
             lat.append(time.perf_counter() - t_sub[len(pk) - 1])
         return time.perf_counter() - t0, np.array(lat), pk
 
@@ -65,6 +76,7 @@ def main():
     runs = []
     for _ in range(args.repeats):
         rx.reset()
+        n_msgs[0] = 0
         runs.append(run(args.chunks))
     walls = [r[0] for r in runs]
     wall, lat, pk = sorted(runs, key=lambda r: r[0])[len(runs) // 2]   # the median window
@@ -86,7 +98,26 @@ def main():
         "realtime_factor": air / wall,
         "injected_packets": len(info), "recovered_first_pass": int(found),
         "packets_total": int(sum(len(x) for ch in pk for x in ch)),
+        "parse": bool(args.parse),
     }
+    if args.parse:
+        import math
+        res["messages_last_window"] = n_msgs[0]
+        # the route without device parse: one chunk at a time, the receiver quiet when its state is read
+        rq = wideband.WidebandReceiver(cfg, sample_format=args.sample_format)
+        rq.demodulate(chunks[0])
+        rq.reset()
+        n, nm, t0 = max(args.chunks // 4, nk), 0, time.perf_counter()
+        for k in range(n):
+            for c, ps in enumerate(rq.demodulate(chunks[k % nk])):
+                for p in ps:
+                    if dsp.parse_packet(p.data) is not None:
+                        mean = np.mean(rq.discriminated(c)[p.index: p.index + cfg.preamble_length])
+                        nm += isinstance(-int((mean * float(cfg.sample_rate)) / (2 * math.pi)), int)
+        dt = time.perf_counter() - t0
+        res["host_route"] = {"chunks": n, "chunks_per_s": n / dt, "messages": nm}
+        print(f"parsed() per chunk: {n_msgs[0]} messages in the last window; without device parse (quiet receiver, "
+              f"discriminated(channel) per CRC-valid packet): {n / dt:.0f} chunks/s over {n} chunks, {nm} messages")
     print(f"{args.chunks} chunks of {1e3 * B / out_rate:.1f} ms air x {rx.n_channels} channels in {wall:.3f} s: "
           f"{res['chunks_per_s']:.0f} chunks/s, {res['wideband_msps']:.0f} wideband MS/s, real-time factor "
           f"{res['realtime_factor']:.0f}x")
