@@ -334,3 +334,45 @@ def freq_error(discriminated: np.ndarray, index: int, cfg: OracleConfig) -> int:
     """Frequency error of Parser.parse (src/rtldavis/protocol.py:304-311)."""
     mean = np.mean(discriminated[index: index + cfg.preamble_length])
     return -int((mean * float(cfg.sample_rate)) / (2 * math.pi))
+
+
+def freq_error_x(discriminated: np.ndarray, index: int, cfg: OracleConfig) -> float:
+    """mean * fs / 2 pi of protocol.py:304-311 before int() (the frequency error is -int() of it)."""
+    mean = np.mean(discriminated[index: index + cfg.preamble_length])
+    return float((mean * float(cfg.sample_rate)) / (2 * math.pi))
+
+
+def parse_rows(packets: Sequence[OraclePacket], discriminated: np.ndarray, cfg: OracleConfig):
+    """Parser.parse's front half (src/rtldavis/protocol.py:283-319) on one call's packets and the demodulator's
+    discriminated buffer right after that call: a ``seen`` set on the swapped bytes (:293-295), the CRC gate on
+    data[2:] (:297), id = data[2] & 7 (:314-315) and the frequency error (:304-311).  One row per packet that passes
+    ``seen``: (index, on-air hex, crc_ok, id, freq_err, x) with x = mean * fs / 2 pi before int(); id, freq_err and x
+    are given for CRC-invalid packets too (what a parser without the gate would report).  A packet without message
+    bytes (data[2:] empty: the reference would index an empty msg_data, :315) has crc_ok False and id -1."""
+    seen = set()
+    rows = []
+    for p in packets:
+        data = bytes(swap_bit_order(int(b)) for b in p.data)
+        if data in seen:
+            continue
+        seen.add(data)
+        msg = data[2:]
+        crc_ok = len(msg) > 0 and crc16_ccitt(msg) == 0
+        x = freq_error_x(discriminated, p.index, cfg)
+        rows.append((int(p.index), bytes(p.data).hex(), crc_ok, (msg[0] & 7) if msg else -1, -int(x), x))
+    return rows
+
+
+def parse_calls(blocks, cfg: OracleConfig, states: bool = False):
+    """``OracleDemodulator`` block by block (uint8 [2B] or complex128 [B] blocks) with ``parse_rows`` behind every
+    call: a list, one entry per call, of that call's rows.  The reference's own dedupe is restated in ``parse_rows``
+    on purpose: a caller that compares ``len(rows)`` with ``len(packets)`` checks that it never drops a packet the
+    demodulator kept.  ``states=True`` also returns [(packets, discriminated copy, quantized copy)] per call."""
+    dem = OracleDemodulator(cfg)
+    calls, st = [], []
+    for blk in blocks:
+        pk = dem.demodulate(blk)
+        calls.append(parse_rows(pk, dem.discriminated, cfg))
+        if states:
+            st.append((pk, dem.discriminated.copy(), dem.quantized.copy()))
+    return (calls, st) if states else calls

@@ -67,6 +67,16 @@ def _host_expected(dsp, cfg, packets, disc, stream, call):
     return out
 
 
+def _oracle_expected(blocks_per_stream, block_size):
+    """The same, from the independent oracle (oracle.dsp_oracle.parse_calls: OracleDemodulator, crc16_ccitt,
+    swap_bit_order, freq_error) on the input blocks themselves: per call, [(row, x)] of all streams, stream-major."""
+    from oracle import dsp_oracle as O
+    cfg = O.OracleConfig(19200, 14, 16, 80, PREAMBLE, block_size)
+    per = [O.parse_calls(blocks, cfg) for blocks in blocks_per_stream]
+    return [[((s, b, r[0], r[3], r[4], r[1]), r[5]) for s, calls in enumerate(per) for r in calls[b] if r[2]]
+            for b in range(len(per[0]))]
+
+
 def assert_rows_match(got, want_x, what):
     """Equality; where mean * fs / 2 pi lies within 1e-6 of an integer (the two sides sum the same float64 values in a
     different order) the frequency error may differ by 1 Hz.  Returns how many messages did not need the exception."""

@@ -16,8 +16,8 @@ import pytest
 
 from conftest import dense_calls
 from rtldavis_amd import synth
-from stream_parse_helpers import (_cfg, _crc16_bitwise, _host_expected, _pkey, _rows, _swap, _want_rows,
-                                  assert_rows_match)
+from stream_parse_helpers import (_cfg, _crc16_bitwise, _host_expected, _oracle_expected, _pkey, _rows, _swap,
+                                  _want_rows, assert_rows_match)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -400,6 +400,9 @@ def test_parsed_in_the_multi_launch_form(dsp):
         got.append(_rows(md.parsed()))
         strict = sum(assert_rows_match(got[b], want[b], (seeds, b)) for b in range(nb))
         assert got_pk == want_pk
+        # ... and the independent oracle on the same blocks
+        orc = _oracle_expected([[r[2 * B * b: 2 * B * (b + 1)] for b in range(nb)] for r in raws], B)
+        assert sum(assert_rows_match(got[b], orc[b], ("oracle", seeds, b)) for b in range(nb)) >= 1
         assert strict >= 1, "the input holds no message that is compared exactly"
         assert {r[0] for rows in got for r in rows} == set(range(len(seeds)))   # every stream's burst is CRC-valid
     # a complex128 block on the multi-launch form (the complex ring's view)
@@ -407,14 +410,16 @@ def test_parsed_in_the_multi_launch_form(dsp):
     cplx = ((raw.astype(np.float64) - 127.4) / 127.6).view(np.complex128)
     quiet, dem = dsp.Demodulator(cfg), dsp.Demodulator(cfg)
     dem.set_parse(True)
-    strict = 0
+    strict = strict_o = 0
+    orc = _oracle_expected([[cplx[B * b: B * (b + 1)] for b in range(nb)]], B)
     for b in range(nb):
         ps = quiet.demodulate(cplx[B * b: B * (b + 1)])
         want = _host_expected(dsp, cfg, ps, lambda: quiet.discriminated, 0, b)
         ps2 = dem.demodulate(cplx[B * b: B * (b + 1)])
         assert _pkey([ps2]) == _pkey([ps])
         strict += assert_rows_match(_rows(dem.parsed()), want, ("c128", b))
-    assert strict >= 1
+        strict_o += assert_rows_match(_rows(dem.parsed()), orc[b], ("c128 oracle", b))
+    assert strict >= 1 and strict_o >= 1
 
 
 @pytest.mark.gpu

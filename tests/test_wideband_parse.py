@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from rtldavis_amd import synth
-from stream_parse_helpers import _cfg, _host_expected, _pkey, _rows, assert_rows_match
+from stream_parse_helpers import _cfg, _host_expected, _oracle_expected, _pkey, _rows, assert_rows_match
 
 B = 8192
 SIX = [0, 7, 24, 25, 26, 50]   # both band edges, the centre and its neighbours
@@ -60,6 +60,9 @@ def test_wideband_parsed_with_two_chunks_in_flight(fmt):
     take()
     strict = sum(assert_rows_match(got[k], want[k], (fmt, k)) for k in range(NK))
     assert strict >= 1
+    # ... and the independent oracle on the channelized bytes of every chunk
+    orc = _oracle_expected([[got_bytes[k][c] for k in range(NK)] for c in range(len(SIX))], B)
+    assert sum(assert_rows_match(got[k], orc[k], ("oracle", fmt, k)) for k in range(NK)) >= 1
     msgs = [r for rows in got for r in rows]
     assert {r[0] for r in msgs} == set(range(len(SIX)))            # every channel yields at least one message
     for r in msgs:
