@@ -82,6 +82,37 @@ def test_create_argument_checks_without_gpu():
     assert _lib.lib().rd_batch_results(b._b, None, 0, C.byref(n)) in (_lib.RD_ERR_STATE, _lib.RD_ERR_DEVICE)
 
 
+def test_batch_size_limit_at_its_edge():
+    """rd_batch_create (host only, allocates nothing): a batch holds at most 0x0FFFFFFF 32-sample runs - a fix-up
+    entry's word index has 28 bits.  The limit itself is accepted, one more stream is RD_ERR_ARG; for the production
+    block size, where a stream's run count is even and the limit odd, the nearest count below it."""
+    import ctypes as C
+    from rtldavis_amd import _lib, dsp
+    from rtldavis_amd.dsp import _cfg_struct
+    L = _lib.lib()
+    limit = 0x0FFFFFFF
+
+    def create(cfg, ns, nb):
+        h = C.c_void_p()
+        rc = L.rd_batch_create(C.byref(_cfg_struct(cfg)), ns, nb, C.byref(h))
+        msg = L.rd_last_error() if rc else b""
+        if h:
+            L.rd_batch_destroy(h)
+        return rc, msg
+
+    # block_size 36, 2 blocks: 72 samples = 3 runs per stream, and 3 divides the limit
+    small = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 36)
+    prod = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
+    for cfg, nb in ((small, 2), (prod, 33), (prod, 1)):
+        runs = (nb * cfg.block_size + 31) // 32
+        ns = limit // runs
+        assert ns * runs <= limit < (ns + 1) * runs
+        assert create(cfg, ns, nb) == (_lib.RD_OK, b""), (cfg.block_size, nb)
+        rc, msg = create(cfg, ns + 1, nb)
+        assert rc == _lib.RD_ERR_ARG and b"batch too large" in msg, (cfg.block_size, nb, rc, msg)
+    assert (limit // 3) * 3 == limit   # the first case sits on the limit exactly
+
+
 def test_no_silent_cpu_fallback():
     """Without a GPU every compute entry point must raise, never return numbers."""
     from rtldavis_amd import _lib, batch, dsp
