@@ -378,6 +378,18 @@ int rd_wideband_copy_discriminated(rd_wideband *w, int channel, double *out, siz
  * shows the state after the NEWEST chunk and needs a quiet receiver) */
 int rd_wb_set_parse(rd_wideband *w, int enabled);
 int rd_wb_parsed(rd_wideband *w, rd_parsed *out, int cap, int *n);
+/* Retune: channel c mixes with shift_hz[c] (as rd_wb_create_fmt's; n = n_channels, |shift| <= wide rate / 2, else
+ * RD_ERR_ARG and nothing changes) from the next submitted chunk on, phase-continuous at that boundary: with t the
+ * absolute output time, the output phase is frac((s_c t + P_c) / out_rate), P_c an integer in [0, out_rate) that is 0
+ * after create and reset, and a retune s -> s' at the boundary t_b sets P' = (P + (s - s') t_b) mod out_rate.  Every
+ * output from t_b on is filtered with the new band-pass, the few whose window reaches into the previous chunk included.
+ * Host bookkeeping only: no device work, no wait, legal with chunks in flight; the next rd_wideband_submit queues the
+ * rebuild of the changed channels' tables (a kernel) in front of its channelizer.  Calls before that submit collapse
+ * into the last; shifts equal to those in force change nothing.  Filter history, clock and demodulator state are kept.
+ * rd_wideband_reset drops a pending retune and returns to the constructed shifts with P = 0.
+ * rd_wb_tuning: the tuning the next submitted chunk will use, shifts as given and P_c (host only, no device needed). */
+int rd_wb_retune(rd_wideband *w, const int64_t *shift_hz, int n);
+int rd_wb_tuning(rd_wideband *w, int64_t *shift_hz, int64_t *phase, int n);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

@@ -146,6 +146,8 @@ SIGNATURES = {
     "rd_wideband_copy_discriminated": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "rd_wb_set_parse": (C.c_int, [_P, C.c_int]),
     "rd_wb_parsed": (C.c_int, [_P, C.POINTER(RdParsed), C.c_int, C.POINTER(C.c_int)]),
+    "rd_wb_retune": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_tuning": (C.c_int, [_P, _P, _P, C.c_int]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),

@@ -76,6 +76,15 @@
 // b128 reads are 2-way bank conflicted by the bank rule (not measured).  Measured: 0.40 ms per second of capture,
 // 2.66 x uint8 - twice the MFMAs on twice the bytes, the rest at one wave per SIMD; 2480 x real time.  Not tried: a
 // 64-output tile (two workgroups per CU, but twice the A traffic from L2).
+//
+// RETUNE (streaming form only; rd_wideband.hip: rd_wb_retune).  With a phase accumulator P_c, an integer in [0, Fo) that is
+// 0 after create and reset, and t the absolute output time,
+//   z_c[t] = e^{-j 2 pi frac((shift_c t + P_c) / Fo)} sum_k g_c[k] x[D t - k],   g_c[k] = h[k] e^{+j 2 pi shift_c k / Fw}
+// - the definition above when P_c = 0.  A retune shift -> shift' at a chunk boundary t_b replaces shift, g and
+// P -> P' = (P + (shift - shift') t_b) mod Fo, exact integer arithmetic: the phase is continuous at t_b.  Every output
+// from t_b on is filtered with the NEW band-pass g', the few whose window reaches back into the previous chunk included:
+// the history is not re-mixed at the old frequency (the samples are kept, not the old mixer's products).  The tables of
+// the channels that change are rebuilt in place by k_chan_retune, queued between the two chunks' k_channelize.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -127,9 +136,17 @@ struct rd_chan {
     std::vector<uint16_t> h_amat;  // f16 A operand in fragment order [group][K step][term][row block][lane][8]
     std::vector<float> h_dc;       // [channel][RD_CHAN_DCN][2]: -127.4 (1+j) sum of the taps a given output sees; the 32-step phasor
     std::vector<int64_t> shifts;   // Hz, reduced mod out_rate
+    // the tuning the tables hold (rd_chan_retune): the shifts as given, and the phase accumulators P_c in [0, out_rate)
+    std::vector<int64_t> shift_hz, phase;
+    std::vector<double> taps;      // the float64 prototype (a retune rebuilds a channel's tables from it)
+    double tap_scale = 1.0;        // 2^s
     uint16_t *d_amat = nullptr;
     float *d_dc = nullptr;
     int64_t *d_shifts = nullptr;
+    int64_t *d_phase = nullptr;
+    double *d_taps = nullptr;      // streaming form only: k_chan_retune's input, uploaded once
+    int64_t *h_rt = nullptr;       // pinned: two slots of [n_channels][4] retune records (channel, shift, shift mod Fo, P)
+    int64_t *d_rt = nullptr;       // one slot on the device (its copies and kernels are ordered by the stream)
     uint8_t *d_wide = nullptr;     // resident capture, rd_fmt_in_bps bytes per sample
     size_t wide_cap = 0, wide_n = 0;
     bool dev_ready = false;
@@ -179,7 +196,8 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
                                                     const int64_t *shifts, int T, int D, int n_ch, int n_early,
                                                     long out_rate, float gain, float tap_unscale, long n_out,
                                                     uint8_t *out, size_t out_stride, int xs_bytes,
-                                                    const uint8_t *__restrict__ prev, long t_base_mod) {
+                                                    const uint8_t *__restrict__ prev, long t_base_mod,
+                                                    const int64_t *phase) {
     extern __shared__ uint8_t lds[];
     uint8_t *xs = lds;                            // window samples 0 .. span-1, LB bytes each
     constexpr int IB = rd_fmt_in_bps(FMT), LB = rd_fmt_lds_bps(FMT), KC = rd_fmt_kc(FMT);
@@ -321,9 +339,9 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
         const int ch = 16 * (RD_CHAN_RBG * grp + wave) + (row >> 1);
         if (ch >= n_ch) continue;
-        // frac(shift t / Fo) exactly: shift, tm < Fo < 2^26, the product is exact in float64; the quotient from a
-        // multiplication by 1 / Fo is off by one at most
-        const double x = (double)shifts[ch] * (double)tm;
+        // frac((shift t + P) / Fo) exactly: shift, tm, P < Fo < 2^26, product and sum are exact in float64 (< 2^53; P is 0
+        // until a retune, rd_chan_retune); the quotient from a multiplication by 1 / Fo is off by one at most
+        const double x = (double)shifts[ch] * (double)tm + (double)phase[ch];
         double rm = __builtin_fma(-floor(x * inv_fo), fo, x);
         if (rm < 0.0) rm += fo;
         if (rm >= fo) rm -= fo;
@@ -348,6 +366,85 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
             const float c2 = cs * ci - sn * si, s2 = sn * ci + cs * si;
             cs = c2; sn = s2;
         }
+    }
+}
+
+// RETUNE (rd_chan_retune; rd_wideband.hip: rd_wb_retune): the tables of the channels whose tuning changes, rebuilt in
+// place between two chunks of a stream.  One workgroup per record (channel, shift, shift mod Fo, P); it writes what
+// chan_build_channel writes for that channel, by the same expressions - the fp32 taps g through the exact 64-bit
+// remainder (shift k) mod Fw and float64 sine / cosine, their two-term f16 split in the A operand's fragment order (every
+// K step, both lane halves, both terms, the zero taps included: one 16-byte store per fragment), the DC entries summed in
+// float64 in the host's order (one lane: t_pad dependent additions while the rest of its wave idles, beside the other
+// waves' stores; not measured yet), the 32-output rotation, shift mod Fo and P.
+// Equal to the host's tables UP TO LIBM: the device's float64 sin / cos need not equal glibc's in the last bit.  Every
+// value is rounded to fp32 before anything else uses it, which absorbs a last-bit difference unless the product lies
+// within a float64 ulp or two of an fp32 rounding boundary (about 2^-28 per tap), so the tests that compare a receiver
+// reset after a retune with a fresh one byte for byte (tests/test_wideband_retune.py) rely on that, not on a guarantee.
+// Should one fail on a new ROCm with a single differing table entry: the definition holds either way (both are the
+// correctly-derived fp32 taps within half an ulp + libm's error, inside term 1 of tests/chan_bound.py) - change that test's
+// seed or compare it through the model's bound, do not loosen the kernel.  The f16 values: a 2^s is an fp32 number and so is what the first digit leaves of it,
+// so both digits are one rounding each, float -> half.  The stream orders it behind the previous chunk's k_channelize and
+// in front of the next one's: no second copy of the tables.
+__global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__ rec, const double *__restrict__ taps,
+                                                     int fmt, int T, int t_pad, int D, long out_rate, double tap_scale,
+                                                     uint4 *amat, float2 *dc, int64_t *shifts, int64_t *phase) {
+    extern __shared__ uint8_t lds[];
+    float2 *g = (float2 *)lds;                    // the channel's fp32 taps (g_r, g_i), k < t_pad
+    const int c = (int)rec[4 * blockIdx.x];
+    const long shift = rec[4 * blockIdx.x + 1], smod = rec[4 * blockIdx.x + 2];
+    const long fw = out_rate * D;
+    const double wide_rate = (double)out_rate * D;
+    for (int k = threadIdx.x; k < t_pad; k += blockDim.x) {
+        float2 v = float2{0.0f, 0.0f};
+        if (k < T) {
+            long r = (shift * k) % fw;            // |shift| <= Fw / 2 < 2^37, k < 2^13: exact in 64 bits
+            if (r < 0) r += fw;
+            const double ph = 2.0 * M_PI * ((double)r / wide_rate);
+            v = float2{(float)(taps[k] * cos(ph)), (float)(taps[k] * sin(ph))};
+        }
+        g[k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        shifts[c] = smod;
+        phase[c] = rec[4 * blockIdx.x + 3];
+        const long inc = (smod * 32) % out_rate;
+        const double ph = -2.0 * M_PI * ((double)inc / (double)out_rate);
+        dc[(size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1] = float2{(float)cos(ph), (float)sin(ph)};
+    }
+    if (threadIdx.x == 64 && fmt != RD_IQ_S16) {   // (a lane of the second wave: the first one's has the rotation)
+        const double dc_level = fmt == RD_IQ_U8 ? 127.4 : 128.0;
+        double sr = 0.0, si = 0.0;
+        int kdone = 0;
+        for (int t = 0; t <= RD_CHAN_EARLY; t++) {
+            const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)D * t : (long)t_pad - 1;
+            for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += (double)g[kdone].x; si += (double)g[kdone].y; }
+            dc[(size_t)c * RD_CHAN_DCN + t] = float2{(float)(-dc_level * (sr - si)), (float)(-dc_level * (sr + si))};
+        }
+    }
+    const int kc = fmt == RD_IQ_S16 ? RD_CHAN_KC / 2 : RD_CHAN_KC, per_lane = kc / 2, n_q = t_pad / kc + 1;
+    const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
+    // one fragment (8 f16 = 16 bytes) per item: K step q, term, lane half hh, part
+    for (int it = threadIdx.x; it < 8 * n_q; it += blockDim.x) {
+        const int part = it & 1, hh = (it >> 1) & 1, tm = (it >> 2) & 1, q = it >> 3;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int el = 0; el < 8; el++) {
+            // the inverse of chan_build_channel's element position: (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi) x 2
+            const int comp = (el >> 1) & 1;
+            const int sl = fmt == RD_IQ_S16 ? el >> 2 : 2 * (el >> 2) + (el & 1), dig = fmt == RD_IQ_S16 ? el & 1 : 1;
+            const int k = t_pad - (q * kc + hh * per_lane + sl);
+            if (k < 0 || k >= t_pad) continue;
+            const float2 gk = g[k];
+            const double a = part == 0 ? (comp == 0 ? (double)gk.x : -(double)gk.y) : (comp == 0 ? (double)gk.y : (double)gk.x);
+            const double as = a * tap_scale * (dig == 0 ? 1.0 / 256.0 : 1.0);
+            const _Float16 hi = (_Float16)(float)as;
+            const _Float16 lo = (_Float16)(float)(as - (double)hi);
+            const uint32_t bits = (uint32_t)__builtin_bit_cast(uint16_t, tm == 0 ? hi : lo);
+            w[el >> 1] |= bits << (16 * (el & 1));
+        }
+        const int lane = 32 * hh + r0 + part;
+        amat[((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane] = uint4{w[0], w[1], w[2], w[3]};
     }
 }
 
@@ -376,6 +473,79 @@ static double f16_val(uint16_t b) {
 static size_t chan_lds_bytes(int fmt, int decim, int t_pad) {
     const size_t span = (size_t)(RD_CHAN_TT - 1) * decim + t_pad + rd_fmt_kc(fmt);
     return (rd_fmt_lds_bps(fmt) * span + 15 + 16) & ~(size_t)15;
+}
+
+// The tables of channel c for the shift `shift_hz` (Hz, as given) and the phase accumulator `phase` (header: RETUNE; 0 at
+// create): its two rows of the A operand, its DC entries and 32-output rotation, shifts[c].  On the host - rd_chan_create_fmt
+// for every channel, rd_chan_retune for a channel retuned before the device tables exist; k_chan_retune is the same on
+// the device.
+static void chan_build_channel(rd_chan *h, int c, int64_t shift_hz, int64_t phase) {
+    const rd_chan_config *cfg = &h->cfg;
+    const int fmt = h->fmt, T = cfg->n_taps, t_pad = h->t_pad, kc = rd_fmt_kc(fmt), n_q = t_pad / kc + 1;
+    const double *taps = h->taps.data();
+    const double tap_scale = h->tap_scale;
+    const double wide_rate = (double)cfg->out_rate * cfg->decim;
+    const double dc_level = fmt == RD_IQ_U8 ? 127.4 : fmt == RD_IQ_S8 ? 128.0 : 0.0;
+    h->shift_hz[c] = shift_hz;
+    h->phase[c] = phase;
+    h->shifts[c] = ((shift_hz % cfg->out_rate) + cfg->out_rate) % cfg->out_rate;  // shift mod Fo in [0, Fo): all the output phasor needs
+    std::vector<double> gr(t_pad), gi(t_pad);
+    for (int k = 0; k < t_pad; k++) {
+        gr[k] = gi[k] = 0.0;
+        if (k >= T) continue;
+        // g_c[k] = h[k] e^{+j 2 pi shift k / Fw}; the phase through an exact integer remainder
+        const __int128 prod = (__int128)shift_hz * k;
+        const long fw = (long)cfg->out_rate * cfg->decim;
+        long r = (long)(prod % fw);
+        if (r < 0) r += fw;
+        const double ph = 2.0 * M_PI * ((double)r / wide_rate);
+        gr[k] = (double)(float)(taps[k] * cos(ph));  // the fp32 taps are the definition's taps on the device
+        gi[k] = (double)(float)(taps[k] * sin(ph));
+    }
+    // DC term: output t sees taps k <= D t (zero history before)
+    double sr = 0.0, si = 0.0;
+    int kdone = 0;
+    for (int t = 0; t <= RD_CHAN_EARLY; t++) {
+        // (RD_IQ_S8 stages 0x80 = the value 0 before the capture: every output sees all the taps)
+        const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)cfg->decim * t : (long)t_pad - 1;
+        for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += gr[kdone]; si += gi[kdone]; }
+        // lut(b) = (b - 127.4) / 127.6 and the kernel sums g b: the constant is -127.4 (1 + j)(sr + j si)
+        // (128 for the offset-binary bytes of RD_IQ_S8, nothing for RD_IQ_S16)
+        h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2] = (float)(-dc_level * (sr - si));
+        h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2 + 1] = (float)(-dc_level * (sr + si));
+    }
+    {   // the rotation that takes the output phasor 32 output times on (exact remainder, float64 sin / cos)
+        const long inc = (long)(((__int128)h->shifts[c] * 32) % cfg->out_rate);
+        const double ph = -2.0 * M_PI * ((double)inc / (double)cfg->out_rate);
+        h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2] = (float)cos(ph);
+        h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2 + 1] = (float)sin(ph);
+    }
+    // rows 2c (re) and 2c+1 (im); kappa = 2 i + comp, window sample i = t_pad - 1 - k
+    const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
+    // RD_IQ_S16: kappa = 4 i + 2 comp + digit, a lane holds two samples (Ilo Ihi Qlo Qhi each); the low digit's taps
+    // are scaled by 2^-8 against the high digit's
+    const int per_lane = kc / 2, n_dig = fmt == RD_IQ_S16 ? 2 : 1;
+    for (int i = 0; i < kc * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
+        const int k = t_pad - i;
+        if (k < 0 || k >= t_pad) continue;  // (zero taps: the entries stay 0)
+        const int q = i / kc, hh = (i % kc) / per_lane, sl = i % per_lane;  // K step, lane half, sample within the lane's
+        for (int part = 0; part < 2; part++)
+            for (int comp = 0; comp < 2; comp++)
+                for (int dig = 0; dig < n_dig; dig++) {
+                    const double a = part == 0 ? (comp == 0 ? gr[k] : -gi[k]) : (comp == 0 ? gi[k] : gr[k]);
+                    const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
+                    const uint16_t hi = f16_rn(as), lo = f16_rn(as - f16_val(hi));
+                    const uint16_t term[RD_CHAN_TERMS] = {hi, lo};
+                    const int lane = 32 * hh + r0 + part;
+                    // element position inside the fragment, see the kernel's B fragments:
+                    // (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi | the same of the second sample)
+                    const int el = fmt == RD_IQ_S16 ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
+                    for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
+                        const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + el;
+                        h->h_amat[at] = term[tm];
+                    }
+                }
+    }
 }
 
 extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, const int64_t *shift_hz, rd_chan **out) {
@@ -408,9 +578,10 @@ extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const doub
     const int n_q = t_pad / kc + 1;  // the window starts one sample early (aligned): one more K step
     h->h_amat.assign((size_t)h->n_groups * n_q * (RD_CHAN_Q_BYTES / 2), 0);
     h->h_dc.assign((size_t)cfg->n_channels * RD_CHAN_DCN * 2, 0.0f);
-    h->shifts.resize(cfg->n_channels);  // shift mod Fo in [0, Fo): all the output phasor needs
-    for (int c = 0; c < cfg->n_channels; c++) h->shifts[c] = ((shift_hz[c] % cfg->out_rate) + cfg->out_rate) % cfg->out_rate;
-    const double wide_rate = (double)cfg->out_rate * cfg->decim;
+    h->shifts.resize(cfg->n_channels);
+    h->shift_hz.resize(cfg->n_channels);
+    h->phase.resize(cfg->n_channels);
+    h->taps.assign(taps, taps + T);
     // every |g_c[k]| <= max |h[k]|: scale the taps by the power of two that brings that just below 2^15 (f16: 11
     // significant bits from 2^-14 up), the kernel multiplies the sums back
     double hmax = 0.0;
@@ -419,70 +590,11 @@ extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const doub
     if (hmax > 0.0) sexp = 14 - (int)std::ceil(std::log2(hmax));
     if (sexp > 60) sexp = 60;
     if (sexp < -60) sexp = -60;
-    const double tap_scale = std::ldexp(1.0, sexp);
+    h->tap_scale = std::ldexp(1.0, sexp);
     // (+24: the samples enter as k 2^-24; RD_IQ_S16: the low digit's taps carry 2^-8 more, so that the high digit's
     // factor 256 stays inside f16)
     h->tap_unscale = (float)std::ldexp(1.0, -sexp + 24 + (fmt == RD_IQ_S16 ? 8 : 0));
-    const double dc_level = fmt == RD_IQ_U8 ? 127.4 : fmt == RD_IQ_S8 ? 128.0 : 0.0;
-    std::vector<double> gr(t_pad), gi(t_pad);
-    for (int c = 0; c < cfg->n_channels; c++) {
-        for (int k = 0; k < t_pad; k++) {
-            gr[k] = gi[k] = 0.0;
-            if (k >= T) continue;
-            // g_c[k] = h[k] e^{+j 2 pi shift k / Fw}; the phase through an exact integer remainder
-            const __int128 prod = (__int128)shift_hz[c] * k;
-            const long fw = (long)cfg->out_rate * cfg->decim;
-            long r = (long)(prod % fw);
-            if (r < 0) r += fw;
-            const double ph = 2.0 * M_PI * ((double)r / wide_rate);
-            gr[k] = (double)(float)(taps[k] * cos(ph));  // the fp32 taps are the definition's taps on the device
-            gi[k] = (double)(float)(taps[k] * sin(ph));
-        }
-        // DC term: output t sees taps k <= D t (zero history before)
-        double sr = 0.0, si = 0.0;
-        int kdone = 0;
-        for (int t = 0; t <= RD_CHAN_EARLY; t++) {
-            // (RD_IQ_S8 stages 0x80 = the value 0 before the capture: every output sees all the taps)
-            const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)cfg->decim * t : (long)t_pad - 1;
-            for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += gr[kdone]; si += gi[kdone]; }
-            // lut(b) = (b - 127.4) / 127.6 and the kernel sums g b: the constant is -127.4 (1 + j)(sr + j si)
-            // (128 for the offset-binary bytes of RD_IQ_S8, nothing for RD_IQ_S16)
-            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2] = (float)(-dc_level * (sr - si));
-            h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2 + 1] = (float)(-dc_level * (sr + si));
-        }
-        {   // the rotation that takes the output phasor 32 output times on (exact remainder, float64 sin / cos)
-            const long inc = (long)(((__int128)h->shifts[c] * 32) % cfg->out_rate);
-            const double ph = -2.0 * M_PI * ((double)inc / (double)cfg->out_rate);
-            h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2] = (float)cos(ph);
-            h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2 + 1] = (float)sin(ph);
-        }
-        // rows 2c (re) and 2c+1 (im); kappa = 2 i + comp, window sample i = t_pad - 1 - k
-        const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
-        // RD_IQ_S16: kappa = 4 i + 2 comp + digit, a lane holds two samples (Ilo Ihi Qlo Qhi each); the low digit's taps
-        // are scaled by 2^-8 against the high digit's
-        const int per_lane = kc / 2, n_dig = fmt == RD_IQ_S16 ? 2 : 1;
-        for (int i = 0; i < kc * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
-            const int k = t_pad - i;
-            if (k < 0 || k >= t_pad) continue;  // (zero taps: the entries stay 0)
-            const int q = i / kc, hh = (i % kc) / per_lane, sl = i % per_lane;  // K step, lane half, sample within the lane's
-            for (int part = 0; part < 2; part++)
-                for (int comp = 0; comp < 2; comp++)
-                    for (int dig = 0; dig < n_dig; dig++) {
-                        const double a = part == 0 ? (comp == 0 ? gr[k] : -gi[k]) : (comp == 0 ? gi[k] : gr[k]);
-                        const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
-                        const uint16_t hi = f16_rn(as), lo = f16_rn(as - f16_val(hi));
-                        const uint16_t term[RD_CHAN_TERMS] = {hi, lo};
-                        const int lane = 32 * hh + r0 + part;
-                        // element position inside the fragment, see the kernel's B fragments:
-                        // (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi | the same of the second sample)
-                        const int el = fmt == RD_IQ_S16 ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
-                        for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
-                            const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + el;
-                            h->h_amat[at] = term[tm];
-                        }
-                    }
-        }
-    }
+    for (int c = 0; c < cfg->n_channels; c++) chan_build_channel(h, c, shift_hz[c], 0);
     *out = h;
     return RD_OK;
 }
@@ -493,6 +605,7 @@ extern "C" void rd_chan_destroy(rd_chan *h) {
     if (h->dev_ready && h->pid == getpid()) {
         if (h->device >= 0) hipSetDevice(h->device);
         hipFree(h->d_amat); hipFree(h->d_dc); hipFree(h->d_shifts); hipFree(h->d_wide);
+        hipFree(h->d_phase); hipFree(h->d_taps); hipFree(h->d_rt); hipHostFree(h->h_rt);
     }
     delete h;
 }
@@ -510,6 +623,8 @@ static int chan_alloc(rd_chan *h, size_t n_wide) {
         CHK(hipMemcpy(h->d_dc, h->h_dc.data(), h->h_dc.size() * sizeof(float), hipMemcpyHostToDevice));
         CHK(hipMalloc(&h->d_shifts, h->shifts.size() * sizeof(int64_t)));
         CHK(hipMemcpy(h->d_shifts, h->shifts.data(), h->shifts.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        CHK(hipMalloc(&h->d_phase, h->phase.size() * sizeof(int64_t)));
+        CHK(hipMemcpy(h->d_phase, h->phase.data(), h->phase.size() * sizeof(int64_t), hipMemcpyHostToDevice));
         h->dev_ready = true;
     }
     if (n_wide > h->wide_cap) {
@@ -557,13 +672,13 @@ static int chan_launch(rd_chan *h, bool stream, const uint8_t *wide, long n_wide
     const size_t lds = chan_lds_bytes(h->fmt, D, T);
     const uint4 *amat = (const uint4 *)h->d_amat;
     const float2 *dc = (const float2 *)h->d_dc;
-    const int64_t *shifts = h->d_shifts;
+    const int64_t *shifts = h->d_shifts, *phase = h->d_phase;
     long out_rate = (long)h->cfg.out_rate;
     float gain = (float)h->cfg.gain, tap_unscale = h->tap_unscale;
     uint8_t *out = (uint8_t *)dst;
     int xs_bytes = (int)lds;
     void *args[] = {&wide, &n_wide, &amat, &dc, &shifts, &T, &D, &n_ch, &n_early, &out_rate, &gain, &tap_unscale, &n_out,
-                    &out, &dst_stride, &xs_bytes, &prev, &t_base_mod};   // k_channelize's parameters, in order
+                    &out, &dst_stride, &xs_bytes, &prev, &t_base_mod, &phase};   // k_channelize's parameters, in order
     CHK(hipLaunchKernel(chan_kernel(stream, h->fmt), dim3(gx, (unsigned)h->n_groups), dim3(256), args, lds, st));
     CHK(hipGetLastError());
     return RD_OK;
@@ -610,7 +725,60 @@ int rd_chan_stream_prepare(rd_chan *h) {
     if (rc) return rc;
     const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
     CHK(hipFuncSetAttribute(chan_kernel(true, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (!h->d_taps) {   // what a retune needs: the float64 taps, and the records' staging (two pinned slots, one on the device)
+        const size_t rt_bytes = (size_t)h->cfg.n_channels * 4 * sizeof(int64_t);
+        CHK(hipMalloc(&h->d_taps, h->taps.size() * sizeof(double)));
+        CHK(hipMemcpy(h->d_taps, h->taps.data(), h->taps.size() * sizeof(double), hipMemcpyHostToDevice));
+        CHK(hipMalloc(&h->d_rt, rt_bytes));
+        CHK(hipHostMalloc((void **)&h->h_rt, 2 * rt_bytes, hipHostMallocDefault));
+        CHK(hipFuncSetAttribute((const void *)k_chan_retune, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(h->t_pad * sizeof(float2))));
+    }
     return RD_OK;
+}
+
+// Retune n channels (header: RETUNE): rec = n x (channel, shift in Hz as given, phase accumulator P in [0, out_rate)),
+// the caller's arithmetic (rd_wideband.hip).  Before the device tables exist the channels are rebuilt on the host, which
+// chan_alloc then uploads; afterwards the records go through pinned slot `slot` (0 / 1: the caller knows that slot's
+// last copy has completed) and k_chan_retune, both queued on st - in front of the next rd_chan_stream_launch on it.
+int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t st) {
+    if (!h || (n > 0 && !rec)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    const int n_ch = h->cfg.n_channels;
+    const int64_t fo = h->cfg.out_rate;
+    if (n < 0 || n > n_ch || (slot & ~1)) return rd_fail_msg(RD_ERR_ARG, "retune: %d records for %d channels, slot %d", n, n_ch, slot);
+    for (int i = 0; i < n; i++)
+        if (rec[3 * i] < 0 || rec[3 * i] >= n_ch || rec[3 * i + 2] < 0 || rec[3 * i + 2] >= fo)
+            return rd_fail_msg(RD_ERR_ARG, "retune: record %d out of range", i);
+    if (n == 0) return RD_OK;
+    if (!h->dev_ready) {
+        for (int i = 0; i < n; i++) chan_build_channel(h, (int)rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]);
+        return RD_OK;
+    }
+    if (!h->d_taps) return rd_fail_msg(RD_ERR_STATE, "rd_chan_stream_prepare first");
+    int64_t *stage = h->h_rt + (size_t)slot * n_ch * 4;
+    for (int i = 0; i < n; i++) {
+        stage[4 * i] = rec[3 * i]; stage[4 * i + 1] = rec[3 * i + 1]; stage[4 * i + 2] = ((rec[3 * i + 1] % fo) + fo) % fo;
+        stage[4 * i + 3] = rec[3 * i + 2];
+    }
+    CHK(hipMemcpyAsync(h->d_rt, stage, (size_t)n * 4 * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_chan_retune, dim3((unsigned)n), dim3(256), h->t_pad * sizeof(float2), st, (const int64_t *)h->d_rt,
+                       (const double *)h->d_taps, h->fmt, h->cfg.n_taps, h->t_pad, h->cfg.decim, (long)h->cfg.out_rate,
+                       h->tap_scale, (uint4 *)h->d_amat, (float2 *)h->d_dc, h->d_shifts, h->d_phase);
+    CHK(hipGetLastError());
+    // queued: only now does the host's record of what the tables hold follow (a failure above leaves it, and the
+    // caller's pending retune, as they were - the next submit tries again)
+    for (int i = 0; i < n; i++) {
+        const int c = (int)stage[4 * i];
+        h->shift_hz[c] = stage[4 * i + 1];
+        h->shifts[c] = stage[4 * i + 2];
+        h->phase[c] = stage[4 * i + 3];
+    }
+    return RD_OK;
+}
+
+void rd_chan_tuning(const rd_chan *h, const int64_t **shift_hz, const int64_t **phase) {
+    *shift_hz = h->shift_hz.data();
+    *phase = h->phase.data();
 }
 
 // Channelize one chunk of n_out * decim samples (of the handle's format) at `wide` (device) whose predecessor lies at `prev` (null: zero history)
@@ -632,4 +800,6 @@ int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, 
 }
 
 int rd_chan_n_channels(const rd_chan *h) { return h ? h->cfg.n_channels : 0; }
+int64_t rd_chan_out_rate(const rd_chan *h) { return h ? h->cfg.out_rate : 0; }
+int64_t rd_chan_wide_rate(const rd_chan *h) { return h ? (int64_t)h->cfg.out_rate * h->cfg.decim : 0; }
 int rd_chan_bytes_per_sample(const rd_chan *h) { return h ? rd_fmt_in_bps(h->fmt) : 0; }

@@ -204,7 +204,14 @@ void rd_launch_pack_bytes(const uint8_t *in01, uint32_t *words, size_t n, hipStr
 int rd_chan_stream_prepare(rd_chan *h);
 int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, size_t n_out, uint64_t t_base, void *dst,
                           size_t dst_stride, hipStream_t st);
+// Retune n channels of the handle (rd_channelizer.hip: RETUNE): rec = n x (channel, shift in Hz, phase accumulator P).
+// On the host before the device tables exist; afterwards through pinned slot `slot` (0 / 1, free by the caller's
+// ordering) and k_chan_retune, queued on st.  rd_chan_tuning: the shifts (as given) and phases the tables hold.
+int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t st);
+void rd_chan_tuning(const rd_chan *h, const int64_t **shift_hz, const int64_t **phase);
 int rd_chan_n_channels(const rd_chan *h);
+int64_t rd_chan_out_rate(const rd_chan *h);
+int64_t rd_chan_wide_rate(const rd_chan *h);
 int rd_chan_bytes_per_sample(const rd_chan *h);   // of an IQ pair in the handle's sample format
 // rd_api.hip: the handle's device state and its two non-blocking streams (compute, copy)
 int rd_demod_prepare(rd_demod *h, hipStream_t *st, hipStream_t *st_copy);

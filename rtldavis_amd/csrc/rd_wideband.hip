@@ -13,7 +13,16 @@
 // The output clock is a 64-bit count kept here; the kernel gets it mod out_rate, so the mixer phase stays exact however
 // long the receiver runs.  A fetch that times out loses the chunk's packets, not the clock or the history: both advance
 // at submit.
+//
+// Retune (rd_wb_retune; the definition: rd_channelizer.hip, RETUNE): new mixer frequencies for any channels from the next
+// chunk boundary on, phase-continuous, with chunks in flight.  The call only records the wanted shifts; the next submit
+// turns them into (shift, P) at its boundary t_b = clock - P' = (P + (s - s') t_b) mod Fo, exact integers - and queues
+// the records of the channels that change and k_chan_retune on the compute stream in front of that chunk's k_channelize
+// (the previous chunk's is earlier on the same stream, so one set of tables serves).  The records travel through a
+// pinned slot of the chunk's parity: chunk k-2, the slot's last user, has been fetched or dropped - all its work is done.
+// Before the first submit the tables are still the host's, and are rebuilt there.
 #include <cstring>
+#include <vector>
 #include <unistd.h>
 
 #include <hip/hip_runtime.h>
@@ -45,7 +54,44 @@ struct rd_wideband {
     uint8_t *d_out[2] = {nullptr, nullptr};        // channelized chunks [n_channels][2 B]
     hipEvent_t e_in[2] = {nullptr, nullptr};       // chunk buffer k & 1 copied
     hipEvent_t e_chan[2] = {nullptr, nullptr};     // chunk k's channelizer done
+    // tuning: the constructed shifts (reset() returns to them), the tuning in force (that of the last chunk submitted, or
+    // (plan, 0) after create / reset - the channelizer's tables may still hold another, rd_chan_tuning) and the shifts
+    // the last rd_wb_retune asked for
+    std::vector<int64_t> plan, shift, phase, want;
+    bool pending = false;                          // a retune waits for the next submit
+    bool restored = false;                         // reset() since the last submit: the tables may hold an earlier retune
+    std::vector<int64_t> rec, next_shift, next_phase;   // scratch: a submit's retune records and its tuning
 };
+
+// the tuning the next submitted chunk will use, channel c: the pending shift takes over at t_b = clock
+static void wb_next_tuning(const rd_wideband *w, int c, int64_t *shift, int64_t *phase) {
+    *shift = w->pending ? w->want[c] : w->shift[c];
+    const __int128 fo = rd_chan_out_rate(w->chan);
+    __int128 p = (__int128)w->phase[c] + (__int128)(w->shift[c] - *shift) * (__int128)(w->clock % (uint64_t)fo);
+    p %= fo;
+    *phase = (int64_t)(p < 0 ? p + fo : p);
+}
+
+// Make the channelizer's tables those of the next chunk's tuning: the channels that differ, on the host before the device
+// tables exist, else as records in pinned slot `slot` and k_chan_retune on the compute stream.  Nothing differs: nothing queued.
+static int wb_apply_tuning(rd_wideband *w, int slot) {
+    if (!w->pending && !w->restored) return RD_OK;
+    const int64_t *ts, *tp;
+    rd_chan_tuning(w->chan, &ts, &tp);
+    w->rec.clear();
+    std::vector<int64_t> &ns = w->next_shift, &np = w->next_phase;
+    ns.resize(w->n_ch);
+    np.resize(w->n_ch);
+    for (int c = 0; c < w->n_ch; c++) {
+        wb_next_tuning(w, c, &ns[c], &np[c]);
+        if (ns[c] != ts[c] || np[c] != tp[c]) w->rec.insert(w->rec.end(), {(int64_t)c, ns[c], np[c]});
+    }
+    const int rc = rd_chan_retune(w->chan, w->rec.data(), (int)(w->rec.size() / 3), slot, w->st);
+    if (rc) return rc;           // (nothing queued, nothing recorded: the next submit tries again)
+    for (int c = 0; c < w->n_ch; c++) { w->shift[c] = ns[c]; w->phase[c] = np[c]; }
+    w->pending = w->restored = false;
+    return RD_OK;
+}
 
 extern "C" int rd_wideband_create(const rd_config *cfg, const rd_chan_config *ccfg, const double *taps,
                                   const int64_t *shift_hz, rd_wideband **out) {
@@ -72,6 +118,9 @@ extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg
     w->n_ch = ccfg->n_channels;
     w->B = (size_t)cfg->block_size;
     w->chunk_bytes = (size_t)rd_chan_bytes_per_sample(ch) * (size_t)ccfg->decim * w->B;
+    w->plan.assign(shift_hz, shift_hz + w->n_ch);
+    w->shift = w->want = w->plan;
+    w->phase.assign(w->n_ch, 0);
     *out = w;
     return RD_OK;
 }
@@ -116,6 +165,29 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->clock = 0;
     w->n_sub = 0;                // (no previous chunk: zero history)
     w->last = -1;
+    w->shift = w->plan;          // a pending retune is dropped; the next submit rebuilds what the tables hold otherwise
+    w->phase.assign(w->n_ch, 0);
+    w->pending = false;
+    w->restored = true;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_retune(rd_wideband *w, const int64_t *shift_hz, int n) {
+    if (!w || !shift_hz) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d shifts for %d channels", n, w->n_ch);
+    const int64_t half = rd_chan_wide_rate(w->chan) / 2;
+    for (int c = 0; c < n; c++)
+        if (shift_hz[c] > half || shift_hz[c] < -half)
+            return rd_fail_msg(RD_ERR_ARG, "channel %d: a shift of %lld Hz lies outside the captured band", c, (long long)shift_hz[c]);
+    w->want.assign(shift_hz, shift_hz + n);
+    w->pending = true;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_tuning(rd_wideband *w, int64_t *shift_hz, int64_t *phase, int n) {
+    if (!w || !shift_hz || !phase) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d channels of %d", n, w->n_ch);
+    for (int c = 0; c < n; c++) wb_next_tuning(w, c, &shift_hz[c], &phase[c]);
     return RD_OK;
 }
 
@@ -123,7 +195,9 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (!w || !wide_iq) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (nbytes != w->chunk_bytes)
         return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: got %zu bytes, expected %zu", nbytes, w->chunk_bytes);
-    int rc = wb_alloc(w);
+    int rc = RD_OK;
+    if (!w->dev_ready && (rc = wb_apply_tuning(w, 0))) return rc;   // (the tables are still the host's)
+    rc = wb_alloc(w);
     if (rc) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
@@ -135,6 +209,11 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (w->n_sub >= 1) WCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s ^ 1], 0));
     WCHK(hipMemcpyAsync(w->d_wide[s], w->h_in[s], nbytes, hipMemcpyHostToDevice, w->st_copy));
     WCHK(hipEventRecord(w->e_in[s], w->st_copy));
+    // Pinned record slot s was last used by chunk k-2, whose records were copied on the COMPUTE stream: e_in[s] above (the
+    // copy stream's event) does not order that copy.  The slot is free because rd_demod_check_room refuses a third chunk:
+    // chunk k-2 has been fetched, or waited for as stale, so all its work on the compute stream is done.  Whoever relaxes
+    // that limit must give the slot an event of its own.
+    if ((rc = wb_apply_tuning(w, s))) return rc;
     WCHK(hipStreamWaitEvent(w->st, w->e_in[s], 0));
     rc = rd_chan_stream_launch(w->chan, w->d_wide[s], w->n_sub >= 1 ? w->d_wide[s ^ 1] : nullptr, w->B, w->clock,
                                w->d_out[s], 2 * w->B, w->st);

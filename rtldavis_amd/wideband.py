@@ -42,6 +42,7 @@ class WidebandReceiver:
         if int(cfg.block_size) % 128 or int(cfg.block_size) < 128:
             raise ValueError(f"block_size {cfg.block_size} is not a positive multiple of 128")
         plan_channels(self, channels_hz, centre_hz, decim, taps, gain, int(cfg.bit_rate) * int(cfg.symbol_length))
+        self._plan_shift_hz = self.shift_hz.copy()                  # the constructed plan: retune() offsets, reset()
         self.block_size = int(cfg.block_size)
         self.chunk_samples = self.decim * self.block_size           # IQ pairs per chunk
         self.chunk_bytes = 2 * np.dtype(self.dtype).itemsize * self.chunk_samples
@@ -108,9 +109,37 @@ class WidebandReceiver:
         from .dsp import _parsed_array
         return _parsed_array(_lib.lib().rd_wb_parsed, self._h)
 
+    def retune(self, offset_hz) -> None:
+        """From the next submitted chunk on, receive channel c as if its centre were ``channels_hz[c] + offset_hz[c]`` -
+        the reference's ``channel_freq + freq_corr`` (runners/rtlsdr.py:51,72), so the ``freq_err`` values of ``parsed()``,
+        averaged the caller's way (protocol.py:258-271), go in as they are.  ``offset_hz``: one integer for all channels or
+        one per channel, relative to the constructed plan (not cumulative).  Phase-continuous at the chunk boundary, legal
+        with chunks in flight, nothing else disturbed (filter history, clock, demodulators); only the tables of the
+        channels that change are rebuilt, by a kernel in front of that chunk's channelizer.  ValueError for a wrong
+        length or a channel pushed outside the captured band."""
+        off = np.asarray(offset_hz)
+        if off.dtype.kind not in "iu" or off.ndim > 1 or (off.ndim == 1 and off.size != self.n_channels):
+            raise ValueError(f"offset_hz: one integer or {self.n_channels} of them")
+        shift = np.ascontiguousarray(self._plan_shift_hz + off.astype(np.int64), np.int64)
+        if shift.size and np.abs(shift).max() > self.wide_rate // 2:
+            raise ValueError("a channel lies outside the captured band")
+        _lib.check(_lib.lib().rd_wb_retune(self._h, shift.ctypes.data, shift.size))
+        self.shift_hz = shift
+
+    def tuning(self):
+        """``(shift_hz, phase)``, int64 per channel: the mixer frequencies the next submitted chunk will use and the
+        integer phase accumulators P_c that keep the phase continuous across retunes - the output phase of channel c at
+        the absolute output time t is ``frac((shift_hz[c] * t + phase[c]) / out_rate)``."""
+        shift = np.empty(self.n_channels, np.int64)
+        phase = np.empty(self.n_channels, np.int64)
+        _lib.check(_lib.lib().rd_wb_tuning(self._h, shift.ctypes.data, phase.ctypes.data, shift.size))
+        return shift, phase
+
     def reset(self) -> None:
-        """Back to the state after construction: clock at 0, zero history, demodulators reset."""
+        """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel
+        plan (a pending or earlier ``retune`` is dropped)."""
         _lib.check(_lib.lib().rd_wideband_reset(self._h))
+        self.shift_hz = self._plan_shift_hz.copy()
 
     def channelized(self) -> np.ndarray:
         """uint8 [n_channels, 2*block_size]: the channelized chunk the last fetch returned (until the next submit)."""

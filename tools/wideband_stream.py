@@ -9,11 +9,15 @@ around work that ends in a fetch:
   - how many injected packets came back on the first pass over the capture.
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
 
-    python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse] [--json OUT]
+    python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
+                                    [--retune {none,one,all}] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
 the CRC gate on the host, discriminated(channel) per CRC-valid packet.
+--retune one | all: WidebandReceiver.retune before every submit - channel 25, or all 51 channels, alternately 1 Hz up and
+back on the plan - so every chunk carries the rebuild of those channels' tables (k_chan_retune) in front of its
+channelizer; 1 Hz keeps every burst where it was.
 """
 import argparse
 import json
@@ -37,6 +41,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--sample-format", default="u8", choices=["u8", "s8", "s16"], help="the capture's sample format")
     ap.add_argument("--parse", action="store_true", help="device parse on, parsed() read per chunk; also time the route without it")
+    ap.add_argument("--retune", default="none", choices=["none", "one", "all"],
+                    help="retune one channel or all of them before every chunk")
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -51,6 +57,8 @@ def main():
     n_msgs = [0]
     step = 2 * rx.chunk_samples      # array elements per chunk
     chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
+    moved = np.zeros(rx.n_channels, np.int64)
+    moved[[25] if args.retune == "one" else slice(None)] = 1
 
     def run(n):
         """n chunks round and round through submit / fetch, two in flight; per-chunk latency and packets."""
@@ -64,6 +72,8 @@ def main():
                     n_msgs[0] += len(rx.parsed())
                 lat.append(time.perf_counter() - t_sub[len(pk) - 1])
             t_sub.append(time.perf_counter())
+            if args.retune != "none":
+                rx.retune(moved * ((k + 1) & 1))
             rx.submit(chunks[k % nk])
         while rx.inflight:
             pk.append(rx.fetch())
@@ -98,7 +108,7 @@ def main():
         "realtime_factor": air / wall,
         "injected_packets": len(info), "recovered_first_pass": int(found),
         "packets_total": int(sum(len(x) for ch in pk for x in ch)),
-        "parse": bool(args.parse),
+        "parse": bool(args.parse), "retune": args.retune,
     }
     if args.parse:
         import math
