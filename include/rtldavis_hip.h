@@ -338,6 +338,11 @@ int rd_chan_input_ptr(rd_chan *h, size_t n_wide_samples, void **dev_ptr);
 int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_stream_stride, void *hip_stream);
 /* Same, into a host array uint8 [n_channels][n_out][2] (synchronous). */
 int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, size_t nbytes);
+/* Per-channel gain: gain[c] replaces cfg.gain for channel c (n = n_channels, every gain finite and > 0 - in float32
+ * too, which is what the kernel multiplies with - else RD_ERR_ARG and nothing changes) in the runs that follow.  With every
+ * entry equal to cfg.gain the output is the scalar form's, byte for byte.  Needs a quiet handle: the caller has waited
+ * for the streams its earlier rd_chan_run calls were queued on. */
+int rd_chan_set_gain(rd_chan *h, const double *gain, int n);
 
 /* ---------------------------------------------------------------------------------------------
  * Wideband receiver (rtldavis_amd/csrc/rd_wideband.hip): one capture that never ends, fed in
@@ -390,6 +395,45 @@ int rd_wb_parsed(rd_wideband *w, rd_parsed *out, int cap, int *n);
  * rd_wb_tuning: the tuning the next submitted chunk will use, shifts as given and P_c (host only, no device needed). */
 int rd_wb_retune(rd_wideband *w, const int64_t *shift_hz, int n);
 int rd_wb_tuning(rd_wideband *w, int64_t *shift_hz, int64_t *phase, int n);
+/* Gain (the mechanism of an AGC; the policy is the caller's, e.g. rtldavis_amd/agc.py): channel c is re-quantised with
+ * gain[c] - absolute values that replace cfg.gain, stored as float32 - from the next submitted chunk on, exactly at
+ * that chunk boundary.  n = n_channels and every gain finite and > 0 (in float32 too), else RD_ERR_ARG and nothing
+ * changes.  Host bookkeeping only, like rd_wb_retune: no device work, no wait, legal with two chunks in flight; the next
+ * rd_wideband_submit queues the table (one copy through the pinned slot of the chunk's parity, only if an entry differs)
+ * in front of its channelizer.  Nothing else is touched: filter history, clock, phase accumulators, demodulator state.
+ * With every gain equal to cfg.gain the bytes are those of a receiver that never called it.
+ * rd_wb_gains: the gains the next submitted chunk will use (the float32 values; host only, no device needed).
+ * rd_wideband_reset drops a pending change and returns to cfg.gain. */
+int rd_wb_set_gain(rd_wideband *w, const double *gain, int n);
+int rd_wb_gains(rd_wideband *w, double *gain, int n);
+/* Level metering (k_chan_levels, rd_channelizer.hip): with levels on, every chunk carries one more launch behind its
+ * channelizer.  All quantities are exact integers.
+ *   per channel, over the 2 * block_size bytes b of its channelized chunk, a = 2 b - 255:
+ *     peak = max |a|, clipped = bytes equal to 0 or 255, power = sum a^2, gain = the float32 gain in force for the chunk
+ *     (RMS as a fraction of full scale: sqrt(power / (2 * block_size)) / 255)
+ *   for the input chunk, over its 2 * decim * block_size components k, a = 2 k - 255 (RD_IQ_U8) or a = k (RD_IQ_S8, _S16):
+ *     peak = max |a|, clipped = components at either end of the format's range, power = sum a^2
+ *     (no admissible chunk overflows a field: < 2^32 components, a^2 <= 2^30)
+ *   chunk = the chunk's sequence number since create / reset (rd_packet.call of its packets); rd_chan_level carries its low 32 bits.
+ * rd_wb_set_levels needs a quiet receiver (RD_ERR_STATE otherwise), like rd_wb_set_parse; off (the default): nothing is
+ * launched.  rd_wb_levels: the records of the chunk the last fetch returned (n = n_channels; `in` may be NULL), kept by
+ * that fetch - valid with later chunks in flight, until the next fetch.  RD_ERR_STATE before any fetch and when that chunk
+ * was submitted with levels off. */
+typedef struct rd_chan_level {
+    uint64_t power;
+    uint32_t peak;
+    uint32_t clipped;
+    float gain;
+    uint32_t chunk;
+} rd_chan_level;
+typedef struct rd_input_level {
+    uint64_t power;
+    uint64_t chunk;
+    uint32_t peak;
+    uint32_t clipped;
+} rd_input_level;
+int rd_wb_set_levels(rd_wideband *w, int enabled);
+int rd_wb_levels(rd_wideband *w, rd_chan_level *out, int n, rd_input_level *in);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

@@ -49,6 +49,15 @@ class RdChanConfig(C.Structure):
                 ("gain", C.c_double)]
 
 
+class RdChanLevel(C.Structure):
+    _fields_ = [("power", C.c_uint64), ("peak", C.c_uint32), ("clipped", C.c_uint32), ("gain", C.c_float),
+                ("chunk", C.c_uint32)]
+
+
+class RdInputLevel(C.Structure):
+    _fields_ = [("power", C.c_uint64), ("chunk", C.c_uint64), ("peak", C.c_uint32), ("clipped", C.c_uint32)]
+
+
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
 RD_IQ_U8, RD_IQ_S8, RD_IQ_S16 = 0, 1, 2
 SAMPLE_FORMATS = {"u8": (RD_IQ_U8, np.uint8), "s8": (RD_IQ_S8, np.int8), "s16": (RD_IQ_S16, np.int16)}
@@ -134,6 +143,7 @@ SIGNATURES = {
     "rd_chan_input_ptr": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "rd_chan_run": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "rd_chan_run_host": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
+    "rd_chan_set_gain": (C.c_int, [_P, _P, C.c_int]),
     "rd_wideband_create": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), _P, _P, C.POINTER(_P)]),
     "rd_wb_create_fmt": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), C.c_int, _P, _P, C.POINTER(_P)]),
     "rd_wideband_destroy": (None, [_P]),
@@ -148,6 +158,10 @@ SIGNATURES = {
     "rd_wb_parsed": (C.c_int, [_P, C.POINTER(RdParsed), C.c_int, C.POINTER(C.c_int)]),
     "rd_wb_retune": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_tuning": (C.c_int, [_P, _P, _P, C.c_int]),
+    "rd_wb_set_gain": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_gains": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_set_levels": (C.c_int, [_P, C.c_int]),
+    "rd_wb_levels": (C.c_int, [_P, _P, C.c_int, C.POINTER(RdInputLevel)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),
@@ -192,6 +206,21 @@ def check(rc: int) -> None:
     if rc == RD_ERR_STATE:
         raise RuntimeError(msg)
     raise HipError(msg)
+
+
+def gain_array(gain, n_channels):
+    """``gain`` - one positive finite number for all channels or one per channel - as float64 [n_channels];
+    ValueError otherwise (the library checks again, float32 range included)."""
+    try:
+        g = np.asarray(gain, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"gain: one positive number or {n_channels} of them") from None
+    if g.ndim > 1 or (g.ndim == 1 and g.size != n_channels):
+        raise ValueError(f"gain: one positive number or {n_channels} of them")
+    g = np.ascontiguousarray(np.broadcast_to(g, (n_channels,)), np.float64)
+    if not (np.all(np.isfinite(g)) and np.all(g > 0)):
+        raise ValueError("every gain must be finite and > 0")
+    return g
 
 
 def make_config(bit_rate, symbol_length, preamble_symbols, packet_symbols, preamble, block_size) -> RdConfig:

@@ -88,6 +88,14 @@ class Channelizer:
         except Exception:
             pass
 
+    def set_gain(self, gain) -> None:
+        """Re-quantise channel c with ``gain[c]`` in the runs that follow: one positive number for all channels or one
+        per channel, absolute values that replace the constructed ``gain`` (stored as float32).  With every entry equal
+        to the constructed gain the bytes do not change.  ValueError for a wrong length or a gain that is not finite and
+        > 0.  Call it between runs whose results have been taken (``run_host``, or a synchronised ``run_into``)."""
+        g = _lib.gain_array(gain, self.n_channels)
+        _lib.check(_lib.lib().rd_chan_set_gain(self._h, g.ctypes.data, g.size))
+
     def upload(self, wide_iq: np.ndarray) -> None:
         """Copy a capture (``self.dtype``, I,Q interleaved: flat or [n, 2]) to the device."""
         a = _lib.iq_array(wide_iq, self.dtype)

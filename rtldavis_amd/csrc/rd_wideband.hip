@@ -21,6 +21,14 @@
 // (the previous chunk's is earlier on the same stream, so one set of tables serves).  The records travel through a
 // pinned slot of the chunk's parity: chunk k-2, the slot's last user, has been fetched or dropped - all its work is done.
 // Before the first submit the tables are still the host's, and are rebuilt there.
+//
+// Gain (rd_wb_set_gain; rd_channelizer.hip, GAIN): the same pattern for the per-channel gains - the call records what is
+// wanted, the next submit stages the table in the pinned slot of its parity and queues one copy in front of its
+// k_channelize, only when an entry differs from what the table holds.
+// Levels (rd_wb_set_levels / rd_wb_levels; rd_channelizer.hip, LEVELS): with levels on, k_chan_levels is queued behind the
+// chunk's k_channelize (behind e_chan: the copy stream never waits for it) and writes its records into the mapped pinned
+// slot of the chunk's parity.  The chunk's demodulator launch comes after it on the compute stream, so when a fetch has
+// seen that launch report, the records are complete; the fetch copies them out of the slot, which chunk k+2 reuses.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -61,6 +69,17 @@ struct rd_wideband {
     bool pending = false;                          // a retune waits for the next submit
     bool restored = false;                         // reset() since the last submit: the tables may hold an earlier retune
     std::vector<int64_t> rec, next_shift, next_phase;   // scratch: a submit's retune records and its tuning
+    // gain: the constructed one (reset() returns to it) and what the next submitted chunk will use, as float32
+    float gain0 = 0.0f;
+    std::vector<float> gain;
+    // levels: on / off (switched on a quiet receiver: every chunk in flight has the same), the mapped pinned slots
+    // [n_channels] rd_chan_level + one rd_input_level per parity, the kernel's device words, and the records the last
+    // fetch kept
+    bool levels = false, last_levels = false;
+    rd_chan_level *h_lv[2] = {nullptr, nullptr};
+    uint32_t *d_lvacc = nullptr;
+    std::vector<rd_chan_level> lv_last;
+    rd_input_level lv_in_last = {};
 };
 
 // the tuning the next submitted chunk will use, channel c: the pending shift takes over at t_b = clock
@@ -121,6 +140,8 @@ extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg
     w->plan.assign(shift_hz, shift_hz + w->n_ch);
     w->shift = w->want = w->plan;
     w->phase.assign(w->n_ch, 0);
+    w->gain0 = (float)ccfg->gain;
+    w->gain.assign(w->n_ch, w->gain0);
     *out = w;
     return RD_OK;
 }
@@ -133,7 +154,9 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_in[i]); hipFree(w->d_wide[i]); hipFree(w->d_out[i]);
             if (w->e_in[i]) hipEventDestroy(w->e_in[i]);
             if (w->e_chan[i]) hipEventDestroy(w->e_chan[i]);
+            hipHostFree(w->h_lv[i]);
         }
+        hipFree(w->d_lvacc);
     }
     rd_chan_destroy(w->chan);
     delete w;
@@ -158,6 +181,23 @@ static int wb_alloc(rd_wideband *w) {
     return RD_OK;
 }
 
+// the level records' slots and the kernel's words, when levels are first wanted
+static size_t wb_lv_bytes(const rd_wideband *w) { return (size_t)w->n_ch * sizeof(rd_chan_level) + sizeof(rd_input_level); }
+static int wb_alloc_levels(rd_wideband *w) {
+    if (w->d_lvacc) return RD_OK;
+    for (int i = 0; i < 2; i++)
+        if (!w->h_lv[i]) {
+            WCHK(hipHostMalloc((void **)&w->h_lv[i], wb_lv_bytes(w), hipHostMallocMapped));
+            memset(w->h_lv[i], 0xFF, wb_lv_bytes(w));   // (no chunk has the sequence number 2^64 - 1)
+        }
+    uint32_t *acc = nullptr;
+    WCHK(hipMalloc(&acc, RD_LV_ACC_WORDS * sizeof(uint32_t)));
+    hipError_t e = hipMemsetAsync(acc, 0, RD_LV_ACC_WORDS * sizeof(uint32_t), w->st);   // (ordered before the first launch)
+    if (e != hipSuccess) { hipFree(acc); return rd_fail_msg(RD_ERR_DEVICE, "hipMemsetAsync: %s", hipGetErrorString(e)); }
+    w->d_lvacc = acc;
+    return RD_OK;
+}
+
 extern "C" int rd_wideband_reset(rd_wideband *w) {
     if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
     int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
@@ -169,6 +209,43 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->phase.assign(w->n_ch, 0);
     w->pending = false;
     w->restored = true;
+    w->gain.assign(w->n_ch, w->gain0);   // a pending gain change is dropped; the next submit rewrites the table if it differs
+    w->last_levels = false;
+    for (int i = 0; i < 2; i++)   // (chunk numbers restart: no record of the run before may pass for one of this run)
+        if (w->h_lv[i]) memset(w->h_lv[i], 0xFF, wb_lv_bytes(w));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_gain(rd_wideband *w, const double *gain, int n) {
+    if (!w || !gain) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    int rc = rd_chan_check_gains(w->chan, gain, n);
+    if (rc) return rc;
+    for (int c = 0; c < n; c++) w->gain[c] = (float)gain[c];
+    return RD_OK;
+}
+
+extern "C" int rd_wb_gains(rd_wideband *w, double *gain, int n) {
+    if (!w || !gain) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d channels of %d", n, w->n_ch);
+    for (int c = 0; c < n; c++) gain[c] = (double)w->gain[c];
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_levels(rd_wideband *w, int enabled) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before levels are switched", rd_demod_inflight(w->dem));
+    w->levels = enabled != 0;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_levels(rd_wideband *w, rd_chan_level *out, int n, rd_input_level *in) {
+    if (!w || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d channels of %d", n, w->n_ch);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_levels) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with levels off (rd_wb_set_levels)");
+    memcpy(out, w->lv_last.data(), (size_t)n * sizeof(rd_chan_level));
+    if (in) *in = w->lv_in_last;
     return RD_OK;
 }
 
@@ -199,6 +276,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (!w->dev_ready && (rc = wb_apply_tuning(w, 0))) return rc;   // (the tables are still the host's)
     rc = wb_alloc(w);
     if (rc) return rc;
+    if (w->levels && (rc = wb_alloc_levels(w))) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
     const int s = (int)(w->n_sub & 1);
@@ -214,18 +292,42 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     // chunk k-2 has been fetched, or waited for as stale, so all its work on the compute stream is done.  Whoever relaxes
     // that limit must give the slot an event of its own.
     if ((rc = wb_apply_tuning(w, s))) return rc;
+    if ((rc = rd_chan_stream_gains(w->chan, w->gain.data(), s, w->st))) return rc;   // (its own slot s, free by the same argument)
     WCHK(hipStreamWaitEvent(w->st, w->e_in[s], 0));
     rc = rd_chan_stream_launch(w->chan, w->d_wide[s], w->n_sub >= 1 ? w->d_wide[s ^ 1] : nullptr, w->B, w->clock,
                                w->d_out[s], 2 * w->B, w->st);
     if (rc) return rc;
     WCHK(hipEventRecord(w->e_chan[s], w->st));
+    if (w->levels) {
+        // level slot s was last written for chunk k-2 and read by its fetch (or the chunk was dropped): free, as above
+        rd_chan_level *lv = nullptr;
+        WCHK(hipHostGetDevicePointer((void **)&lv, w->h_lv[s], 0));
+        rc = rd_chan_stream_levels(w->chan, w->d_wide[s], w->B, w->d_out[s], 2 * w->B, (uint64_t)w->n_sub, lv,
+                                   (rd_input_level *)(lv + w->n_ch), w->d_lvacc, w->st);
+        if (rc) return rc;
+    }
     w->clock += w->B;
     w->n_sub++;
     return rd_demod_submit_device(w->dem, w->d_out[s]);
 }
 
 static int wb_fetched(rd_wideband *w, int rc) {
-    if (rc == RD_OK || rc == RD_ERR_CAPACITY) w->last = w->n_sub - 1 - rd_demod_pending(w->dem);  // (the oldest in flight)
+    if (rc != RD_OK && rc != RD_ERR_CAPACITY) return rc;
+    w->last = w->n_sub - 1 - rd_demod_pending(w->dem);  // (the oldest in flight)
+    w->last_levels = false;
+    if (!w->levels) return rc;
+    // The chunk's demodulator launch has reported, and k_chan_levels ran before it on the same stream: keep its records
+    // (the slot is chunk last + 2's from its submit on).  Every record carries the chunk's number - a record of another
+    // chunk here would be an ordering bug, not something to hand on.
+    const rd_chan_level *lv = w->h_lv[w->last & 1];
+    w->lv_last.assign(lv, lv + w->n_ch);
+    memcpy(&w->lv_in_last, lv + w->n_ch, sizeof(rd_input_level));
+    for (int c = 0; c < w->n_ch; c++)
+        if (w->lv_last[c].chunk != (uint32_t)w->last)
+            return rd_fail_msg(RD_ERR_DEVICE, "level record of channel %d belongs to chunk %u, not %ld", c, w->lv_last[c].chunk, w->last);
+    if (w->lv_in_last.chunk != (uint64_t)w->last)
+        return rd_fail_msg(RD_ERR_DEVICE, "the input level record belongs to chunk %llu, not %ld", (unsigned long long)w->lv_in_last.chunk, w->last);
+    w->last_levels = true;
     return rc;
 }
 

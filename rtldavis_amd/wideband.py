@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -22,6 +22,26 @@ from .channelizer import DEFAULT_CENTRE_HZ, DEFAULT_DECIM, US_CHANNELS_HZ, chan_
 from .dsp import Packet, _cfg_struct, _packets_per_stream
 
 logger = logging.getLogger(__name__)
+
+# levels(): one row per channel
+LEVEL_DTYPE = np.dtype([("gain", np.float32), ("peak", np.uint32), ("clipped", np.uint32), ("power", np.uint64)])
+
+
+class InputLevel(NamedTuple):
+    """The capture chunk's own levels (``Levels.input``): over its ``2 * chunk_samples`` components k, with a = 2 k - 255
+    for "u8" and a = k for "s8" / "s16": ``peak`` = max |a|, ``clipped`` = components at either end of the format's
+    range, ``power`` = sum a^2."""
+    peak: int
+    clipped: int
+    power: int
+
+
+class Levels(NamedTuple):
+    """``WidebandReceiver.levels()``: ``channels`` (structured array of ``LEVEL_DTYPE``, one row per channel), ``input``
+    (``InputLevel``) and ``chunk``, the chunk's number since construction / ``reset()`` (its packets' ``call``)."""
+    channels: np.ndarray
+    input: InputLevel
+    chunk: int
 
 
 class WidebandReceiver:
@@ -135,9 +155,48 @@ class WidebandReceiver:
         _lib.check(_lib.lib().rd_wb_tuning(self._h, shift.ctypes.data, phase.ctypes.data, shift.size))
         return shift, phase
 
+    def set_gain(self, gain) -> None:
+        """From the next submitted chunk on, re-quantise channel c with ``gain[c]``: one positive number for all channels
+        or one per channel - absolute values (not relative to the constructed ``gain``), stored as float32.  The change
+        takes effect exactly at that chunk boundary, is legal with chunks in flight and disturbs nothing else (filter
+        history, clock, tuning, demodulators); with every entry equal to the constructed gain the bytes are those of a
+        receiver that never called it.  ValueError for a wrong length or a gain that is not finite and > 0.
+        ``Packet.rssi`` is measured on the channel's bytes: referred to the input it is ``rssi - 20 log10(gain)``."""
+        g = _lib.gain_array(gain, self.n_channels)
+        _lib.check(_lib.lib().rd_wb_set_gain(self._h, g.ctypes.data, g.size))
+
+    def gains(self) -> np.ndarray:
+        """float64 per channel: the gains the next submitted chunk will use (exactly the float32 values in the table)."""
+        g = np.empty(self.n_channels, np.float64)
+        _lib.check(_lib.lib().rd_wb_gains(self._h, g.ctypes.data, g.size))
+        return g
+
+    def set_levels(self, on: bool = True) -> None:
+        """From the next chunk on, meter every chunk on the device (one more kernel behind its channelizer); ``levels()``
+        returns the records.  Needs a receiver with nothing in flight.  Off (the default): nothing is launched."""
+        _lib.check(_lib.lib().rd_wb_set_levels(self._h, 1 if on else 0))
+
+    def levels(self) -> "Levels":
+        """Levels of the chunk the last ``fetch()`` returned - later chunks may be in flight - as exact integers:
+        per channel, over the ``2 * block_size`` bytes b of its channelized chunk with a = 2 b - 255, ``peak`` = max |a|,
+        ``clipped`` = bytes equal to 0 or 255, ``power`` = sum a^2, and ``gain``, the float32 in force for that chunk;
+        the capture chunk's own record (``InputLevel``: how hard the ADC is driven); and the chunk's number.
+        Conversions: a channel's RMS as a fraction of full scale is ``sqrt(power / (2 * block_size)) / 255``; the input's
+        likewise with its component count and 255 ("u8"), 128 ("s8") or 32768 ("s16").  ``agc.GainControl.update`` takes
+        the result as it is.  RuntimeError before any fetch and when levels were off for that chunk."""
+        recs = (_lib.RdChanLevel * self.n_channels)()
+        inp = _lib.RdInputLevel()
+        _lib.check(_lib.lib().rd_wb_levels(self._h, recs, self.n_channels, C.byref(inp)))
+        raw = np.frombuffer(recs, dtype=np.dtype([("power", np.uint64), ("peak", np.uint32), ("clipped", np.uint32),
+                                                  ("gain", np.float32), ("chunk", np.uint32)]))
+        out = np.empty(self.n_channels, LEVEL_DTYPE)
+        for f in LEVEL_DTYPE.names:
+            out[f] = raw[f]
+        return Levels(out, InputLevel(int(inp.peak), int(inp.clipped), int(inp.power)), int(inp.chunk))
+
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel
-        plan (a pending or earlier ``retune`` is dropped)."""
+        plan (a pending or earlier ``retune`` is dropped) and the constructed gain (``set_gain`` likewise)."""
         _lib.check(_lib.lib().rd_wideband_reset(self._h))
         self.shift_hz = self._plan_shift_hz.copy()
 

@@ -10,7 +10,7 @@ around work that ends in a fetch:
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
 
     python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
-                                    [--retune {none,one,all}] [--json OUT]
+                                    [--retune {none,one,all}] [--levels] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -18,6 +18,8 @@ the CRC gate on the host, discriminated(channel) per CRC-valid packet.
 --retune one | all: WidebandReceiver.retune before every submit - channel 25, or all 51 channels, alternately 1 Hz up and
 back on the plan - so every chunk carries the rebuild of those channels' tables (k_chan_retune) in front of its
 channelizer; 1 Hz keeps every burst where it was.
+--levels: level metering on (WidebandReceiver.set_levels: k_chan_levels behind every chunk's channelizer), levels() read
+after every fetch and handed to agc.GainControl.update, whose gains go into set_gain when a channel moves.
 """
 import argparse
 import json
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--parse", action="store_true", help="device parse on, parsed() read per chunk; also time the route without it")
     ap.add_argument("--retune", default="none", choices=["none", "one", "all"],
                     help="retune one channel or all of them before every chunk")
+    ap.add_argument("--levels", action="store_true", help="metering on; levels() -> GainControl.update -> set_gain per chunk")
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -54,11 +57,22 @@ def main():
                                      sample_format=args.sample_format)
     rx = wideband.WidebandReceiver(cfg, sample_format=args.sample_format)
     rx.set_parse(args.parse)
+    ctl = None
+    if args.levels:
+        from rtldavis_amd import agc
+        rx.set_levels(True)
+        ctl = agc.GainControl(rx.n_channels, B)
     n_msgs = [0]
     step = 2 * rx.chunk_samples      # array elements per chunk
     chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
     moved = np.zeros(rx.n_channels, np.int64)
     moved[[25] if args.retune == "one" else slice(None)] = 1
+
+    def meter():
+        if ctl is not None:
+            g = ctl.update(rx.levels())
+            if g is not None:
+                rx.set_gain(g)
 
     def run(n):
         """n chunks round and round through submit / fetch, two in flight; per-chunk latency and packets."""
@@ -70,6 +84,7 @@ def main():
                 pk.append(rx.fetch())
                 if args.parse:
                     n_msgs[0] += len(rx.parsed())
+                meter()
                 lat.append(time.perf_counter() - t_sub[len(pk) - 1])
             t_sub.append(time.perf_counter())
             if args.retune != "none":
@@ -79,6 +94,7 @@ def main():
             pk.append(rx.fetch())
             if args.parse:
                 n_msgs[0] += len(rx.parsed())
+            meter()
             lat.append(time.perf_counter() - t_sub[len(pk) - 1])
         return time.perf_counter() - t0, np.array(lat), pk
 
@@ -108,7 +124,7 @@ def main():
         "realtime_factor": air / wall,
         "injected_packets": len(info), "recovered_first_pass": int(found),
         "packets_total": int(sum(len(x) for ch in pk for x in ch)),
-        "parse": bool(args.parse), "retune": args.retune,
+        "parse": bool(args.parse), "retune": args.retune, "levels": bool(args.levels),
     }
     if args.parse:
         import math
