@@ -280,7 +280,7 @@ int rd_quantize(const double *in, uint8_t *out, size_t n);
 int rd_search(const rd_config *cfg, const uint8_t *quantized, size_t n, int32_t *indices, int cap, int *count);
 
 /* ---------------------------------------------------------------------------------------------
- * Wideband front end: one IQ capture (uint8, int8 or int16) at decim * out_rate samples/s ->
+ * Wideband front end: one IQ capture (uint8, int8, int16 or float32) at decim * out_rate samples/s ->
  * one out_rate uint8 IQ stream per channel, e.g. the 51 US hop channels (protocol.py:119-171) out
  * of one 26.88 MS/s capture, written straight into a batch demodulator's input buffer.
  * The reference has no channelizer (it retunes one dongle per hop, runners/rtlsdr.py:51,72):
@@ -307,11 +307,18 @@ typedef struct rd_chan rd_chan;
  *   RD_IQ_U8   uint8 I, Q                    x = (I - 127.4) / 127.6 + j (Q - 127.4) / 127.6   (RTL-SDR; dsp.py:20-39)
  *   RD_IQ_S8   int8 I, Q                     x = I / 128 + j Q / 128                           (sc8 / CS8)
  *   RD_IQ_S16  int16 I, Q, host byte order   x = I / 32768 + j Q / 32768                       (sc16 / CS16)
- * Everything behind x - filter, mixer, gain, output quantiser, the contract above - is the same; the bound of a
- * format is tests/chan_bound_fmt.py:error_bound_fmt. */
+ *   RD_IQ_CF32 float32 I, Q, host byte order x = adm(I) + j adm(Q)                             (CF32 / fc32 / numpy complex64)
+ *              8 bytes per IQ pair, nominal full scale +-1.0; adm(v) = 0 if v is NaN, else v clamped to [-8, +8] (+-Inf
+ *              is +-8: 18 dB of headroom, and one NaN does not poison every window it falls into).  No DC term; samples
+ *              outside the capture are exactly 0.  The kernel splits 2^12 adm(v) into two f16 digits hi = f16(s),
+ *              lo = f16(s - hi), exact to max(2^-22 |x|, 2^-37).
+ * Everything behind x - filter, mixer, phase accumulator, per-channel gain, output quantiser, the contract above - is
+ * the same; the bound of a format is tests/chan_bound_fmt.py:error_bound_fmt, of RD_IQ_CF32
+ * tests/chan_bound_cf32.py:error_bound_cf32.  Code 3 stays unassigned and the name "f32" unknown: both are errors. */
 #define RD_IQ_U8 0
 #define RD_IQ_S8 1
 #define RD_IQ_S16 2
+#define RD_IQ_CF32 4
 
 /* taps: n_taps doubles; shift_hz[c]: the wideband frequency (Hz, relative to the capture's centre)
  * that channel c moves to 0 Hz of its output - for rtldavis the channel centre plus out_rate / 4,
@@ -322,7 +329,8 @@ int rd_chan_create(const rd_chan_config *cfg, const double *taps, const int64_t 
  * in 4 .. 4096, 1 .. 8192 taps, 1 .. 4096 channels, out_rate < 2^26; with t_pad = n_taps rounded up to 8:
  *   RD_IQ_U8, RD_IQ_S8  2 (127 decim + t_pad + 8) + 16 <= 160 KiB of LDS, and ceil((t_pad - 1) / decim) <= 64
  *   RD_IQ_S16           8 (127 decim + t_pad + 4) + 16 <= 160 KiB of LDS (a sample is staged as four 16-bit lanes)
- *                       and no limit on n_taps / decim (there is no DC term to tabulate). */
+ *                       and no limit on n_taps / decim (there is no DC term to tabulate).
+ *   RD_IQ_CF32          as RD_IQ_S16 (the same four lanes per staged sample): decim <= 160 at 8 taps. */
 int rd_chan_create_fmt(const rd_chan_config *cfg, int sample_format, const double *taps, const int64_t *shift_hz,
                        rd_chan **out);
 void rd_chan_destroy(rd_chan *h);
@@ -363,8 +371,8 @@ int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg, int sampl
 void rd_wideband_destroy(rd_wideband *w);
 /* clock to 0, history to zero, demod state as rd_reset (waits for the chunks in flight) */
 int rd_wideband_reset(rd_wideband *w);
-/* one chunk: I,Q of decim * block_size wideband samples in the handle's format, i.e. (2 or, for RD_IQ_S16, 4)
- * * decim * block_size bytes (else RD_ERR_ARG "Incompatible array sizes"); host->device copy, channelize (streaming form), one demod launch - all queued on the
+/* one chunk: I,Q of decim * block_size wideband samples in the handle's format, i.e. (2 or, for RD_IQ_S16, 4, for
+ * RD_IQ_CF32, 8) * decim * block_size bytes (else RD_ERR_ARG "Incompatible array sizes"); host->device copy, channelize (streaming form), one demod launch - all queued on the
  * handle's own non-blocking streams, returns at once.  At most two chunks in flight (a third:
  * RD_ERR_STATE); the copy of chunk k+1 overlaps chunk k's kernels.  The clock and the history
  * advance here, so a fetch that times out loses only that chunk's packets. */
@@ -413,6 +421,8 @@ int rd_wb_gains(rd_wideband *w, double *gain, int n);
  *     (RMS as a fraction of full scale: sqrt(power / (2 * block_size)) / 255)
  *   for the input chunk, over its 2 * decim * block_size components k, a = 2 k - 255 (RD_IQ_U8) or a = k (RD_IQ_S8, _S16):
  *     peak = max |a|, clipped = components at either end of the format's range, power = sum a^2
+ *     RD_IQ_CF32, in int16 units (full scale 32768): a = k = clip(rint(adm(v) * 32768), -32768, 32767), rint ties-to-even;
+ *     clipped = components with k at either end plus NaN components (a NaN is the value 0 for peak and power)
  *     (no admissible chunk overflows a field: < 2^32 components, a^2 <= 2^30)
  *   chunk = the chunk's sequence number since create / reset (rd_packet.call of its packets); rd_chan_level carries its low 32 bits.
  * rd_wb_set_levels needs a quiet receiver (RD_ERR_STATE otherwise), like rd_wb_set_parse; off (the default): nothing is

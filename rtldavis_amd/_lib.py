@@ -59,8 +59,10 @@ class RdInputLevel(C.Structure):
 
 
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
-RD_IQ_U8, RD_IQ_S8, RD_IQ_S16 = 0, 1, 2
-SAMPLE_FORMATS = {"u8": (RD_IQ_U8, np.uint8), "s8": (RD_IQ_S8, np.int8), "s16": (RD_IQ_S16, np.int16)}
+# (code 3 is unassigned and there is no "f32": float32 I/Q is "cf32", code 4)
+RD_IQ_U8, RD_IQ_S8, RD_IQ_S16, RD_IQ_CF32 = 0, 1, 2, 4
+SAMPLE_FORMATS = {"u8": (RD_IQ_U8, np.uint8), "s8": (RD_IQ_S8, np.int8), "s16": (RD_IQ_S16, np.int16),
+                  "cf32": (RD_IQ_CF32, np.float32)}
 
 
 def sample_format(name):
@@ -74,10 +76,19 @@ def sample_format(name):
 def iq_array(a, dtype):
     """A capture as a flat contiguous array of ``dtype`` (I,Q interleaved; [n, 2] or flat in).  Integer arrays of
     another width whose values fit are converted; anything else (complex, float, out of range) is a ValueError -
-    never a silent cast.  (uint8 keeps the conversion it always had: numpy's cast.)"""
+    never a silent cast.  (uint8 keeps the conversion it always had: numpy's cast.)  A float32 capture ("cf32") is
+    complex64 of shape [n], viewed as its float32 pairs without a copy, or float32, flat or [n, 2]; nothing else -
+    complex128, float64 and integers included."""
     if np.dtype(dtype) == np.uint8:
         return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
     a = np.asarray(a)
+    if np.dtype(dtype) == np.float32:
+        if a.dtype == np.complex64 and a.ndim == 1:
+            return np.ascontiguousarray(a).view(np.float32)
+        if a.dtype == np.float32 and (a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 2)):
+            return np.ascontiguousarray(a).reshape(-1)
+        raise ValueError(f"a {a.dtype} array of shape {a.shape} is not a capture of float32 I,Q samples "
+                         "(complex64 [n], or float32 flat or [n, 2])")
     if a.dtype != dtype:
         info = np.iinfo(dtype)
         if a.dtype.kind not in "iu" or (a.size and (a.min() < info.min or a.max() > info.max)):

@@ -1,4 +1,4 @@
-"""Wideband front end: one IQ capture (uint8, int8 or int16) -> one 268.8 kSPS uint8 IQ stream
+"""Wideband front end: one IQ capture (uint8, int8, int16 or float32) -> one 268.8 kSPS uint8 IQ stream
 per hop channel, channelized on the GPU straight into a BatchDemodulator's input buffer.
 
 rtldavis itself has no channelizer: it retunes one narrow-band dongle per hop
@@ -67,7 +67,8 @@ class Channelizer:
     """``Channelizer(channels_hz, centre_hz)`` moves each channel's centre to -out_rate/4, where the
     demodulator's Fs/4 rotation (dsp.py:42-49) expects the carrier, low-passes, decimates by
     ``decim`` and re-quantises to uint8 with ``gain``.  ``sample_format`` is the capture's: ``"u8"`` (RTL-SDR offset
-    bytes, x = (k - 127.4) / 127.6), ``"s8"`` (int8, x = k / 128) or ``"s16"`` (int16, x = k / 32768)."""
+    bytes, x = (k - 127.4) / 127.6), ``"s8"`` (int8, x = k / 128), ``"s16"`` (int16, x = k / 32768) or ``"cf32"``
+    (float32 I,Q or ``complex64``, nominal full scale 1.0: x = the value itself, clamped to [-8, 8], a NaN taken as 0)."""
 
     def __init__(self, channels_hz: Sequence[int] = US_CHANNELS_HZ, centre_hz: int = DEFAULT_CENTRE_HZ,
                  decim: int = DEFAULT_DECIM, taps: Optional[np.ndarray] = None, gain: float = 3.0,
@@ -97,7 +98,8 @@ class Channelizer:
         _lib.check(_lib.lib().rd_chan_set_gain(self._h, g.ctypes.data, g.size))
 
     def upload(self, wide_iq: np.ndarray) -> None:
-        """Copy a capture (``self.dtype``, I,Q interleaved: flat or [n, 2]) to the device."""
+        """Copy a capture (``self.dtype``, I,Q interleaved: flat or [n, 2]; ``"cf32"`` also ``complex64`` [n]) to the
+        device."""
         a = _lib.iq_array(wide_iq, self.dtype)
         _lib.check(_lib.lib().rd_chan_upload(self._h, a.ctypes.data, a.nbytes))
         self.n_wide = a.size // 2

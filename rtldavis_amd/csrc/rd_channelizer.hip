@@ -1,4 +1,4 @@
-// rd_channelizer.hip - wideband front end: one IQ capture (uint8, int8 or int16) at
+// rd_channelizer.hip - wideband front end: one IQ capture (uint8, int8, int16 or float32) at
 // decim x 268.8 kSPS -> one 268.8 kSPS uint8 IQ stream per hop channel, written straight into a
 // batch demodulator's resident input buffer.
 //
@@ -10,6 +10,7 @@
 //   x[n]   = lut(I[n]) + j lut(Q[n]),  lut(k) = (k - 127.4) / 127.6        (RD_IQ_U8: uint8, dsp.py:20-39)
 //                                       lut(k) = k / 128                    (RD_IQ_S8: int8)
 //                                       lut(k) = k / 32768                  (RD_IQ_S16: int16, host byte order)
+//                                       lut(v) = adm(v)                     (RD_IQ_CF32: float32, host byte order; below)
 //   z_c[t] = sum_{k<T} h[k] x[D t - k] e^{-j 2 pi shift_c (D t - k) / Fw}    (x[n<0] = 0)
 //          = e^{-j 2 pi frac(shift_c t / Fo)} sum_k g_c[k] x[D t - k],   g_c[k] = h[k] e^{+j 2 pi shift_c k / Fw}
 //   out_c[t] = clip(rint(gain z 127.6 + 127.4), 0, 255) per component       (the synth's quantiser)
@@ -77,6 +78,22 @@
 // 2.66 x uint8 - twice the MFMAs on twice the bytes, the rest at one wave per SIMD; 2480 x real time.  Not tried: a
 // 64-output tile (two workgroups per CU, but twice the A traffic from L2).
 //
+// RD_IQ_CF32: interleaved float32 I, Q in host byte order, 8 bytes per IQ pair, nominal full scale +-1.0.  The admitted
+// value of a component v is adm(v) = 0 if v is NaN, otherwise v clamped to [-8, +8] (so +-Inf is +-8), and
+// x[n] = adm(I[n]) + j adm(Q[n]); everything behind x is the definition above.  No DC term; a sample outside the capture
+// is exactly 0.  (Why 8: 18 dB over nominal keeps every digit far inside f16 and every fp32 partial sum far from
+// overflow; one NaN would otherwise poison every channel's window.)  The kernel is the int16 one with other digits: a
+// component enters as s = 2^12 adm(v) - an exact power-of-two pre-scale, |s| <= 2^15, undone in tap_unscale - split as
+// hi = f16(s), lo = f16(s - hi), both round-to-nearest-even conversions, s - hi exact in fp32.  |s - hi - lo| <=
+// max(2^-22 |s|, 2^-25); the pre-scale moves the f16 subnormal floor 2^-25 to 2^-37 in x's units, below the last bit
+// of any float32 that matters (without it a capture at 1 % of full scale would lose its low digit to the floor).  The
+// conversion must PRODUCE f16 subnormals (lo is one whenever |s| < 2^-3): the kernel relies on the default float
+// mode, f16 denormals enabled (FP_DENORM of f16/f64 = 3), the same mode under which the matrix pipe takes them.  The
+// staged sample is the four 16-bit lanes Ilo Ihi Qlo Qhi in int16's fragment order - one aligned ds_read_b128 per B
+// fragment, no VALU work in the loop; both digits meet the SAME tap (no 2^-8), the epilogue's scale is gains[ch].
+// Products stay exact: 11 x 11 bits, the smallest non-zero one 2^-24 2^-24 = 2^-48.  Bound: tests/chan_bound_cf32.py.
+// Levels: k = clip(rint(2^15 adm(v)), -32768, 32767) per component, i.e. int16 units (k_chan_levels).
+//
 // RETUNE (streaming form only; rd_wideband.hip: rd_wb_retune).  With a phase accumulator P_c, an integer in [0, Fo) that is
 // 0 after create and reset, and t the absolute output time,
 //   z_c[t] = e^{-j 2 pi frac((shift_c t + P_c) / Fo)} sum_k g_c[k] x[D t - k],   g_c[k] = h[k] e^{+j 2 pi shift_c k / Fw}
@@ -126,9 +143,13 @@ extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_
                                             // phasor of 32 output times e^{-j 2 pi frac(32 shift / Fo)} (cos, sin)
 
 // per sample format (rtldavis_hip.h: RD_IQ_*): bytes of an IQ pair in memory and staged in LDS, window samples per K step
-__host__ __device__ constexpr int rd_fmt_in_bps(int f) { return f == RD_IQ_S16 ? 4 : 2; }
-__host__ __device__ constexpr int rd_fmt_lds_bps(int f) { return f == RD_IQ_S16 ? 8 : 2; }
-__host__ __device__ constexpr int rd_fmt_kc(int f) { return f == RD_IQ_S16 ? RD_CHAN_KC / 2 : RD_CHAN_KC; }
+__host__ __device__ constexpr int rd_fmt_in_bps(int f) { return f == RD_IQ_CF32 ? 8 : f == RD_IQ_S16 ? 4 : 2; }
+__host__ __device__ constexpr int rd_fmt_lds_bps(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32 ? 8 : 2; }
+__host__ __device__ constexpr int rd_fmt_kc(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32 ? RD_CHAN_KC / 2 : RD_CHAN_KC; }
+// two 16-bit digits per component (four lanes per staged sample): the formats whose B fragment is one ds_read_b128
+__host__ __device__ constexpr bool rd_fmt_digits(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32; }
+#define RD_CF32_CLAMP 8.0f                  // adm: |v| <= 8
+#define RD_CF32_PRESCALE_LOG2 12            // staged s = 2^12 adm(v), |s| <= 2^15 < 65504
 
 typedef float rd_f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 rd_f16x8 __attribute__((ext_vector_type(8)));
@@ -203,6 +224,20 @@ __device__ __forceinline__ uint2 rd_chan_sm16(uint32_t w) {
                  (sq < 0 ? 0x80008000u : 0u) | (mq & 0xFFu) | ((mq >> 8) << 16)};
 }
 
+// adm (header: RD_IQ_CF32) of a float32 component given as its bits: NaN -> 0, else clamped to [-8, 8]
+__device__ __forceinline__ float rd_chan_adm(uint32_t bits) {
+    const float v = __builtin_bit_cast(float, bits);
+    return v != v ? 0.0f : fminf(fmaxf(v, -RD_CF32_CLAMP), RD_CF32_CLAMP);
+}
+// One float32 component -> its LDS dword lo | hi << 16: s = 2^12 adm(v), hi = f16(s), lo = f16(s - hi), both
+// round-to-nearest-even with subnormal results kept (the default float mode); s - hi is exact in fp32
+__device__ __forceinline__ uint32_t rd_chan_f32_digits(uint32_t bits) {
+    const float s = rd_chan_adm(bits) * (float)(1 << RD_CF32_PRESCALE_LOG2);
+    const _Float16 hi = (_Float16)s;
+    const _Float16 lo = (_Float16)(s - (float)hi);
+    return (uint32_t)__builtin_bit_cast(uint16_t, lo) | ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16);
+}
+
 template <bool STREAM, int FMT>
 __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint8_t *__restrict__ wide, long n_wide,
                                                     const uint4 *__restrict__ amat, const float2 *__restrict__ dc,
@@ -242,6 +277,11 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
 #pragma unroll
                     for (int w = 0; w < 4; w++) e[w] = (n + w >= 0 && n + w < n_wide) ? *(const uint32_t *)(wide + 4 * (n + w)) : 0u;
                     v[u] = uint4{e[0], e[1], e[2], e[3]};
+                } else if constexpr (FMT == RD_IQ_CF32) {
+                    uint2 e[2];
+#pragma unroll
+                    for (int w = 0; w < 2; w++) e[w] = (n + w >= 0 && n + w < n_wide) ? *(const uint2 *)(wide + 8 * (n + w)) : uint2{0u, 0u};
+                    v[u] = uint4{e[0].x, e[0].y, e[1].x, e[1].y};
                 } else {
                     uint16_t e[8];
 #pragma unroll
@@ -259,6 +299,10 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
                 const uint2 a = rd_chan_sm16(v[u].x), b = rd_chan_sm16(v[u].y), c = rd_chan_sm16(v[u].z), d = rd_chan_sm16(v[u].w);
                 *(uint4 *)(xs + 32 * q) = uint4{a.x, a.y, b.x, b.y};
                 *(uint4 *)(xs + 32 * q + 16) = uint4{c.x, c.y, d.x, d.y};
+            } else if constexpr (FMT == RD_IQ_CF32) {
+                // two samples (I0 Q0 I1 Q1 as float32) -> their eight lanes Ilo Ihi Qlo Qhi | the same of the second
+                *(uint4 *)(xs + 16 * q) = uint4{rd_chan_f32_digits(v[u].x), rd_chan_f32_digits(v[u].y),
+                                                rd_chan_f32_digits(v[u].z), rd_chan_f32_digits(v[u].w)};
             } else {
                 if constexpr (FMT == RD_IQ_S8) {
                     v[u].x ^= 0x80808080u; v[u].y ^= 0x80808080u; v[u].z ^= 0x80808080u; v[u].w ^= 0x80808080u;
@@ -288,7 +332,7 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         for (int e = 0; e < 16; e++) acc[b][e] = 0.0f;
     // B fragment of (time block tb, K step q): window samples 8q + 4h .. +3 of column 32 tb + r = eight bytes
     // (I0 Q0 I1 Q1 | I2 Q2 I3 Q3) -> eight 16-bit lanes
-    // (RD_IQ_S16: window samples 4q + 2h, + 1 = sixteen bytes = the eight 16-bit lanes as they are)
+    // (RD_IQ_S16, RD_IQ_CF32: window samples 4q + 2h, + 1 = sixteen bytes = the eight 16-bit lanes as they are)
     const uint8_t *xl = xs + LB * (D * r + (KC / 2) * h);
     for (int c0 = 0; c0 < n_chunks; c0 += NPF) {
 #pragma unroll
@@ -305,14 +349,14 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
                 for (int term = 0; term < RD_CHAN_TERMS; term++)
                     pre[s][term] = amine[(size_t)(qn * RD_CHAN_TERMS + term) * (RD_CHAN_RBG * 64)];
             }
-            using raw_t = typename std::conditional<FMT == RD_IQ_S16, uint4, uint2>::type;
+            using raw_t = typename std::conditional<rd_fmt_digits(FMT), uint4, uint2>::type;
             raw_t raw[RD_CHAN_TB];
 #pragma unroll
             for (int tb = 0; tb < RD_CHAN_TB; tb++) raw[tb] = *(const raw_t *)(xl + LB * (D * 32 * tb + KC * q));
 #pragma unroll
             for (int tb = 0; tb < RD_CHAN_TB; tb++) {
                 uint4 f;
-                if constexpr (FMT == RD_IQ_S16) {
+                if constexpr (rd_fmt_digits(FMT)) {
                     f = raw[tb];
                 } else {
                     // element order (I0 I1 Q0 Q1 | I2 I3 Q2 Q3) - the A fragments are laid out to match: the even bytes of
@@ -355,7 +399,7 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         // until a retune, rd_chan_retune); the quotient from a multiplication by 1 / Fo is off by one at most
         const double x = (double)shifts[ch] * (double)tm + (double)phase[ch];
         // the channel's gain (GAIN: a table, rd_chan_set_gain / rd_wb_set_gain; every entry (float)cfg.gain until then)
-        const float scale = gains[ch] * (FMT == RD_IQ_U8 ? 1.0f / 127.6f : FMT == RD_IQ_S8 ? 1.0f / 128.0f : 1.0f / 32768.0f);
+        const float scale = gains[ch] * (FMT == RD_IQ_U8 ? 1.0f / 127.6f : FMT == RD_IQ_S8 ? 1.0f / 128.0f : FMT == RD_IQ_S16 ? 1.0f / 32768.0f : 1.0f);
         double rm = __builtin_fma(-floor(x * inv_fo), fo, x);
         if (rm < 0.0) rm += fo;
         if (rm >= fo) rm -= fo;
@@ -369,8 +413,8 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
         for (int tb = 0; tb < RD_CHAN_TB; tb++) {
             const long t = t0 + 32 * tb + r;
             if (t < n_out) {
-                float2 d0 = float2{0.0f, 0.0f};   // (RD_IQ_S16: signed digits, no DC term)
-                if constexpr (FMT != RD_IQ_S16) d0 = dcc[t < n_early ? (int)t : RD_CHAN_EARLY];
+                float2 d0 = float2{0.0f, 0.0f};   // (RD_IQ_S16, RD_IQ_CF32: signed digits, no DC term)
+                if constexpr (!rd_fmt_digits(FMT)) d0 = dcc[t < n_early ? (int)t : RD_CHAN_EARLY];
                 const float re = __builtin_fmaf(acc[tb][e], tap_unscale, d0.x), im = __builtin_fmaf(acc[tb][e + 1], tap_unscale, d0.y);
                 const float zr = (re * cs - im * sn) * scale, zi = (re * sn + im * cs) * scale;
                 const float qr = fminf(fmaxf(rintf(zr * 127.6f + 127.4f), 0.0f), 255.0f);
@@ -426,7 +470,7 @@ __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__
         const double ph = -2.0 * M_PI * ((double)inc / (double)out_rate);
         dc[(size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1] = float2{(float)cos(ph), (float)sin(ph)};
     }
-    if (threadIdx.x == 64 && fmt != RD_IQ_S16) {   // (a lane of the second wave: the first one's has the rotation)
+    if (threadIdx.x == 64 && !rd_fmt_digits(fmt)) {   // (a lane of the second wave: the first one's has the rotation)
         const double dc_level = fmt == RD_IQ_U8 ? 127.4 : 128.0;
         double sr = 0.0, si = 0.0;
         int kdone = 0;
@@ -436,7 +480,8 @@ __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__
             dc[(size_t)c * RD_CHAN_DCN + t] = float2{(float)(-dc_level * (sr - si)), (float)(-dc_level * (sr + si))};
         }
     }
-    const int kc = fmt == RD_IQ_S16 ? RD_CHAN_KC / 2 : RD_CHAN_KC, per_lane = kc / 2, n_q = t_pad / kc + 1;
+    const int kc = rd_fmt_kc(fmt), per_lane = kc / 2, n_q = t_pad / kc + 1;
+    const bool two = rd_fmt_digits(fmt);          // two digits per component; int16's low one meets taps scaled 2^-8, cf32's does not
     const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
     // one fragment (8 f16 = 16 bytes) per item: K step q, term, lane half hh, part
     for (int it = threadIdx.x; it < 8 * n_q; it += blockDim.x) {
@@ -444,14 +489,14 @@ __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__
         uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int el = 0; el < 8; el++) {
-            // the inverse of chan_build_channel's element position: (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi) x 2
+            // the inverse of chan_build_channel's element position: (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi) x 2 (int16, cf32)
             const int comp = (el >> 1) & 1;
-            const int sl = fmt == RD_IQ_S16 ? el >> 2 : 2 * (el >> 2) + (el & 1), dig = fmt == RD_IQ_S16 ? el & 1 : 1;
+            const int sl = two ? el >> 2 : 2 * (el >> 2) + (el & 1), dig = two ? el & 1 : 1;
             const int k = t_pad - (q * kc + hh * per_lane + sl);
             if (k < 0 || k >= t_pad) continue;
             const float2 gk = g[k];
             const double a = part == 0 ? (comp == 0 ? (double)gk.x : -(double)gk.y) : (comp == 0 ? (double)gk.y : (double)gk.x);
-            const double as = a * tap_scale * (dig == 0 ? 1.0 / 256.0 : 1.0);
+            const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
             const _Float16 hi = (_Float16)(float)as;
             const _Float16 lo = (_Float16)(float)(as - (double)hi);
             const uint32_t bits = (uint32_t)__builtin_bit_cast(uint16_t, tm == 0 ? hi : lo);
@@ -472,6 +517,8 @@ __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__
 //     ticket takes the totals out (an exchange with 0, which leaves the words clear for the next launch) and writes the
 //     record.  uint8: a = 2 k - 255 as above.  int8: bit 7 flipped, u = k + 128, is the same byte arithmetic with
 //     a = u - 128, power = sum u^2 - 256 sum u + 16384 n, the ends -128 / 127 are u = 0 / 255.  int16: a = k per component.
+//     float32: a = k = clip(rint(2^15 adm(v)), -32768, 32767) per component - int16 units, full scale 32768 -, clipped =
+//     components with k at either end plus NaN components (a NaN is the value 0 for peak and power).
 // Sum b and sum b^2 of a dword are one packed-byte dot product each (v_dot4_u32_u8 against 0x01010101 and against
 // itself); the byte maxima are packed 16-bit maxima over the even and the odd bytes; a byte at an end of the range is a
 // zero byte of w or of ~w, counted by the carry-free zero-byte test and a population count.  A lane adds a vector's two
@@ -488,7 +535,7 @@ __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__
 typedef unsigned short rd_u16x2 __attribute__((ext_vector_type(2)));
 
 struct rd_lv_sums {
-    uint32_t hi, lo;       // packed 16-bit lanes while a lane runs, then scalars: max b and max (255 - b); int16: max |k|, 0
+    uint32_t hi, lo;       // packed 16-bit lanes while a lane runs, then scalars: max b and max (255 - b); int16, cf32: max |k|, 0
     uint32_t ends;
     uint64_t s1, s2;       // sum u, sum u^2 (int16: 0, sum k^2)
 };
@@ -524,6 +571,20 @@ __device__ __forceinline__ void rd_lv_words(rd_lv_sums &a, uint4 v) {
         a.hi = max(a.hi, max(m0, m1));
         a.ends += (uint32_t)(k0 == -32768 || k0 == 32767) + (uint32_t)(k1 == -32768 || k1 == 32767);
         a.s2 += (uint64_t)(m0 * m0 + m1 * m1);   // <= 2^31
+    }
+}
+// float32 components in int16 units (header: RD_IQ_CF32): k = clip(rint(2^15 adm(v)), -32768, 32767), the product exact
+// in fp32, rint ties-to-even; a NaN is the value 0 and counts as clipped
+__device__ __forceinline__ void rd_lv_floats(rd_lv_sums &a, uint4 v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const float f = __builtin_bit_cast(float, w[i]);
+        const int k = (int)fminf(fmaxf(rintf(rd_chan_adm(w[i]) * 32768.0f), -32768.0f), 32767.0f);
+        const uint32_t m = (uint32_t)(k < 0 ? -k : k);   // 0 .. 32768
+        a.hi = max(a.hi, m);
+        a.ends += (uint32_t)(k == -32768 || k == 32767 || f != f);
+        a.s2 += (uint64_t)(m * m);   // <= 2^30
     }
 }
 // the workgroup's totals in thread 0 (hi / lo as scalars)
@@ -577,12 +638,15 @@ __global__ __launch_bounds__(RD_LV_THREADS) void k_chan_levels(const uint4 *__re
     if (fmt == RD_IQ_S16) {
 #pragma unroll 4
         for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_words(a, wide[q]);
+    } else if (fmt == RD_IQ_CF32) {
+#pragma unroll 4
+        for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_floats(a, wide[q]);
     } else {
         const uint32_t flip = fmt == RD_IQ_S8 ? 0x80808080u : 0u;
 #pragma unroll 4
         for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_bytes(a, wide[q], flip);
     }
-    rd_lv_reduce(a, fmt != RD_IQ_S16);
+    rd_lv_reduce(a, !rd_fmt_digits(fmt));
     if (threadIdx.x != 0) return;
     unsigned long long *acc64 = (unsigned long long *)(acc + 4);
     atomicMax(&acc[0], a.hi);
@@ -687,8 +751,8 @@ static void chan_build_channel(rd_chan *h, int c, int64_t shift_hz, int64_t phas
     // rows 2c (re) and 2c+1 (im); kappa = 2 i + comp, window sample i = t_pad - 1 - k
     const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
     // RD_IQ_S16: kappa = 4 i + 2 comp + digit, a lane holds two samples (Ilo Ihi Qlo Qhi each); the low digit's taps
-    // are scaled by 2^-8 against the high digit's
-    const int per_lane = kc / 2, n_dig = fmt == RD_IQ_S16 ? 2 : 1;
+    // are scaled by 2^-8 against the high digit's.  RD_IQ_CF32: the same layout, both digits against the same tap
+    const int per_lane = kc / 2, n_dig = rd_fmt_digits(fmt) ? 2 : 1;
     for (int i = 0; i < kc * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
         const int k = t_pad - i;
         if (k < 0 || k >= t_pad) continue;  // (zero taps: the entries stay 0)
@@ -703,7 +767,7 @@ static void chan_build_channel(rd_chan *h, int c, int64_t shift_hz, int64_t phas
                     const int lane = 32 * hh + r0 + part;
                     // element position inside the fragment, see the kernel's B fragments:
                     // (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi | the same of the second sample)
-                    const int el = fmt == RD_IQ_S16 ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
+                    const int el = rd_fmt_digits(fmt) ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
                     for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
                         const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + el;
                         h->h_amat[at] = term[tm];
@@ -719,7 +783,7 @@ extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, con
 extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const double *taps, const int64_t *shift_hz,
                                   rd_chan **out) {
     if (!cfg || !taps || !shift_hz || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (fmt != RD_IQ_U8 && fmt != RD_IQ_S8 && fmt != RD_IQ_S16) return rd_fail_msg(RD_ERR_ARG, "unknown sample format %d", fmt);
+    if (fmt != RD_IQ_U8 && fmt != RD_IQ_S8 && fmt != RD_IQ_S16 && fmt != RD_IQ_CF32) return rd_fail_msg(RD_ERR_ARG, "unknown sample format %d", fmt);
     if (cfg->decim < 4 || cfg->decim > 4096 || cfg->decim % 4 || cfg->n_taps < 1 || cfg->n_taps > 8192 ||
         cfg->n_channels < 1 || cfg->n_channels > 4096 || cfg->out_rate < 1 || cfg->out_rate >= (1 << 26) ||
         !(cfg->gain > 0.0))
@@ -729,8 +793,8 @@ extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const doub
     const size_t span = (size_t)(RD_CHAN_TT - 1) * cfg->decim + t_pad + kc;
     if (rd_fmt_lds_bps(fmt) * span + 16 > 160 * 1024)
         return rd_fail_msg(RD_ERR_ARG, "decim x 127 + n_taps samples of %d bytes do not fit the 160 KiB LDS", rd_fmt_lds_bps(fmt));
-    // (RD_IQ_S16 has no DC term, hence no table of early ones and no limit from it)
-    const int n_early = fmt == RD_IQ_S16 ? 0 : (t_pad - 1 + cfg->decim - 1) / cfg->decim;
+    // (RD_IQ_S16 and RD_IQ_CF32 have no DC term, hence no table of early ones and no limit from it)
+    const int n_early = rd_fmt_digits(fmt) ? 0 : (t_pad - 1 + cfg->decim - 1) / cfg->decim;
     if (n_early > RD_CHAN_EARLY) return rd_fail_msg(RD_ERR_ARG, "n_taps / decim too large");
     rd_chan *h = new rd_chan();
     h->cfg = *cfg;
@@ -757,8 +821,9 @@ extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const doub
     if (sexp < -60) sexp = -60;
     h->tap_scale = std::ldexp(1.0, sexp);
     // (+24: the samples enter as k 2^-24; RD_IQ_S16: the low digit's taps carry 2^-8 more, so that the high digit's
-    // factor 256 stays inside f16)
-    h->tap_unscale = (float)std::ldexp(1.0, -sexp + 24 + (fmt == RD_IQ_S16 ? 8 : 0));
+    // factor 256 stays inside f16; RD_IQ_CF32: the samples enter as 2^12 x, real f16 values, not raw patterns)
+    h->tap_unscale = fmt == RD_IQ_CF32 ? (float)std::ldexp(1.0, -sexp - RD_CF32_PRESCALE_LOG2)
+                                       : (float)std::ldexp(1.0, -sexp + 24 + (fmt == RD_IQ_S16 ? 8 : 0));
     for (int c = 0; c < cfg->n_channels; c++) chan_build_channel(h, c, shift_hz[c], 0);
     *out = h;
     return RD_OK;
@@ -830,6 +895,7 @@ static const void *chan_kernel(bool stream, int fmt) {
     switch (fmt) {
     case RD_IQ_S8: return stream ? (const void *)k_channelize<true, RD_IQ_S8> : (const void *)k_channelize<false, RD_IQ_S8>;
     case RD_IQ_S16: return stream ? (const void *)k_channelize<true, RD_IQ_S16> : (const void *)k_channelize<false, RD_IQ_S16>;
+    case RD_IQ_CF32: return stream ? (const void *)k_channelize<true, RD_IQ_CF32> : (const void *)k_channelize<false, RD_IQ_CF32>;
     default: return stream ? (const void *)k_channelize<true, RD_IQ_U8> : (const void *)k_channelize<false, RD_IQ_U8>;
     }
 }

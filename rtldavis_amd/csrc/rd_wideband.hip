@@ -1,5 +1,5 @@
 // rd_wideband.hip - live wideband receiver (include/rtldavis_hip.h: rd_wideband_*): a capture that never ends, fed in
-// chunks of decim x block_size samples (uint8, int8 or int16 IQ: rd_wb_create_fmt), channelized into every hop channel and demodulated, all on the GPU.
+// chunks of decim x block_size samples (uint8, int8, int16 or float32 IQ: rd_wb_create_fmt), channelized into every hop channel and demodulated, all on the GPU.
 //
 // One handle owns one rd_chan configuration and one multi-stream rd_demod (n_streams = n_channels).  Per chunk, queued by
 // rd_wideband_submit and returning at once:

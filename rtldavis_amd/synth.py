@@ -174,7 +174,8 @@ def synth_wideband(seeds, shifts_hz, n_out: int, decim: int = 100, out_rate: int
                    amplitude: float = 0.12, noise: float = 0.02, noise_seed: int = 1234, sample_format: str = "u8",
                    payloads=None):
     """One wideband capture (I,Q interleaved, decim*out_rate samples/s, n_out*decim samples; sample_format "u8":
-    uint8 rint(x 127.6 + 127.4), "s8": int8 rint(x 128), "s16": int16 rint(x 32768), clipped, of the same complex x)
+    uint8 rint(x 127.6 + 127.4), "s8": int8 rint(x 128), "s16": int16 rint(x 32768), clipped, of the same complex x;
+    "cf32": float32 x itself, unquantised and unclipped)
     holding one burst per entry: burst i is the packet synth_stream(seeds[i]) carries, at
     shifts_hz[i] Hz from the capture's centre (+ a random cfo of +-2 kHz), starting somewhere
     between the first and the last 8192 output samples.  ``payloads`` (one on-air hex string per burst) overrides the
@@ -200,6 +201,11 @@ def synth_wideband(seeds, shifts_hz, n_out: int, decim: int = 100, out_rate: int
         phase = (float(shift) + cfo) * lo * (2.0 * np.pi / fw) + np.cumsum(freq) * (2.0 * np.pi / fw)
         x[lo:hi] += amplitude * np.exp(1j * phase)
         info.append((payload, start_out))
+    if sample_format == "cf32":
+        out = np.empty(2 * n, dtype=np.float32)
+        out[0::2] = x.real
+        out[1::2] = x.imag
+        return out, info
     dtype, scale, offset = {"u8": (np.uint8, 127.6, 127.4), "s8": (np.int8, 128.0, 0.0),
                             "s16": (np.int16, 32768.0, 0.0)}[sample_format]
     lim = np.iinfo(dtype)

@@ -47,7 +47,7 @@ class Levels(NamedTuple):
 class WidebandReceiver:
     """``WidebandReceiver(cfg, channels_hz, centre_hz)``: chunks of ``chunk_bytes`` (I,Q of ``chunk_samples`` =
     ``decim * cfg.block_size`` wideband samples at ``decim * cfg.bit_rate * cfg.symbol_length``, in ``sample_format``:
-    ``"u8"`` offset bytes, ``"s8"`` int8 or ``"s16"`` int16, see ``Channelizer``) in,
+    ``"u8"`` offset bytes, ``"s8"`` int8, ``"s16"`` int16 or ``"cf32"`` float32 / ``complex64``, see ``Channelizer``) in,
     one ``List[Packet]`` per channel and chunk out - each channel behaves like its own ``Demodulator``
     fed the channel's stream.  ``submit`` / ``fetch`` keep up to two chunks in flight (the copy of
     one beside the kernels of the other); ``demodulate`` is both in one call."""
@@ -182,7 +182,9 @@ class WidebandReceiver:
         ``clipped`` = bytes equal to 0 or 255, ``power`` = sum a^2, and ``gain``, the float32 in force for that chunk;
         the capture chunk's own record (``InputLevel``: how hard the ADC is driven); and the chunk's number.
         Conversions: a channel's RMS as a fraction of full scale is ``sqrt(power / (2 * block_size)) / 255``; the input's
-        likewise with its component count and 255 ("u8"), 128 ("s8") or 32768 ("s16").  ``agc.GainControl.update`` takes
+        likewise with its component count (``2 * chunk_samples``) and 255 ("u8"), 128 ("s8") or 32768 ("s16", and "cf32",
+        whose components are metered in int16 units: k = clip(rint(32768 v), -32768, 32767) of the value clamped to
+        [-8, 8], a NaN counted as clipped and as the value 0).  ``agc.GainControl.update`` takes
         the result as it is.  RuntimeError before any fetch and when levels were off for that chunk."""
         recs = (_lib.RdChanLevel * self.n_channels)()
         inp = _lib.RdInputLevel()

@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="timed windows (each after a reset); the median is reported")
     ap.add_argument("--capture-chunks", type=int, default=6, help="chunks in the synthesised capture")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--sample-format", default="u8", choices=["u8", "s8", "s16"], help="the capture's sample format")
+    ap.add_argument("--sample-format", default="u8", choices=["u8", "s8", "s16", "cf32"], help="the capture's sample format")
     ap.add_argument("--parse", action="store_true", help="device parse on, parsed() read per chunk; also time the route without it")
     ap.add_argument("--retune", default="none", choices=["none", "one", "all"],
                     help="retune one channel or all of them before every chunk")
