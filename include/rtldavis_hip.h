@@ -346,6 +346,15 @@ int rd_chan_input_ptr(rd_chan *h, size_t n_wide_samples, void **dev_ptr);
 int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_stream_stride, void *hip_stream);
 /* Same, into a host array uint8 [n_channels][n_out][2] (synchronous). */
 int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, size_t nbytes);
+/* Power spectrum of the uploaded capture (SPECTRUM below: the definition, with L = the capture's IQ pairs; the same kernel
+ * as the streaming receiver's, so a chunk uploaded alone gives that chunk's record bit for bit).  power_host: n_bins
+ * doubles in ascending frequency; *segments (may be NULL) = L / n_bins.  Synchronous, like rd_chan_run_host.
+ * RD_ERR_STATE without a resident capture, RD_ERR_ARG for an n_bins that is no power of two in 64 .. 4096 or exceeds L. */
+int rd_chan_spectrum(rd_chan *h, int n_bins, double *power_host, uint32_t *segments);
+/* The same, asynchronous on hip_stream (NULL = default stream) into device memory, as rd_chan_run is to rd_chan_run_host:
+ * dst_dev (16-byte aligned) receives the record {uint64 chunk = 0; uint32 segments; uint32 n_bins} + n_bins doubles.
+ * The first call with a new n_bins builds the tables and waits for that stream once. */
+int rd_chan_spectrum_dev(rd_chan *h, int n_bins, void *dst_dev, void *hip_stream);
 /* Per-channel gain: gain[c] replaces cfg.gain for channel c (n = n_channels, every gain finite and > 0 - in float32
  * too, which is what the kernel multiplies with - else RD_ERR_ARG and nothing changes) in the runs that follow.  With every
  * entry equal to cfg.gain the output is the scalar form's, byte for byte.  Needs a quiet handle: the caller has waited
@@ -444,6 +453,32 @@ typedef struct rd_input_level {
 } rd_input_level;
 int rd_wb_set_levels(rd_wideband *w, int enabled);
 int rd_wb_levels(rd_wideband *w, rd_chan_level *out, int n, rd_input_level *in);
+/* SPECTRUM (k_chan_spectrum, rd_spectrum.hip): the power spectrum of every chunk, on the device.  With N = n_bins a power
+ * of two in 64 .. 4096, L = decim * block_size the chunk's IQ pairs (N <= L) and S = L / N whole segments (segment s =
+ * samples [s N, (s + 1) N) of this chunk; the L - S N samples at its end are not used; no state crosses chunks):
+ *   x[n]   the sample as complex float32, the channelizer's meaning of each format: RD_IQ_U8 (10 k - 1274) * f32(1 / 1276)
+ *          per component (= (k - 127.4) / 127.6 to 1.5 ulp relative), RD_IQ_S8 k / 128, RD_IQ_S16 k / 32768, RD_IQ_CF32 adm(v)
+ *   w[n]   = 0.5 - 0.5 cos(2 pi n / N), periodic Hann, a float32 table rounded once from float64 (the twiddles likewise)
+ *   X_s[k] = sum_n w[n] x[s N + n] e^{-2 pi i k n / N}                                  (float32 arithmetic per segment)
+ *   P[j]   = 1 / (S (N/2)^2) sum_s |X_s[(j + N/2) mod N]|^2                             (float64 sum and scaling)
+ * in ascending frequency: bin j lies at centre + (j - N/2) wide_rate / N, and (N/2)^2 = (sum w)^2, so a full-scale
+ * complex tone on a bin centre reads 1.0.  Against the same in float64 every bin is within 2.01 ((6.7 log2 N + 4) 2^-24)
+ * sum_k P[k] (tests/spectrum_model.py).  The same chunk and N give the same bits on every run: a fixed number of
+ * workgroups min(S, 64), each summing its segments in ascending order, their partial sums added in ascending order.
+ * rd_wb_set_spectrum: n_bins, or 0 = off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE
+ * otherwise), like rd_wb_set_levels; RD_ERR_ARG for another value or n_bins > L.  No device work (safe before fork): the
+ * tables and record slots are made by the next submit.
+ * rd_wb_spectrum: the record of the chunk the last fetch returned (power: n_bins doubles; info may be NULL), kept by that
+ * fetch - valid with later chunks in flight, until the next fetch.  RD_ERR_STATE before any fetch and when that chunk was
+ * submitted with the spectrum off; RD_ERR_ARG when n_bins is not that record's.  rd_wideband_reset keeps the setting and
+ * drops the record. */
+typedef struct rd_spectrum_info {
+    uint64_t chunk;      /* the chunk's sequence number since create / reset */
+    uint32_t segments;   /* S */
+    uint32_t n_bins;     /* N */
+} rd_spectrum_info;
+int rd_wb_set_spectrum(rd_wideband *w, int n_bins);
+int rd_wb_spectrum(rd_wideband *w, double *power, int n_bins, rd_spectrum_info *info);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

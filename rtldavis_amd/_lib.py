@@ -58,6 +58,10 @@ class RdInputLevel(C.Structure):
     _fields_ = [("power", C.c_uint64), ("chunk", C.c_uint64), ("peak", C.c_uint32), ("clipped", C.c_uint32)]
 
 
+class RdSpectrumInfo(C.Structure):
+    _fields_ = [("chunk", C.c_uint64), ("segments", C.c_uint32), ("n_bins", C.c_uint32)]
+
+
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
 # (code 3 is unassigned and there is no "f32": float32 I/Q is "cf32", code 4)
 RD_IQ_U8, RD_IQ_S8, RD_IQ_S16, RD_IQ_CF32 = 0, 1, 2, 4
@@ -155,6 +159,8 @@ SIGNATURES = {
     "rd_chan_run": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "rd_chan_run_host": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
     "rd_chan_set_gain": (C.c_int, [_P, _P, C.c_int]),
+    "rd_chan_spectrum": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "rd_chan_spectrum_dev": (C.c_int, [_P, C.c_int, _P, _P]),
     "rd_wideband_create": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), _P, _P, C.POINTER(_P)]),
     "rd_wb_create_fmt": (C.c_int, [C.POINTER(RdConfig), C.POINTER(RdChanConfig), C.c_int, _P, _P, C.POINTER(_P)]),
     "rd_wideband_destroy": (None, [_P]),
@@ -173,6 +179,8 @@ SIGNATURES = {
     "rd_wb_gains": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_set_levels": (C.c_int, [_P, C.c_int]),
     "rd_wb_levels": (C.c_int, [_P, _P, C.c_int, C.POINTER(RdInputLevel)]),
+    "rd_wb_set_spectrum": (C.c_int, [_P, C.c_int]),
+    "rd_wb_spectrum": (C.c_int, [_P, _P, C.c_int, C.POINTER(RdSpectrumInfo)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),

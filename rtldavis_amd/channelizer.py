@@ -77,6 +77,7 @@ class Channelizer:
         self.sample_format = sample_format
         self._fmt, self.dtype = _lib.sample_format(sample_format)
         plan_channels(self, channels_hz, centre_hz, decim, taps, gain, out_rate, if_hz)
+        self.centre_hz = int(centre_hz)
         _lib.check(_lib.lib().rd_chan_create_fmt(C.byref(chan_config(self)), self._fmt, self.taps.ctypes.data,
                                                  self.shift_hz.ctypes.data, C.byref(self._h)))
         self.n_wide = 0
@@ -110,6 +111,21 @@ class Channelizer:
         out = np.empty((self.n_channels, 2 * n_out), np.uint8)
         _lib.check(_lib.lib().rd_chan_run_host(self._h, n_out, out.ctypes.data, out.size))
         return out
+
+    def spectrum(self, n_bins: int):
+        """Power spectrum of the uploaded capture as ``wideband.Spectrum`` (``chunk`` = 0): what
+        ``WidebandReceiver.spectrum()`` gives for a chunk, over the capture's ``n_wide // n_bins`` whole windows - for a
+        chunk uploaded alone the same bits.  ``n_bins``: a power of two in 64 .. 4096, at most ``n_wide`` (ValueError);
+        RuntimeError without an uploaded capture."""
+        from .wideband import Spectrum, spectrum_freqs
+        if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 64 <= int(n_bins) <= 4096 \
+                or int(n_bins) & (int(n_bins) - 1):
+            raise ValueError("n_bins: a power of two in 64 .. 4096")
+        n = int(n_bins)
+        power = np.empty(n, np.float64)
+        seg = C.c_uint32(0)
+        _lib.check(_lib.lib().rd_chan_spectrum(self._h, n, power.ctypes.data, C.byref(seg)))
+        return Spectrum(power, spectrum_freqs(self.centre_hz, self.wide_rate, n), int(seg.value), 0)
 
     def run_into(self, bd, hip_stream: int = 0) -> None:
         """Channelize straight into a BatchDemodulator's resident input (n_streams == n_channels)."""

@@ -148,7 +148,7 @@ __host__ __device__ constexpr int rd_fmt_lds_bps(int f) { return f == RD_IQ_S16 
 __host__ __device__ constexpr int rd_fmt_kc(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32 ? RD_CHAN_KC / 2 : RD_CHAN_KC; }
 // two 16-bit digits per component (four lanes per staged sample): the formats whose B fragment is one ds_read_b128
 __host__ __device__ constexpr bool rd_fmt_digits(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32; }
-#define RD_CF32_CLAMP 8.0f                  // adm: |v| <= 8
+// RD_CF32_CLAMP (adm: |v| <= 8) and rd_chan_adm: rd_internal.h (k_chan_spectrum admits float32 components the same way)
 #define RD_CF32_PRESCALE_LOG2 12            // staged s = 2^12 adm(v), |s| <= 2^15 < 65504
 
 typedef float rd_f32x16 __attribute__((ext_vector_type(16)));
@@ -183,6 +183,7 @@ struct rd_chan {
     int64_t *d_rt = nullptr;       // one slot on the device (its copies and kernels are ordered by the stream)
     uint8_t *d_wide = nullptr;     // resident capture, rd_fmt_in_bps bytes per sample
     size_t wide_cap = 0, wide_n = 0;
+    rd_spec *spec = nullptr;       // rd_chan_spectrum's tables and scratch (rd_spectrum.hip), made on first use
     bool dev_ready = false;
     int device = -1;               // the device the buffers live on
     pid_t pid = 0;                 // the process that allocated them
@@ -224,11 +225,6 @@ __device__ __forceinline__ uint2 rd_chan_sm16(uint32_t w) {
                  (sq < 0 ? 0x80008000u : 0u) | (mq & 0xFFu) | ((mq >> 8) << 16)};
 }
 
-// adm (header: RD_IQ_CF32) of a float32 component given as its bits: NaN -> 0, else clamped to [-8, 8]
-__device__ __forceinline__ float rd_chan_adm(uint32_t bits) {
-    const float v = __builtin_bit_cast(float, bits);
-    return v != v ? 0.0f : fminf(fmaxf(v, -RD_CF32_CLAMP), RD_CF32_CLAMP);
-}
 // One float32 component -> its LDS dword lo | hi << 16: s = 2^12 adm(v), hi = f16(s), lo = f16(s - hi), both
 // round-to-nearest-even with subnormal results kept (the default float mode); s - hi is exact in fp32
 __device__ __forceinline__ uint32_t rd_chan_f32_digits(uint32_t bits) {
@@ -838,6 +834,7 @@ extern "C" void rd_chan_destroy(rd_chan *h) {
         hipFree(h->d_phase); hipFree(h->d_taps); hipFree(h->d_rt); hipHostFree(h->h_rt);
         hipFree(h->d_gains); hipHostFree(h->h_gains);
     }
+    rd_spec_destroy(h->spec);      // (checks the owning process itself)
     delete h;
 }
 
@@ -948,6 +945,40 @@ extern "C" int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, siz
     }
     hipFree(d);
     return rc;
+}
+
+// SPECTRUM, one-shot form: the power spectrum of the uploaded capture (rd_spectrum.hip: the kernel and launch helper the
+// streaming receiver uses per chunk, so a chunk uploaded alone gives that chunk's record bit for bit).  rd_chan_spectrum_dev
+// queues it on a stream into device memory (as rd_chan_run does); rd_chan_spectrum is the synchronous host form.
+extern "C" int rd_chan_spectrum_dev(rd_chan *h, int n_bins, void *dst_dev, void *hip_stream) {
+    if (!h || !dst_dev) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (!h->dev_ready || !h->d_wide || !h->wide_n) return rd_fail_msg(RD_ERR_STATE, "no capture resident: rd_chan_upload first");
+    int rc = rd_spec_check(n_bins, h->wide_n);
+    if (rc) return rc;
+    if (h->device >= 0) CHK(hipSetDevice(h->device));
+    if ((rc = rd_spec_prepare(&h->spec, n_bins, h->wide_n, (hipStream_t)hip_stream))) return rc;
+    return rd_spec_launch(h->spec, h->d_wide, h->fmt, h->wide_n, 0, dst_dev, (hipStream_t)hip_stream);
+}
+
+extern "C" int rd_chan_spectrum(rd_chan *h, int n_bins, double *power_host, uint32_t *segments) {
+    if (!h || !power_host) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (!h->dev_ready || !h->d_wide || !h->wide_n) return rd_fail_msg(RD_ERR_STATE, "no capture resident: rd_chan_upload first");
+    int rc = rd_spec_check(n_bins, h->wide_n);
+    if (rc) return rc;
+    const size_t bytes = RD_SPEC_HDR_BYTES + (size_t)n_bins * sizeof(double);
+    uint8_t *d = nullptr;
+    CHK(hipMalloc(&d, bytes));
+    std::vector<uint8_t> rec(bytes);
+    rc = rd_chan_spectrum_dev(h, n_bins, d, nullptr);
+    if (rc == RD_OK) {
+        hipError_t e = hipMemcpy(rec.data(), d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = rd_fail_msg(RD_ERR_DEVICE, "hipMemcpy: %s", hipGetErrorString(e));
+    }
+    hipFree(d);
+    if (rc) return rc;
+    memcpy(power_host, rec.data() + RD_SPEC_HDR_BYTES, (size_t)n_bins * sizeof(double));
+    if (segments) memcpy(segments, rec.data() + 8, sizeof(uint32_t));
+    return RD_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1100,6 +1131,7 @@ int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, 
     return chan_launch(h, true, wide, n_wide, prev, n_early, t_base_mod, (long)n_out, gx, dst, dst_stride, st);
 }
 
+int rd_chan_format(const rd_chan *h) { return h ? h->fmt : RD_IQ_U8; }
 int rd_chan_n_channels(const rd_chan *h) { return h ? h->cfg.n_channels : 0; }
 int64_t rd_chan_out_rate(const rd_chan *h) { return h ? h->cfg.out_rate : 0; }
 int64_t rd_chan_wide_rate(const rd_chan *h) { return h ? (int64_t)h->cfg.out_rate * h->cfg.decim : 0; }

@@ -221,6 +221,27 @@ int rd_chan_stream_gains(rd_chan *h, const float *gain, int slot, hipStream_t st
 #define RD_LV_ACC_WORDS 8
 int rd_chan_stream_levels(rd_chan *h, const uint8_t *wide, size_t n_out, const uint8_t *chan_out, size_t out_stride,
                           uint64_t seq, rd_chan_level *out, rd_input_level *in, uint32_t *acc, hipStream_t st);
+// adm (include/rtldavis_hip.h: RD_IQ_CF32) of a float32 component given as its bits: NaN -> 0, else clamped to [-8, 8]
+#define RD_CF32_CLAMP 8.0f
+__device__ __forceinline__ float rd_chan_adm(uint32_t bits) {
+    const float v = __builtin_bit_cast(float, bits);
+    return v != v ? 0.0f : fminf(fmaxf(v, -RD_CF32_CLAMP), RD_CF32_CLAMP);
+}
+// Power spectrum of a capture (rd_spectrum.hip: k_chan_spectrum; the definition: include/rtldavis_hip.h, SPECTRUM).
+// rd_spec: the tables of one n_bins (periodic Hann window, per-stage twiddles), the workgroups' partial sums and the
+// ticket word, on the current device.  rd_spec_check: the argument rule (RD_ERR_ARG with a message, no device work).
+// rd_spec_prepare: (re)builds *sp when it is null or holds another n_bins or fewer workgroups than n_samples needs - the
+// caller knows that no launch on the old one is still running.  rd_spec_launch: one launch on st over IQ pairs
+// [0, n_samples) of `wide` (device, 16-byte aligned, sample format fmt); out: RD_SPEC_HDR_BYTES of header {uint64 seq;
+// uint32 segments; uint32 n_bins} + n_bins doubles, a device address (mapped host memory included).
+#define RD_SP_MAX_GROUPS 64
+#define RD_SPEC_HDR_BYTES 16
+struct rd_spec;
+int rd_spec_check(int n_bins, size_t n_samples);
+int rd_spec_prepare(rd_spec **sp, int n_bins, size_t n_samples, hipStream_t st);
+int rd_spec_launch(rd_spec *sp, const uint8_t *wide, int fmt, size_t n_samples, uint64_t seq, void *out, hipStream_t st);
+void rd_spec_destroy(rd_spec *sp);
+int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);
 int64_t rd_chan_wide_rate(const rd_chan *h);

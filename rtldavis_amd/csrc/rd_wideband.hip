@@ -29,6 +29,12 @@
 // chunk's k_channelize (behind e_chan: the copy stream never waits for it) and writes its records into the mapped pinned
 // slot of the chunk's parity.  The chunk's demodulator launch comes after it on the compute stream, so when a fetch has
 // seen that launch report, the records are complete; the fetch copies them out of the slot, which chunk k+2 reuses.
+// Spectrum (rd_wb_set_spectrum / rd_wb_spectrum; rd_spectrum.hip): with n_bins set, k_chan_spectrum is queued in the same
+// place - behind e_chan, in front of the chunk's demodulator launch, beside k_chan_levels when both are on - and writes
+// the record (header + n_bins doubles) into a mapped pinned slot of the chunk's parity, which the fetch copies out like
+// the level records.  Both kernels READ d_wide[s] after the chunk's channelizer: that buffer is next overwritten by the
+// copy of chunk k+2, which waits for e_chan of chunk k+1 - recorded later on the compute stream than either kernel of
+// chunk k, so the copy cannot overtake them although they come behind chunk k's own e_chan.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -80,7 +86,17 @@ struct rd_wideband {
     uint32_t *d_lvacc = nullptr;
     std::vector<rd_chan_level> lv_last;
     rd_input_level lv_in_last = {};
+    // spectrum: bins per record (0: off; switched on a quiet receiver like levels), the kernel's tables and scratch, the
+    // mapped pinned slots (header + sp_slot_n doubles) per parity, and the record the last fetch kept
+    int spec_n = 0, sp_slot_n = 0;
+    bool last_spec = false;
+    rd_spec *spec = nullptr;
+    uint8_t *h_sp[2] = {nullptr, nullptr};
+    rd_spectrum_info sp_info_last = {};
+    std::vector<double> sp_last;
 };
+
+static_assert(sizeof(rd_spectrum_info) == RD_SPEC_HDR_BYTES, "the slot's header is rd_spectrum_info");
 
 // the tuning the next submitted chunk will use, channel c: the pending shift takes over at t_b = clock
 static void wb_next_tuning(const rd_wideband *w, int c, int64_t *shift, int64_t *phase) {
@@ -155,9 +171,11 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             if (w->e_in[i]) hipEventDestroy(w->e_in[i]);
             if (w->e_chan[i]) hipEventDestroy(w->e_chan[i]);
             hipHostFree(w->h_lv[i]);
+            hipHostFree(w->h_sp[i]);
         }
         hipFree(w->d_lvacc);
     }
+    rd_spec_destroy(w->spec);   // (checks the owning process itself)
     rd_chan_destroy(w->chan);
     delete w;
 }
@@ -198,6 +216,26 @@ static int wb_alloc_levels(rd_wideband *w) {
     return RD_OK;
 }
 
+// the spectrum's tables and scratch for the setting in force, and the two record slots (remade when n_bins changes:
+// the receiver was quiet when it did, so nothing reads or writes the old ones)
+static size_t wb_sp_bytes(int n) { return RD_SPEC_HDR_BYTES + (size_t)n * sizeof(double); }
+static int wb_alloc_spectrum(rd_wideband *w) {
+    const size_t samples = w->chunk_bytes / (size_t)rd_chan_bytes_per_sample(w->chan);
+    int rc = rd_spec_prepare(&w->spec, w->spec_n, samples, w->st);
+    if (rc || w->sp_slot_n == w->spec_n) return rc;
+    for (int i = 0; i < 2; i++) {
+        if (w->h_sp[i]) WCHK(hipHostFree(w->h_sp[i]));
+        w->h_sp[i] = nullptr;
+    }
+    w->sp_slot_n = 0;
+    for (int i = 0; i < 2; i++) {
+        WCHK(hipHostMalloc((void **)&w->h_sp[i], wb_sp_bytes(w->spec_n), hipHostMallocMapped));
+        memset(w->h_sp[i], 0xFF, RD_SPEC_HDR_BYTES);   // (no chunk has the sequence number 2^64 - 1)
+    }
+    w->sp_slot_n = w->spec_n;
+    return RD_OK;
+}
+
 extern "C" int rd_wideband_reset(rd_wideband *w) {
     if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
     int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
@@ -213,6 +251,9 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->last_levels = false;
     for (int i = 0; i < 2; i++)   // (chunk numbers restart: no record of the run before may pass for one of this run)
         if (w->h_lv[i]) memset(w->h_lv[i], 0xFF, wb_lv_bytes(w));
+    w->last_spec = false;         // (the setting stays; the record of the run before goes)
+    for (int i = 0; i < 2; i++)
+        if (w->h_sp[i]) memset(w->h_sp[i], 0xFF, RD_SPEC_HDR_BYTES);
     return RD_OK;
 }
 
@@ -249,6 +290,29 @@ extern "C" int rd_wb_levels(rd_wideband *w, rd_chan_level *out, int n, rd_input_
     return RD_OK;
 }
 
+extern "C" int rd_wb_set_spectrum(rd_wideband *w, int n_bins) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before the spectrum is switched", rd_demod_inflight(w->dem));
+    if (n_bins != 0) {
+        int rc = rd_spec_check(n_bins, w->chunk_bytes / (size_t)rd_chan_bytes_per_sample(w->chan));
+        if (rc) return rc;
+    }
+    w->spec_n = n_bins;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_spectrum(rd_wideband *w, double *power, int n_bins, rd_spectrum_info *info) {
+    if (!w || !power) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_spec) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with the spectrum off (rd_wb_set_spectrum)");
+    if (n_bins != (int)w->sp_info_last.n_bins)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d bins of %u", n_bins, w->sp_info_last.n_bins);
+    memcpy(power, w->sp_last.data(), (size_t)n_bins * sizeof(double));
+    if (info) *info = w->sp_info_last;
+    return RD_OK;
+}
+
 extern "C" int rd_wb_retune(rd_wideband *w, const int64_t *shift_hz, int n) {
     if (!w || !shift_hz) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d shifts for %d channels", n, w->n_ch);
@@ -277,6 +341,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     rc = wb_alloc(w);
     if (rc) return rc;
     if (w->levels && (rc = wb_alloc_levels(w))) return rc;
+    if (w->spec_n && (rc = wb_alloc_spectrum(w))) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
     const int s = (int)(w->n_sub & 1);
@@ -306,6 +371,14 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                                    (rd_input_level *)(lv + w->n_ch), w->d_lvacc, w->st);
         if (rc) return rc;
     }
+    if (w->spec_n) {
+        // spectrum slot s: free by the argument for the level slot; the kernel reads d_wide[s] only (header comment)
+        void *sp = nullptr;
+        WCHK(hipHostGetDevicePointer(&sp, w->h_sp[s], 0));
+        rc = rd_spec_launch(w->spec, w->d_wide[s], rd_chan_format(w->chan), w->chunk_bytes / (size_t)rd_chan_bytes_per_sample(w->chan),
+                            (uint64_t)w->n_sub, sp, w->st);
+        if (rc) return rc;
+    }
     w->clock += w->B;
     w->n_sub++;
     return rd_demod_submit_device(w->dem, w->d_out[s]);
@@ -315,6 +388,18 @@ static int wb_fetched(rd_wideband *w, int rc) {
     if (rc != RD_OK && rc != RD_ERR_CAPACITY) return rc;
     w->last = w->n_sub - 1 - rd_demod_pending(w->dem);  // (the oldest in flight)
     w->last_levels = false;
+    w->last_spec = false;
+    if (w->spec_n) {
+        // as the level records below: k_chan_spectrum ran before the demodulator launch that has reported
+        const uint8_t *slot = w->h_sp[w->last & 1];
+        memcpy(&w->sp_info_last, slot, sizeof(rd_spectrum_info));
+        if (w->sp_info_last.chunk != (uint64_t)w->last || (int)w->sp_info_last.n_bins != w->spec_n)
+            return rd_fail_msg(RD_ERR_DEVICE, "the spectrum record belongs to chunk %llu (%u bins), not %ld (%d bins)",
+                               (unsigned long long)w->sp_info_last.chunk, w->sp_info_last.n_bins, w->last, w->spec_n);
+        const double *p = (const double *)(slot + RD_SPEC_HDR_BYTES);
+        w->sp_last.assign(p, p + w->spec_n);
+        w->last_spec = true;
+    }
     if (!w->levels) return rc;
     // The chunk's demodulator launch has reported, and k_chan_levels ran before it on the same stream: keep its records
     // (the slot is chunk last + 2's from its submit on).  Every record carries the chunk's number - a record of another

@@ -44,6 +44,31 @@ class Levels(NamedTuple):
     chunk: int
 
 
+class Spectrum(NamedTuple):
+    """``WidebandReceiver.spectrum()`` / ``Channelizer.spectrum()``: ``power`` (float64 [n_bins], ascending frequency,
+    1.0 = a full-scale complex tone on a bin centre), ``freqs_hz`` (float64 [n_bins], the bins' absolute RF centres:
+    ``centre_hz + (j - n_bins / 2) * wide_rate / n_bins``), ``segments`` (windows of ``n_bins`` samples averaged) and
+    ``chunk`` (the chunk's number since construction / ``reset()``; 0 for a ``Channelizer``)."""
+    power: np.ndarray
+    freqs_hz: np.ndarray
+    segments: int
+    chunk: int
+
+    def db(self) -> np.ndarray:
+        """``10 log10(power)`` in dBFS, an empty bin as the smallest positive float64's."""
+        return 10.0 * np.log10(np.maximum(self.power, np.finfo(np.float64).tiny))
+
+    def band_power(self, lo_hz: float, hi_hz: float) -> float:
+        """The sum of the bins whose centres lie in [lo_hz, hi_hz] - e.g. the occupancy of one hop channel."""
+        sel = (self.freqs_hz >= lo_hz) & (self.freqs_hz <= hi_hz)
+        return float(self.power[sel].sum())
+
+
+def spectrum_freqs(centre_hz: int, wide_rate: int, n_bins: int) -> np.ndarray:
+    """The bin centres of an ``n_bins`` spectrum in Hz, ascending; entry ``n_bins // 2`` is ``centre_hz``."""
+    return float(centre_hz) + (np.arange(n_bins, dtype=np.float64) - n_bins // 2) * (float(wide_rate) / n_bins)
+
+
 class WidebandReceiver:
     """``WidebandReceiver(cfg, channels_hz, centre_hz)``: chunks of ``chunk_bytes`` (I,Q of ``chunk_samples`` =
     ``decim * cfg.block_size`` wideband samples at ``decim * cfg.bit_rate * cfg.symbol_length``, in ``sample_format``:
@@ -63,11 +88,13 @@ class WidebandReceiver:
             raise ValueError(f"block_size {cfg.block_size} is not a positive multiple of 128")
         plan_channels(self, channels_hz, centre_hz, decim, taps, gain, int(cfg.bit_rate) * int(cfg.symbol_length))
         self._plan_shift_hz = self.shift_hz.copy()                  # the constructed plan: retune() offsets, reset()
+        self.centre_hz = int(centre_hz)                             # spectrum(): the bins' absolute frequencies
         self.block_size = int(cfg.block_size)
         self.chunk_samples = self.decim * self.block_size           # IQ pairs per chunk
         self.chunk_bytes = 2 * np.dtype(self.dtype).itemsize * self.chunk_samples
         _lib.check(_lib.lib().rd_wb_create_fmt(C.byref(_cfg_struct(cfg)), C.byref(chan_config(self)), self._fmt,
                                                self.taps.ctypes.data, self.shift_hz.ctypes.data, C.byref(self._h)))
+        self._spectrum_bins = self._fetched_bins = 0                # set_spectrum(); the setting at the last fetch
         self._cap = 64 * max(1, self.n_channels)
         self._recs = (_lib.RdPacket * self._cap)()
 
@@ -103,7 +130,9 @@ class WidebandReceiver:
         """Packets of the oldest chunk in flight, one list per channel."""
         n = C.c_int(0)
         rc = _lib.lib().rd_wideband_fetch(self._h, self._recs, self._cap, C.byref(n))
-        return self._take(rc, n)
+        out = self._take(rc, n)
+        self._fetched_bins = self._spectrum_bins
+        return out
 
     def demodulate(self, chunk: np.ndarray) -> List[List[Packet]]:
         """submit + fetch of one chunk on a quiet receiver."""
@@ -196,10 +225,36 @@ class WidebandReceiver:
             out[f] = raw[f]
         return Levels(out, InputLevel(int(inp.peak), int(inp.clipped), int(inp.power)), int(inp.chunk))
 
+    def set_spectrum(self, n_bins: Optional[int]) -> None:
+        """From the next chunk on, compute every chunk's power spectrum on the device (one more kernel behind its
+        channelizer; ``spectrum()`` returns it): ``n_bins`` a power of two in 64 .. 4096 and at most ``chunk_samples``;
+        ``0`` or ``None`` switches it off (the default: nothing is launched).  Needs a receiver with nothing in flight
+        (RuntimeError); ValueError for another value."""
+        n = 0 if n_bins is None else n_bins
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError("n_bins: 0 / None, or a power of two in 64 .. 4096")
+        if not -2 ** 31 <= int(n) < 2 ** 31:
+            raise ValueError("n_bins: 0 / None, or a power of two in 64 .. 4096")
+        _lib.check(_lib.lib().rd_wb_set_spectrum(self._h, int(n)))
+        self._spectrum_bins = int(n)
+
+    def spectrum(self) -> "Spectrum":
+        """Power spectrum of the chunk the last ``fetch()`` returned - later chunks may be in flight: Welch's method over
+        the chunk's ``chunk_samples // n_bins`` whole windows of ``n_bins`` samples (periodic Hann, no overlap, the
+        samples left over at the chunk's end unused), float32 per window, float64 across windows, scaled so that a
+        full-scale complex tone on a bin centre reads 1.0 (0 dBFS); bit-identical from run to run.  RuntimeError before
+        any fetch and when the spectrum was off for that chunk."""
+        n = self._fetched_bins or 64                     # (the record's size: the setting when its chunk was fetched)
+        power = np.empty(n, np.float64)
+        info = _lib.RdSpectrumInfo()
+        _lib.check(_lib.lib().rd_wb_spectrum(self._h, power.ctypes.data, n, C.byref(info)))
+        return Spectrum(power, spectrum_freqs(self.centre_hz, self.wide_rate, n), int(info.segments), int(info.chunk))
+
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel
         plan (a pending or earlier ``retune`` is dropped) and the constructed gain (``set_gain`` likewise)."""
         _lib.check(_lib.lib().rd_wideband_reset(self._h))
+        self._fetched_bins = 0
         self.shift_hz = self._plan_shift_hz.copy()
 
     def channelized(self) -> np.ndarray:
