@@ -479,6 +479,50 @@ typedef struct rd_spectrum_info {
 } rd_spectrum_info;
 int rd_wb_set_spectrum(rd_wideband *w, int n_bins);
 int rd_wb_spectrum(rd_wideband *w, double *power, int n_bins, rd_spectrum_info *info);
+/* BURSTS (k_chan_bursts, rd_bursts.hip): where on each channel there is energy, and at which frequency - from bursts the
+ * demodulator cannot decode, e.g. because the receiver's reference is further off than the +-4.8 kHz deviation
+ * (rtldavis_amd/acquire.py turns the records into one retune).  With bursts on, every chunk carries one more launch behind
+ * its channelizer.  All quantities are exact integers.  Channel c, the 2 * block_size bytes b of its channelized chunk,
+ * aI[t] = 2 b[2t] - 255, aQ[t] = 2 b[2t+1] - 255, z = aI + j aQ; windows of 128 outputs, nW = block_size / 128; window w:
+ *   p_w = sum |z[t]|^2 over its 128 outputs
+ *   r_w = sum z[t] conj(z[t-1]) over the 127 pairs inside it (nothing crosses a window or a chunk: no state)
+ *   ON when p_w >= thr[c]; the default thr[c] = 0xFFFFFFFF leaves every window OFF (p_w <= 16646400)
+ * A burst is a maximal run of consecutive ON windows inside the chunk: one rd_burst per run, a channel's in ascending
+ * `first`, the channels in ascending order; the OFF windows are summed in the channel's rd_burst_floor (the noise floor,
+ * and the correlation the channel filter gives noise - what an estimator subtracts).  The same chunk and thresholds give
+ * the same bits on every run.
+ * rd_wb_set_bursts: on / off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE otherwise), like
+ * rd_wb_set_levels; RD_ERR_ARG when switched on with nW > 4096.  No device work (safe before fork).
+ * rd_wb_set_burst_threshold: thr[c] for channel c (n = n_channels, else RD_ERR_ARG and nothing changes) from the next
+ * submitted chunk on, exactly at that boundary.  Host bookkeeping only, like rd_wb_set_gain: legal with two chunks in
+ * flight; calls before that submit collapse into the last.  The table in force for a chunk is echoed in its floor
+ * records.  rd_wideband_reset returns to the default table.  rd_wb_burst_thresholds: what the next submitted chunk will use.
+ * rd_wb_bursts: the records of the chunk the last fetch returned, kept by that fetch - valid with later chunks in flight,
+ * until the next fetch.  *n = the number of records; with cap < *n: RD_ERR_CAPACITY, nothing is lost, call again (out may
+ * be NULL with cap = 0).  floor: NULL, or room for n_floor = n_channels records.  RD_ERR_STATE before any fetch and when
+ * that chunk was submitted with bursts off. */
+typedef struct rd_burst {
+    int32_t  channel;
+    uint32_t first;          /* first window of the run */
+    uint32_t windows;        /* length of the run in windows */
+    uint32_t flags;          /* bit 0: first == 0; bit 1: the run ends at window nW-1 */
+    uint64_t power;          /* sum of p_w over the run */
+    uint32_t peak;           /* max p_w over the run */
+    uint32_t pad;
+    int64_t  corr_re, corr_im;   /* sum of r_w over the run */
+} rd_burst;
+typedef struct rd_burst_floor {      /* one per channel */
+    uint32_t threshold;      /* thr[c] in force for this chunk */
+    uint32_t windows_off;
+    uint32_t n_bursts;
+    uint32_t chunk;          /* the chunk's sequence number since create / reset, its low 32 bits */
+    uint64_t power_off;      /* sum of p_w over the off-windows */
+    int64_t  corr_re_off, corr_im_off;
+} rd_burst_floor;
+int rd_wb_set_bursts(rd_wideband *w, int enabled);
+int rd_wb_set_burst_threshold(rd_wideband *w, const uint32_t *thr, int n);
+int rd_wb_burst_thresholds(rd_wideband *w, uint32_t *thr, int n);
+int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor *floor, int n_floor);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

@@ -62,6 +62,17 @@ class RdSpectrumInfo(C.Structure):
     _fields_ = [("chunk", C.c_uint64), ("segments", C.c_uint32), ("n_bins", C.c_uint32)]
 
 
+class RdBurst(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("first", C.c_uint32), ("windows", C.c_uint32), ("flags", C.c_uint32),
+                ("power", C.c_uint64), ("peak", C.c_uint32), ("pad", C.c_uint32), ("corr_re", C.c_int64),
+                ("corr_im", C.c_int64)]
+
+
+class RdBurstFloor(C.Structure):
+    _fields_ = [("threshold", C.c_uint32), ("windows_off", C.c_uint32), ("n_bursts", C.c_uint32), ("chunk", C.c_uint32),
+                ("power_off", C.c_uint64), ("corr_re_off", C.c_int64), ("corr_im_off", C.c_int64)]
+
+
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
 # (code 3 is unassigned and there is no "f32": float32 I/Q is "cf32", code 4)
 RD_IQ_U8, RD_IQ_S8, RD_IQ_S16, RD_IQ_CF32 = 0, 1, 2, 4
@@ -181,6 +192,10 @@ SIGNATURES = {
     "rd_wb_levels": (C.c_int, [_P, _P, C.c_int, C.POINTER(RdInputLevel)]),
     "rd_wb_set_spectrum": (C.c_int, [_P, C.c_int]),
     "rd_wb_spectrum": (C.c_int, [_P, _P, C.c_int, C.POINTER(RdSpectrumInfo)]),
+    "rd_wb_set_bursts": (C.c_int, [_P, C.c_int]),
+    "rd_wb_set_burst_threshold": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_burst_thresholds": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_bursts": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),

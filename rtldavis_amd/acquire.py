@@ -1,0 +1,168 @@
+"""Coarse frequency acquisition for ``wideband.WidebandReceiver``: the host policy on top of the device mechanism.
+
+``retune`` learns from ``parsed()``: from messages that already passed the CRC.  A receiver whose reference is further
+off than the +-4.8 kHz deviation decodes nothing and never gets such a number.  The energy of the bursts it cannot decode
+still carries their carrier frequency: the receiver finds them in every chunk (``set_bursts`` / ``bursts()``), and what to
+do with them is decided here, between chunks, as ``agc.GainControl`` decides the gains::
+
+    rx.set_parse(True)
+    rx.set_bursts(True)
+    acq = Acquisition(rx.n_channels, rx.cfg)
+    ...
+    packets = rx.fetch()
+    b = rx.bursts()
+    rx.set_burst_threshold(acq.thresholds(b.floor))
+    new = acq.update(b, rx.parsed(), rx.submitted)
+    if new is not None:
+        rx.retune(new)
+
+Pure Python on the records' exact integers: the same records give the same decisions, on any machine; nothing here
+touches a device.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+WINDOW = 128                 # outputs per window of a burst record (wideband.BURST_WINDOW)
+THRESHOLD_OFF = 2 ** 32 - 1  # wideband.BURST_THRESHOLD_OFF
+FLAG_FIRST, FLAG_LAST = 1, 2
+
+
+def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
+    """The mean frequency of one burst record relative to the channel centre tuned at present, in Hz - what ``retune``
+    adds.  ``R = (corr_re + j corr_im) - windows * (corr_off / windows_off)`` takes off what the channel's own noise
+    contributes to the correlation (the channel filter colours it; no correction when the chunk has no OFF window), and
+    ``angle(R) * out_rate / 2 pi`` is the frequency of the channelized samples, which carry the channel at ``if_hz``
+    (``WidebandReceiver.if_hz``).  Unambiguous within +-out_rate / 2 of the channelized band's centre."""
+    r = complex(int(rec["corr_re"]), int(rec["corr_im"]))
+    n_off = int(floor_row["windows_off"])
+    if n_off:
+        r -= int(rec["windows"]) * complex(int(floor_row["corr_re_off"]), int(floor_row["corr_im_off"])) / n_off
+    return math.atan2(r.imag, r.real) * float(out_rate) / (2.0 * math.pi) - float(if_hz)
+
+
+def merge(tail, bursts) -> Tuple[np.ndarray, np.ndarray]:
+    """Join the runs a chunk boundary cut.  ``tail``: the records of the chunk before that end with it (flag bit 1), or
+    None; ``bursts``: the next chunk's records.  Returns ``(complete, new_tail)``: ``new_tail`` are the runs that end with
+    this chunk - they may go on - and ``complete`` all others, a run of ``tail`` joined with the run that begins this
+    chunk on the same channel (the sums add, ``peak`` is the larger, ``first`` and flag bit 0 are the earlier half's) or,
+    when there is none, as it was."""
+    recs = np.asarray(getattr(bursts, "records", bursts))
+    out = recs.copy()
+    heads = {int(r["channel"]): i for i, r in enumerate(out) if int(r["flags"]) & FLAG_FIRST}
+    alone = []
+    for t in ([] if tail is None else tail):
+        i = heads.get(int(t["channel"]))
+        if i is None:
+            alone.append(t)
+            continue
+        r = out[i]
+        for f in ("windows", "power", "corr_re", "corr_im"):
+            r[f] += t[f]
+        r["peak"] = max(int(r["peak"]), int(t["peak"]))
+        r["first"] = t["first"]
+        r["flags"] = (int(r["flags"]) & FLAG_LAST) | (int(t["flags"]) & FLAG_FIRST)
+    goes_on = (out["flags"] & FLAG_LAST) != 0
+    complete = out[~goes_on]
+    if alone:
+        complete = np.concatenate([np.asarray(alone, dtype=out.dtype), complete])
+    return complete, out[goes_on]
+
+
+class Acquisition:
+    """One frequency offset for all channels - a wrong reference moves every channel alike - found from bursts that
+    bring no message.
+
+    ``thresholds(floor)``: per channel ``factor * power_off // windows_off``, ``factor`` times the mean energy of the
+    windows that were OFF; a channel without an OFF window keeps its value.  With the default table every window is OFF,
+    so the first chunk measures the floor.
+
+    ``update(bursts, parsed_rows, submitted)`` takes one fetched chunk: its ``bursts()``, its ``parsed()`` rows and
+    ``WidebandReceiver.submitted`` at that moment.  It returns None, or the offset to ``retune`` to before the next
+    submit: one integer, relative to the constructed plan like every ``retune`` argument.
+
+    - A run is a candidate when it is complete (``merge``: a run that ends with its chunk waits for the next one) and
+      ``min_windows <= windows <= max_windows``: a packet lasts ``packet_symbols * symbol_length`` outputs plus its lead-in,
+      so anything shorter is a fragment or a spike and anything over twice that is no single packet.
+    - A candidate waits one chunk before it counts as an estimate: the message of a burst is reported with the chunk in
+      which the packet ends, which may be the next, and a burst the receiver decodes needs no acquisition.
+    - Chunks submitted before the last proposed retune took effect are ignored: their estimates refer to the old tuning.
+    - After ``need`` estimates the proposal is ``offset + median`` of them, rounded; the estimates start anew.
+    - Once a CRC-valid message arrives, on any channel, the receiver is within reach of the AFC (``parsed()`` ->
+      ``retune``): ``locked`` is set, the candidates and estimates are dropped - that channel's own burst among them - and
+      nothing is proposed any more, until ``reset()``.
+    """
+
+    def __init__(self, n_channels: int, cfg, factor: int = 4, need: int = 3, min_windows: Optional[int] = None,
+                 max_windows: Optional[int] = None, if_hz: Optional[int] = None) -> None:
+        if int(n_channels) < 1 or int(factor) < 1 or int(need) < 1:
+            raise ValueError("n_channels, factor and need must be positive")
+        self.n_channels = int(n_channels)
+        self.out_rate = int(cfg.bit_rate) * int(cfg.symbol_length)
+        self.if_hz = -self.out_rate // 4 if if_hz is None else int(if_hz)     # (channelizer.plan_channels' default)
+        self.factor = int(factor)
+        self.need = int(need)
+        self.min_windows = int(cfg.packet_symbols) * int(cfg.symbol_length) // WINDOW if min_windows is None else int(min_windows)
+        self.max_windows = 2 * self.min_windows + 2 if max_windows is None else int(max_windows)
+        if not 1 <= self.min_windows <= self.max_windows:
+            raise ValueError("1 <= min_windows <= max_windows")
+        self.reset()
+
+    def reset(self) -> None:
+        """Back to the state after construction: offset 0, no estimates, not locked, the default thresholds."""
+        self.offset = 0                  # the offset last proposed
+        self.valid_from = 0              # the first chunk that offset holds for
+        self.locked = False
+        self.estimates: List[float] = []
+        self._thr = np.full(self.n_channels, THRESHOLD_OFF, np.uint64)
+        self._forget()
+
+    def _forget(self) -> None:
+        self._chunk = None               # the chunk of the last update
+        self._tail = None                # its runs that may go on
+        self._waiting: List[Tuple[int, float]] = []   # its candidates (channel, Hz)
+
+    def thresholds(self, floor) -> np.ndarray:
+        """uint32 per channel for ``set_burst_threshold``, from one chunk's floor records."""
+        floor = np.asarray(getattr(floor, "floor", floor))
+        if floor.shape != (self.n_channels,):
+            raise ValueError(f"{floor.size} floor records for {self.n_channels} channels")
+        n_off = floor["windows_off"].astype(np.uint64)
+        some = n_off > 0
+        self._thr[some] = np.minimum(self.factor * floor["power_off"][some].astype(np.uint64) // n_off[some], THRESHOLD_OFF)
+        return self._thr.astype(np.uint32)
+
+    def candidates(self, bursts) -> List[Tuple[int, float]]:
+        """``(channel, offset in Hz)`` of the chunk's complete runs of plausible length; keeps the runs that may go on
+        for the next chunk (a gap in the chunk numbers drops the ones kept before)."""
+        k = int(bursts.chunk)
+        tail = self._tail if self._chunk is not None and k == self._chunk + 1 else None
+        complete, self._tail = merge(tail, bursts.records)
+        return [(int(r["channel"]), burst_offset_hz(r, bursts.floor[int(r["channel"])], self.out_rate, self.if_hz))
+                for r in complete if self.min_windows <= int(r["windows"]) <= self.max_windows]
+
+    def update(self, bursts, parsed_rows, submitted: int) -> Optional[int]:
+        k = int(bursts.chunk)
+        if len(parsed_rows):
+            self.locked = True
+        if self.locked:
+            self.estimates = []
+            self._forget()
+            return None
+        if k < self.valid_from:
+            self._forget()
+            return None
+        if self._chunk is not None and k == self._chunk + 1:
+            self.estimates += [hz for _, hz in self._waiting]
+        self._waiting = self.candidates(bursts)
+        self._chunk = k
+        if len(self.estimates) < self.need:
+            return None
+        self.offset += int(round(float(np.median(self.estimates))))
+        self.valid_from = int(submitted)
+        self.estimates = []
+        self._forget()
+        return self.offset

@@ -241,6 +241,21 @@ int rd_spec_check(int n_bins, size_t n_samples);
 int rd_spec_prepare(rd_spec **sp, int n_bins, size_t n_samples, hipStream_t st);
 int rd_spec_launch(rd_spec *sp, const uint8_t *wide, int fmt, size_t n_samples, uint64_t seq, void *out, hipStream_t st);
 void rd_spec_destroy(rd_spec *sp);
+// Bursts of a channelized chunk (rd_bursts.hip: k_chan_bursts; the definition: include/rtldavis_hip.h, BURSTS).
+// rd_bursts_check: the argument rule for a chunk of n_out outputs per channel (RD_ERR_ARG with a message, no device work).
+// rd_bursts_launch: one launch on st over chan_out (channel c at chan_out + c * out_stride, 2 n_out bytes each, 16-byte
+// aligned); slot: a device address (mapped host memory) of rd_bu_slot_bytes laid out as
+//   [n_ch][cap] rd_burst | [n_ch] rd_burst_floor | [n_ch] uint32 thresholds           cap = rd_bu_cap(n_win)
+// The caller writes the thresholds before the launch; the kernel writes the floor records and, per channel, the first
+// floor.n_bursts of its cap record places.
+#define RD_BU_WINDOW 128
+#define RD_BU_MAX_WINDOWS 4096
+static inline size_t rd_bu_cap(size_t n_win) { return (n_win + 1) / 2; }
+static inline size_t rd_bu_floor_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst); }
+static inline size_t rd_bu_thr_offset(int n_ch, size_t n_win) { return rd_bu_floor_offset(n_ch, n_win) + (size_t)n_ch * sizeof(rd_burst_floor); }
+static inline size_t rd_bu_slot_bytes(int n_ch, size_t n_win) { return rd_bu_thr_offset(n_ch, n_win) + (size_t)n_ch * sizeof(uint32_t); }
+int rd_bursts_check(size_t n_out);
+int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_t n_out, uint64_t seq, void *slot, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

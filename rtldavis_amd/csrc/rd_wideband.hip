@@ -35,6 +35,13 @@
 // the level records.  Both kernels READ d_wide[s] after the chunk's channelizer: that buffer is next overwritten by the
 // copy of chunk k+2, which waits for e_chan of chunk k+1 - recorded later on the compute stream than either kernel of
 // chunk k, so the copy cannot overtake them although they come behind chunk k's own e_chan.
+// Bursts (rd_wb_set_bursts / rd_wb_bursts; rd_bursts.hip): with bursts on, k_chan_bursts is queued in the same place and
+// writes its records into a mapped pinned slot of the chunk's parity, which the fetch copies out.  It reads d_out[s], the
+// chunk's channelized bytes, like the chunk's demodulator launch behind it: d_out[s] is next written by the channelizer of
+// chunk k+2, later on the same stream.  Its thresholds (rd_wb_set_burst_threshold: recorded by the call, in force from the
+// next submit, like the gains) need no copy and no device table: the submit writes the table into the slot itself, which
+// is free by the argument for the level slot, and the kernel reads it there - host writes made before the launch are
+// visible to it - and echoes what it used in the floor records.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -94,7 +101,15 @@ struct rd_wideband {
     uint8_t *h_sp[2] = {nullptr, nullptr};
     rd_spectrum_info sp_info_last = {};
     std::vector<double> sp_last;
+    // bursts: on / off (switched on a quiet receiver like levels), the thresholds the next submitted chunk will use, the
+    // mapped pinned slots per parity (rd_internal.h: rd_bu_slot_bytes) and the records the last fetch kept
+    bool bursts = false, last_bursts = false;
+    std::vector<uint32_t> thr;
+    uint8_t *h_bu[2] = {nullptr, nullptr};
+    std::vector<rd_burst> bu_last;
+    std::vector<rd_burst_floor> bf_last;
 };
+#define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
 static_assert(sizeof(rd_spectrum_info) == RD_SPEC_HDR_BYTES, "the slot's header is rd_spectrum_info");
 
@@ -158,6 +173,7 @@ extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg
     w->phase.assign(w->n_ch, 0);
     w->gain0 = (float)ccfg->gain;
     w->gain.assign(w->n_ch, w->gain0);
+    w->thr.assign(w->n_ch, RD_BU_THR_DEFAULT);
     *out = w;
     return RD_OK;
 }
@@ -172,6 +188,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             if (w->e_chan[i]) hipEventDestroy(w->e_chan[i]);
             hipHostFree(w->h_lv[i]);
             hipHostFree(w->h_sp[i]);
+            hipHostFree(w->h_bu[i]);
         }
         hipFree(w->d_lvacc);
     }
@@ -236,6 +253,20 @@ static int wb_alloc_spectrum(rd_wideband *w) {
     return RD_OK;
 }
 
+// the burst records' slots, when bursts are first wanted
+static size_t wb_bu_windows(const rd_wideband *w) { return w->B / RD_BU_WINDOW; }
+static rd_burst_floor *wb_bu_floor(const rd_wideband *w, int i) {
+    return (rd_burst_floor *)(w->h_bu[i] + rd_bu_floor_offset(w->n_ch, wb_bu_windows(w)));
+}
+static int wb_alloc_bursts(rd_wideband *w) {
+    for (int i = 0; i < 2; i++)
+        if (!w->h_bu[i]) {
+            WCHK(hipHostMalloc((void **)&w->h_bu[i], rd_bu_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
+            memset(wb_bu_floor(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_burst_floor));   // (a run count no chunk can have)
+        }
+    return RD_OK;
+}
+
 extern "C" int rd_wideband_reset(rd_wideband *w) {
     if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
     int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
@@ -254,6 +285,10 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->last_spec = false;         // (the setting stays; the record of the run before goes)
     for (int i = 0; i < 2; i++)
         if (w->h_sp[i]) memset(w->h_sp[i], 0xFF, RD_SPEC_HDR_BYTES);
+    w->thr.assign(w->n_ch, RD_BU_THR_DEFAULT);   // a pending threshold change is dropped
+    w->last_bursts = false;
+    for (int i = 0; i < 2; i++)
+        if (w->h_bu[i]) memset(wb_bu_floor(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_burst_floor));
     return RD_OK;
 }
 
@@ -313,6 +348,45 @@ extern "C" int rd_wb_spectrum(rd_wideband *w, double *power, int n_bins, rd_spec
     return RD_OK;
 }
 
+extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before bursts are switched", rd_demod_inflight(w->dem));
+    if (enabled) {
+        int rc = rd_bursts_check(w->B);
+        if (rc) return rc;
+    }
+    w->bursts = enabled != 0;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_threshold(rd_wideband *w, const uint32_t *thr, int n) {
+    if (!w || !thr) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d thresholds for %d channels", n, w->n_ch);
+    w->thr.assign(thr, thr + n);
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_thresholds(rd_wideband *w, uint32_t *thr, int n) {
+    if (!w || !thr) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d channels of %d", n, w->n_ch);
+    memcpy(thr, w->thr.data(), (size_t)n * sizeof(uint32_t));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor *floor, int n_floor) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (floor && n_floor != w->n_ch)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d floor records of %d", n_floor, w->n_ch);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_bursts) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with bursts off (rd_wb_set_bursts)");
+    *n = (int)w->bu_last.size();
+    if (floor) memcpy(floor, w->bf_last.data(), (size_t)w->n_ch * sizeof(rd_burst_floor));
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d burst records, room for %d", *n, cap);
+    if (*n) memcpy(out, w->bu_last.data(), (size_t)*n * sizeof(rd_burst));
+    return RD_OK;
+}
+
 extern "C" int rd_wb_retune(rd_wideband *w, const int64_t *shift_hz, int n) {
     if (!w || !shift_hz) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d shifts for %d channels", n, w->n_ch);
@@ -342,6 +416,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (rc) return rc;
     if (w->levels && (rc = wb_alloc_levels(w))) return rc;
     if (w->spec_n && (rc = wb_alloc_spectrum(w))) return rc;
+    if (w->bursts && (rc = wb_alloc_bursts(w))) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
     const int s = (int)(w->n_sub & 1);
@@ -379,6 +454,14 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                             (uint64_t)w->n_sub, sp, w->st);
         if (rc) return rc;
     }
+    if (w->bursts) {
+        // burst slot s: free by the argument for the level slot; the thresholds travel in it (header comment)
+        memcpy(w->h_bu[s] + rd_bu_thr_offset(w->n_ch, wb_bu_windows(w)), w->thr.data(), (size_t)w->n_ch * sizeof(uint32_t));
+        void *bu = nullptr;
+        WCHK(hipHostGetDevicePointer(&bu, w->h_bu[s], 0));
+        rc = rd_bursts_launch(w->d_out[s], 2 * w->B, w->n_ch, w->B, (uint64_t)w->n_sub, bu, w->st);
+        if (rc) return rc;
+    }
     w->clock += w->B;
     w->n_sub++;
     return rd_demod_submit_device(w->dem, w->d_out[s]);
@@ -389,6 +472,23 @@ static int wb_fetched(rd_wideband *w, int rc) {
     w->last = w->n_sub - 1 - rd_demod_pending(w->dem);  // (the oldest in flight)
     w->last_levels = false;
     w->last_spec = false;
+    w->last_bursts = false;
+    if (w->bursts) {
+        // as the level records below: k_chan_bursts ran before the demodulator launch that has reported.  Every floor
+        // record carries the chunk's number; a channel's runs are the first n_bursts of its record places.
+        const size_t cap_c = rd_bu_cap(wb_bu_windows(w));
+        const rd_burst *recs = (const rd_burst *)w->h_bu[w->last & 1];
+        const rd_burst_floor *fl = wb_bu_floor(w, (int)(w->last & 1));
+        w->bf_last.assign(fl, fl + w->n_ch);
+        w->bu_last.clear();
+        for (int c = 0; c < w->n_ch; c++) {
+            if (w->bf_last[c].chunk != (uint32_t)w->last || w->bf_last[c].n_bursts > cap_c)
+                return rd_fail_msg(RD_ERR_DEVICE, "burst floor record of channel %d belongs to chunk %u (%u runs), not %ld", c,
+                                   w->bf_last[c].chunk, w->bf_last[c].n_bursts, w->last);
+            w->bu_last.insert(w->bu_last.end(), recs + (size_t)c * cap_c, recs + (size_t)c * cap_c + w->bf_last[c].n_bursts);
+        }
+        w->last_bursts = true;
+    }
     if (w->spec_n) {
         // as the level records below: k_chan_spectrum ran before the demodulator launch that has reported
         const uint8_t *slot = w->h_sp[w->last & 1];

@@ -44,6 +44,26 @@ class Levels(NamedTuple):
     chunk: int
 
 
+# bursts(): one row per run of ON windows / one row per channel - the layouts of rd_burst and rd_burst_floor
+BURST_DTYPE = np.dtype([("channel", np.int32), ("first", np.uint32), ("windows", np.uint32), ("flags", np.uint32),
+                        ("power", np.uint64), ("peak", np.uint32), ("pad", np.uint32), ("corr_re", np.int64),
+                        ("corr_im", np.int64)])
+BURST_FLOOR_DTYPE = np.dtype([("threshold", np.uint32), ("windows_off", np.uint32), ("n_bursts", np.uint32),
+                              ("chunk", np.uint32), ("power_off", np.uint64), ("corr_re_off", np.int64),
+                              ("corr_im_off", np.int64)])
+BURST_WINDOW = 128                     # outputs per window
+BURST_THRESHOLD_OFF = 2 ** 32 - 1      # the default threshold: no window's energy reaches it
+
+
+class Bursts(NamedTuple):
+    """``WidebandReceiver.bursts()``: ``records`` (structured array of ``BURST_DTYPE``, one row per run of ON windows,
+    channels ascending, a channel's runs in ascending ``first``), ``floor`` (``BURST_FLOOR_DTYPE``, one row per channel:
+    the OFF windows and the threshold in force) and ``chunk``, the chunk's number since construction / ``reset()``."""
+    records: np.ndarray
+    floor: np.ndarray
+    chunk: int
+
+
 class Spectrum(NamedTuple):
     """``WidebandReceiver.spectrum()`` / ``Channelizer.spectrum()``: ``power`` (float64 [n_bins], ascending frequency,
     1.0 = a full-scale complex tone on a bin centre), ``freqs_hz`` (float64 [n_bins], the bins' absolute RF centres:
@@ -95,6 +115,8 @@ class WidebandReceiver:
         _lib.check(_lib.lib().rd_wb_create_fmt(C.byref(_cfg_struct(cfg)), C.byref(chan_config(self)), self._fmt,
                                                self.taps.ctypes.data, self.shift_hz.ctypes.data, C.byref(self._h)))
         self._spectrum_bins = self._fetched_bins = 0                # set_spectrum(); the setting at the last fetch
+        self._submitted = 0
+        self._burst_cap = 64
         self._cap = 64 * max(1, self.n_channels)
         self._recs = (_lib.RdPacket * self._cap)()
 
@@ -125,6 +147,13 @@ class WidebandReceiver:
         """Queue one chunk (asynchronous copy, channelizer and demodulator; at most two chunks in flight)."""
         a = self._check_chunk(chunk)
         _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.nbytes))
+        self._submitted += 1
+
+    @property
+    def submitted(self) -> int:
+        """Chunks submitted since construction / ``reset()``: the number the next submitted chunk will carry, i.e. the
+        chunk from which a ``retune``, ``set_gain`` or ``set_burst_threshold`` made now holds."""
+        return self._submitted
 
     def fetch(self) -> List[List[Packet]]:
         """Packets of the oldest chunk in flight, one list per channel."""
@@ -139,7 +168,7 @@ class WidebandReceiver:
         a = self._check_chunk(chunk)
         if self.inflight:
             raise RuntimeError(f"{self.inflight} chunk(s) in flight: fetch them first")
-        _lib.check(_lib.lib().rd_wideband_submit(self._h, a.ctypes.data, a.nbytes))
+        self.submit(a)
         return self.fetch()
 
     @property
@@ -250,11 +279,61 @@ class WidebandReceiver:
         _lib.check(_lib.lib().rd_wb_spectrum(self._h, power.ctypes.data, n, C.byref(info)))
         return Spectrum(power, spectrum_freqs(self.centre_hz, self.wide_rate, n), int(info.segments), int(info.chunk))
 
+    def set_bursts(self, on: bool = True) -> None:
+        """From the next chunk on, look for bursts in every channel's channelized chunk on the device (one more kernel
+        behind its channelizer); ``bursts()`` returns the records.  Needs a receiver with nothing in flight
+        (RuntimeError); ValueError when ``block_size`` exceeds 4096 windows of 128 outputs.  Off (the default): nothing is
+        launched."""
+        _lib.check(_lib.lib().rd_wb_set_bursts(self._h, 1 if on else 0))
+
+    def set_burst_threshold(self, thr) -> None:
+        """From the next submitted chunk on, a window of channel c is ON when its energy reaches ``thr[c]``: one integer
+        for all channels or one per channel, ``0 .. 2**32 - 1`` (the default, ``BURST_THRESHOLD_OFF``: never).  Takes
+        effect exactly at that chunk boundary and is legal with chunks in flight; the table in force is echoed in
+        ``bursts().floor["threshold"]``; ``reset()`` returns to the default.  ValueError for a wrong length or value."""
+        t = np.asarray(thr)
+        if t.dtype.kind not in "iu" or t.ndim > 1 or (t.ndim == 1 and t.size != self.n_channels):
+            raise ValueError(f"thr: one integer or {self.n_channels} of them")
+        if t.size and (int(t.min()) < 0 or int(t.max()) > BURST_THRESHOLD_OFF):
+            raise ValueError("every threshold must lie in 0 .. 2**32 - 1")
+        t = np.ascontiguousarray(np.broadcast_to(t, (self.n_channels,)), np.uint32)
+        _lib.check(_lib.lib().rd_wb_set_burst_threshold(self._h, t.ctypes.data, t.size))
+
+    def burst_thresholds(self) -> np.ndarray:
+        """uint32 per channel: the thresholds the next submitted chunk will use."""
+        t = np.empty(self.n_channels, np.uint32)
+        _lib.check(_lib.lib().rd_wb_burst_thresholds(self._h, t.ctypes.data, t.size))
+        return t
+
+    def bursts(self) -> "Bursts":
+        """Bursts of the chunk the last ``fetch()`` returned - later chunks may be in flight - as exact integers.  Per
+        channel, over windows of 128 outputs of its channelized chunk (z = aI + j aQ, a = 2 b - 255): the window's energy
+        ``p = sum |z|^2`` and lag-1 correlation ``r = sum z[t] conj(z[t-1])`` over the 127 pairs inside it.  A record is a
+        maximal run of windows with ``p >= threshold``: ``channel``, ``first``, ``windows``, ``flags`` (bit 0: the run
+        begins with the chunk, bit 1: it ends with it - ``acquire.merge`` joins the halves), ``power`` = sum p, ``peak`` =
+        max p, ``corr_re`` / ``corr_im`` = sum r.  ``floor``: per channel the same sums over the other windows
+        (``windows_off``, ``power_off``, ``corr_re_off``, ``corr_im_off``), the ``threshold`` in force and ``n_bursts``.
+        ``acquire.burst_offset_hz`` turns a record into a frequency.  RuntimeError before any fetch and when bursts were
+        off for that chunk."""
+        L = _lib.lib()
+        floor = np.empty(self.n_channels, BURST_FLOOR_DTYPE)
+        n = C.c_int(0)
+        recs = np.empty(self._burst_cap, BURST_DTYPE)
+        rc = L.rd_wb_bursts(self._h, recs.ctypes.data, recs.size, C.byref(n), floor.ctypes.data, floor.size)
+        if rc == _lib.RD_ERR_CAPACITY:  # nothing is lost: the handle keeps the records
+            self._burst_cap = max(2 * self._burst_cap, n.value)
+            recs = np.empty(self._burst_cap, BURST_DTYPE)
+            rc = L.rd_wb_bursts(self._h, recs.ctypes.data, recs.size, C.byref(n), floor.ctypes.data, floor.size)
+        _lib.check(rc)
+        return Bursts(recs[: n.value].copy(), floor, int(floor["chunk"][0]))
+
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel
-        plan (a pending or earlier ``retune`` is dropped) and the constructed gain (``set_gain`` likewise)."""
+        plan (a pending or earlier ``retune`` is dropped), the constructed gain (``set_gain`` likewise) and the default
+        burst thresholds."""
         _lib.check(_lib.lib().rd_wideband_reset(self._h))
         self._fetched_bins = 0
+        self._submitted = 0
         self.shift_hz = self._plan_shift_hz.copy()
 
     def channelized(self) -> np.ndarray:

@@ -10,7 +10,7 @@ around work that ends in a fetch:
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
 
     python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
-                                    [--retune {none,one,all}] [--levels] [--json OUT]
+                                    [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -20,6 +20,10 @@ back on the plan - so every chunk carries the rebuild of those channels' tables 
 channelizer; 1 Hz keeps every burst where it was.
 --levels: level metering on (WidebandReceiver.set_levels: k_chan_levels behind every chunk's channelizer), levels() read
 after every fetch and handed to agc.GainControl.update, whose gains go into set_gain when a channel moves.
+--bursts: every repeat times two windows, burst detection off and on (WidebandReceiver.set_bursts: k_chan_bursts behind
+every chunk's channelizer; bursts() read after every fetch, its floor turned into the next thresholds and its records handed
+to acquire.Acquisition.update - a proposed retune is counted, not applied).  "Off" is the baseline of the same run; both go
+into --bursts-out (default profiles/wideband_bursts.txt).  The kernel's own time: the rocprofv3 run above.
 """
 import argparse
 import json
@@ -46,6 +50,9 @@ def main():
     ap.add_argument("--retune", default="none", choices=["none", "one", "all"],
                     help="retune one channel or all of them before every chunk")
     ap.add_argument("--levels", action="store_true", help="metering on; levels() -> GainControl.update -> set_gain per chunk")
+    ap.add_argument("--bursts", action="store_true", help="time every window with burst detection off and on; write --bursts-out")
+    ap.add_argument("--bursts-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                         "wideband_bursts.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -65,14 +72,29 @@ def main():
     n_msgs = [0]
     step = 2 * rx.chunk_samples      # array elements per chunk
     chunks = [np.ascontiguousarray(raw[step * k: step * (k + 1)]) for k in range(nk)]
+    acq, thr0, n_bursts, n_asked = None, None, [0], [0]
+    if args.bursts:
+        from rtldavis_amd import acquire
+        acq = acquire.Acquisition(rx.n_channels, cfg)
+        rx.set_bursts(True)
+        rx.demodulate(chunks[0])     # (no burst starts inside the first chunk: its floor gives the first thresholds)
+        thr0 = acq.thresholds(rx.bursts().floor)
+        rx.set_bursts(False)
     moved = np.zeros(rx.n_channels, np.int64)
     moved[[25] if args.retune == "one" else slice(None)] = 1
+
+    bursts_on = [False]
 
     def meter():
         if ctl is not None:
             g = ctl.update(rx.levels())
             if g is not None:
                 rx.set_gain(g)
+        if bursts_on[0]:
+            b = rx.bursts()
+            n_bursts[0] += len(b.records)
+            rx.set_burst_threshold(acq.thresholds(b.floor))
+            n_asked[0] += acq.update(b, rx.parsed() if args.parse else (), rx.submitted) is not None
 
     def run(n):
         """n chunks round and round through submit / fetch, two in flight; per-chunk latency and packets."""
@@ -99,11 +121,18 @@ def main():
         return time.perf_counter() - t0, np.array(lat), pk
 
     run(args.warmup)
-    runs = []
+    runs, runs_off = [], []
     for _ in range(args.repeats):
-        rx.reset()
-        n_msgs[0] = 0
-        runs.append(run(args.chunks))
+        for on in ((False, True) if args.bursts else (False,)):
+            rx.reset()
+            if args.bursts:
+                rx.set_bursts(on)
+                bursts_on[0] = on
+                acq.reset()
+                rx.set_burst_threshold(thr0)
+                n_bursts[0] = n_asked[0] = 0
+            n_msgs[0] = 0
+            (runs if on or not args.bursts else runs_off).append(run(args.chunks))
     walls = [r[0] for r in runs]
     wall, lat, pk = sorted(runs, key=lambda r: r[0])[len(runs) // 2]   # the median window
     # the first pass over the capture (chunks 0 .. nk-1 after the reset): every channel's burst where it was injected
@@ -124,8 +153,27 @@ def main():
         "realtime_factor": air / wall,
         "injected_packets": len(info), "recovered_first_pass": int(found),
         "packets_total": int(sum(len(x) for ch in pk for x in ch)),
-        "parse": bool(args.parse), "retune": args.retune, "levels": bool(args.levels),
+        "parse": bool(args.parse), "retune": args.retune, "levels": bool(args.levels), "bursts_on": bool(args.bursts),
     }
+    if args.bursts:
+        w_off, l_off, _ = sorted(runs_off, key=lambda r: r[0])[len(runs_off) // 2]
+        res["bursts"] = {"records_last_window": n_bursts[0], "retunes_proposed_last_window": n_asked[0],
+                         "off": {"wall_s": w_off, "wall_s_all": [r[0] for r in runs_off], "chunks_per_s": args.chunks / w_off,
+                                 "latency_ms_median": float(np.median(l_off) * 1e3)}}
+        lines = [
+            "WidebandReceiver burst detection (k_chan_bursts), on against off in the same run: tools/wideband_stream.py --bursts"
+            + (" --parse" if args.parse else ""),
+            f"{rx.n_channels} channels, chunks of {B} outputs ({1e3 * B / out_rate:.1f} ms air, {rx.chunk_bytes} bytes, {args.sample_format}), "
+            f"{args.chunks} chunks per window, {args.repeats} windows each, alternating; the median window is reported",
+            f"  bursts off: {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+            f"  bursts on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+            f"(bursts() read, thresholds set and Acquisition.update run per chunk)",
+            f"  all windows, wall s: off {' '.join(f'{r[0]:.3f}' for r in runs_off)}; on {' '.join(f'{w:.3f}' for w in walls)}",
+            f"  last window on: {n_bursts[0]} burst records, {n_asked[0]} retunes proposed",
+        ]
+        with open(args.bursts_out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
     if args.parse:
         import math
         res["messages_last_window"] = n_msgs[0]
