@@ -523,6 +523,58 @@ int rd_wb_set_bursts(rd_wideband *w, int enabled);
 int rd_wb_set_burst_threshold(rd_wideband *w, const uint32_t *thr, int n);
 int rd_wb_burst_thresholds(rd_wideband *w, uint32_t *thr, int n);
 int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor *floor, int n_floor);
+/* BURST DECODE (k_chan_burst_decode, rd_burst_decode.hip): the messages of the bursts above, wherever in the channel
+ * filter's pass band their carrier lies.  The demodulator slices the discriminator around 0 Hz and gets no message from a
+ * burst further off than the deviation; here every run is sliced around its OWN mean frequency - its record's correlation
+ * sum - and sync word plus CRC-16 prove a message, so one burst gives a message and a carrier estimate, and a burst of any
+ * other device gives nothing.  With decode on, every chunk carries one more launch behind k_chan_bursts.  All quantities
+ * are exact integers.  SL = symbol_length, N = packet_symbols, sync = the preamble's bits; LOOK_W = ceil((N SL + 1) / 128),
+ * LOOK = 128 LOOK_W (9 windows for SL 14, N 80), MAX_W = 32.  Channel c of chunk k: b = its channelized bytes, continued to
+ * t < 0 by chunk k-1's bytes (t + block_size); have_prev: a chunk has been submitted since create / reset; a = 2 b - 255,
+ * z[t] = aI[t] + j aQ[t], p[t] = z[t] conj(z[t-1]).  For every rd_burst of that channel and chunk:
+ *   1. windows > MAX_W: not decoded, counted in long_runs[c].    2. (corr_re, corr_im) = (0, 0): skipped.
+ *   3. region t0 = 128 first - (LOOK if (flags & 1) and have_prev else 0), t1 = 128 (first + windows); skipped when
+ *      t1 - t0 < N SL + 1.
+ *   4. d[t] = im p[t] corr_re - re p[t] corr_im for t0 < t < t1 (Im of p times the conjugate of the run's own correlation
+ *      sum); s[t] = sum_{i < SL} d[t - i] for t0 + SL <= t < t1 (|s| < 2^54); bit[t] = s[t] > 0.
+ *   5. candidate tau, the end of the first symbol: t0 + SL <= tau and tau + SL (N - 1) < t1; symbols bit[tau + SL i],
+ *      i < N; the first 16 equal sync; the N symbols, packed MSB first into N / 8 on-air bytes, pass the CRC gate of
+ *      rd_parse_packet (CRC-16-CCITT over the bit-swapped bytes [2:] is 0); and the packet ends in this chunk,
+ *      tau + SL (N - 1) >= 0 - a message is reported with the chunk in which its packet ends, as the demodulator does, so
+ *      the look-back never reports one twice.
+ *   6. at most one record per run: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
+ * Records: channels ascending, a channel's runs ascending.  The same chunks and thresholds give the same bits on every run.
+ * Not solved here: a packet of which only the last few outputs reach into a chunk whose window 0 stays OFF is missed; a run
+ * of more than 32 windows is not decoded.  A burst the demodulator decodes too is reported by both paths (rd_wb_parsed and
+ * here): the caller dedupes by channel, chunk and data.
+ * rd_wb_set_burst_decode: on / off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE otherwise),
+ * like rd_wb_set_bursts, and bursts on (RD_ERR_STATE otherwise; rd_wb_set_bursts(w, 0) switches decode off too).
+ * RD_ERR_ARG for a configuration other than preamble_symbols = 16, N a multiple of 8 in 40 .. 8 RD_BURST_MSG_BYTES,
+ * N SL + 1 <= 2048, or with block_size < LOOK.  No device work (safe before fork).
+ * rd_wb_burst_messages: the records of the chunk the last fetch returned, kept by that fetch - valid with later chunks in
+ * flight, until the next fetch.  *n = the number of records; with cap < *n: RD_ERR_CAPACITY, nothing is lost, call again
+ * (out may be NULL with cap = 0).  long_runs: NULL, or room for n_channels counts.  RD_ERR_STATE before any fetch and when
+ * that chunk was submitted with decode off. */
+#define RD_BURST_MSG_BYTES 10    /* packet_symbols / 8 at most */
+typedef struct rd_burst_msg {
+    int32_t  channel;
+    uint32_t first;          /* the run's first window (its rd_burst) */
+    int32_t  tau;            /* the end of the first symbol, relative to the chunk's first output; may be negative */
+    uint32_t flags;          /* bit 0: the region reached into the previous chunk */
+    uint64_t time;           /* the chunk's absolute output clock + tau */
+    uint64_t margin;         /* min_i |s[tau + SL i]| */
+    int64_t  f_re, f_im;     /* sum of p[t] over the packet's N SL outputs tau - SL + 1 .. tau + SL (N - 1) */
+    uint8_t  data[RD_BURST_MSG_BYTES];   /* on-air bytes, as rd_packet.data */
+    uint8_t  ones;           /* symbols that are 1 */
+    uint8_t  id;             /* transmitter id: bit-swapped data[2] & 7 */
+    uint8_t  pad[4];
+} rd_burst_msg;
+int rd_wb_set_burst_decode(rd_wideband *w, int enabled);
+int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels);
+/* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
+ * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
+ * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */
+int rd_wb_fetched_chunk(rd_wideband *w, uint64_t *chunk);
 /* test hook (quiet handle): move the output clock forward by n_out (a multiple of 128), history kept */
 int rd_wideband_debug_advance_clock(rd_wideband *w, uint64_t n_out);
 

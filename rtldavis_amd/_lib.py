@@ -73,6 +73,15 @@ class RdBurstFloor(C.Structure):
                 ("power_off", C.c_uint64), ("corr_re_off", C.c_int64), ("corr_im_off", C.c_int64)]
 
 
+RD_BURST_MSG_BYTES = 10
+
+
+class RdBurstMsg(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("first", C.c_uint32), ("tau", C.c_int32), ("flags", C.c_uint32),
+                ("time", C.c_uint64), ("margin", C.c_uint64), ("f_re", C.c_int64), ("f_im", C.c_int64),
+                ("data", C.c_uint8 * RD_BURST_MSG_BYTES), ("ones", C.c_uint8), ("id", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
 # (code 3 is unassigned and there is no "f32": float32 I/Q is "cf32", code 4)
 RD_IQ_U8, RD_IQ_S8, RD_IQ_S16, RD_IQ_CF32 = 0, 1, 2, 4
@@ -196,6 +205,9 @@ SIGNATURES = {
     "rd_wb_set_burst_threshold": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_burst_thresholds": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_bursts": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
+    "rd_wb_set_burst_decode": (C.c_int, [_P, C.c_int]),
+    "rd_wb_burst_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
+    "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
     "rd_debug_mfma_taps8": (None, [_P]),

@@ -16,6 +16,15 @@ do with them is decided here, between chunks, as ``agc.GainControl`` decides the
     if new is not None:
         rx.retune(new)
 
+With ``set_burst_decode`` the receiver also decodes every burst around the burst's own mean frequency
+(``burst_messages()``): one burst then gives a CRC-proven message and, the bits being known, a carrier estimate without
+the payload's 0/1 imbalance in it (``burst_message_offset_hz``).  Handed to ``update`` as ``messages``, one such row is
+enough for a proposal - no ``need``, no waiting chunk, and a burst of any other device never enters::
+
+    rx.set_burst_decode(True)
+    ...
+    new = acq.update(b, rx.parsed(), rx.submitted, rx.burst_messages())
+
 Pure Python on the records' exact integers: the same records give the same decisions, on any machine; nothing here
 touches a device.
 """
@@ -42,6 +51,15 @@ def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
     if n_off:
         r -= int(rec["windows"]) * complex(int(floor_row["corr_re_off"]), int(floor_row["corr_im_off"])) / n_off
     return math.atan2(r.imag, r.real) * float(out_rate) / (2.0 * math.pi) - float(if_hz)
+
+
+def burst_message_offset_hz(row, out_rate: int, if_hz: int, deviation_hz: float = 4800.0, packet_symbols: int = 80) -> float:
+    """The carrier of one decoded burst (a row of ``burst_messages().records``) relative to the channel centre tuned at
+    present, in Hz.  ``angle(f_re + j f_im) * out_rate / 2 pi`` is the mean frequency of the packet's samples, which
+    carry the channel at ``if_hz``; a packet with ``ones`` 1 symbols of ``packet_symbols`` lies
+    ``deviation_hz * (2 ones - packet_symbols) / packet_symbols`` above its carrier on average, and the bits are known."""
+    f = math.atan2(int(row["f_im"]), int(row["f_re"])) * float(out_rate) / (2.0 * math.pi) - float(if_hz)
+    return f - float(deviation_hz) * (2 * int(row["ones"]) - int(packet_symbols)) / float(packet_symbols)
 
 
 def merge(tail, bursts) -> Tuple[np.ndarray, np.ndarray]:
@@ -91,6 +109,11 @@ class Acquisition:
       which the packet ends, which may be the next, and a burst the receiver decodes needs no acquisition.
     - Chunks submitted before the last proposed retune took effect are ignored: their estimates refer to the old tuning.
     - After ``need`` estimates the proposal is ``offset + median`` of them, rounded; the estimates start anew.
+    - With ``messages`` (``burst_messages()`` of the same chunk - a ``BurstMessages`` of another chunk is a ValueError;
+      optional - without it everything is as above): while not
+      locked, a chunk ``>= valid_from`` that brings rows is proposed from at once, ``offset + round(median of
+      burst_message_offset_hz over its rows)``; the CRC is the proof, so there is no ``need`` and no waiting chunk.
+      ``valid_from`` becomes ``submitted``, candidates and estimates are forgotten.
     - Once a CRC-valid message arrives, on any channel, the receiver is within reach of the AFC (``parsed()`` ->
       ``retune``): ``locked`` is set, the candidates and estimates are dropped - that channel's own burst among them - and
       nothing is proposed any more, until ``reset()``.
@@ -102,6 +125,8 @@ class Acquisition:
             raise ValueError("n_channels, factor and need must be positive")
         self.n_channels = int(n_channels)
         self.out_rate = int(cfg.bit_rate) * int(cfg.symbol_length)
+        self.packet_symbols = int(cfg.packet_symbols)
+        self.deviation_hz = 4800.0                                           # the Davis link's (synth.py)
         self.if_hz = -self.out_rate // 4 if if_hz is None else int(if_hz)     # (channelizer.plan_channels' default)
         self.factor = int(factor)
         self.need = int(need)
@@ -144,8 +169,10 @@ class Acquisition:
         return [(int(r["channel"]), burst_offset_hz(r, bursts.floor[int(r["channel"])], self.out_rate, self.if_hz))
                 for r in complete if self.min_windows <= int(r["windows"]) <= self.max_windows]
 
-    def update(self, bursts, parsed_rows, submitted: int) -> Optional[int]:
+    def update(self, bursts, parsed_rows, submitted: int, messages=None) -> Optional[int]:
         k = int(bursts.chunk)
+        if messages is not None and int(getattr(messages, "chunk", k)) != k:
+            raise ValueError(f"messages of chunk {int(messages.chunk)} with the bursts of chunk {k}")
         if len(parsed_rows):
             self.locked = True
         if self.locked:
@@ -155,6 +182,14 @@ class Acquisition:
         if k < self.valid_from:
             self._forget()
             return None
+        rows = [] if messages is None else np.asarray(getattr(messages, "records", messages))
+        if len(rows):
+            est = [burst_message_offset_hz(r, self.out_rate, self.if_hz, self.deviation_hz, self.packet_symbols) for r in rows]
+            self.offset += int(round(float(np.median(est))))
+            self.valid_from = int(submitted)
+            self.estimates = []
+            self._forget()
+            return self.offset
         if self._chunk is not None and k == self._chunk + 1:
             self.estimates += [hz for _, hz in self._waiting]
         self._waiting = self.candidates(bursts)

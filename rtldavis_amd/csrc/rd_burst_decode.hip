@@ -1,0 +1,315 @@
+// rd_burst_decode.hip - decode the bursts k_chan_bursts found, wherever in the channel filter's pass band their carrier
+// lies (include/rtldavis_hip.h, BURST DECODE).  The demodulator slices the discriminator around 0 Hz, so a burst further
+// off than the deviation gives it no message; here the discriminator is sliced around the burst's OWN mean frequency -
+// the run's lag-1 correlation sum, which its rd_burst record carries - and sync word plus CRC-16 prove the message.
+// Used by rd_wideband.hip per streamed chunk (rd_wb_set_burst_decode), behind k_chan_bursts on the same stream.
+//
+// Definition (exact integers throughout; SL = symbol_length, N = packet_symbols, sync = the 16 preamble bits,
+// LOOK_W = ceil((N SL + 1) / 128), LOOK = 128 LOOK_W, MAX_W = 32).  Channel c of chunk k: b = its channelized bytes,
+// continued to t < 0 by chunk k-1's (t + block_size); a = 2 b - 255, z[t] = aI[t] + j aQ[t], p[t] = z[t] conj(z[t-1])
+// (|re p|, |im p| <= 2 x 255^2 < 2^18).  For every rd_burst (first, windows, flags, corr) of the channel, in order:
+//   windows > MAX_W: counted in long_runs, not decoded.  corr = 0: skipped.
+//   region  t0 = 128 first - (LOOK if (flags & 1) and have_prev), t1 = 128 (first + windows); t1 - t0 < N SL + 1: skipped
+//   d[t] = im p[t] corr_re - re p[t] corr_im   (t0 < t < t1)      Im(p conj(corr)); |corr| < 2^30 at MAX_W: |d| < 2^48
+//   s[t] = sum_{i < SL} d[t - i]               (t0 + SL <= t < t1), bit[t] = s[t] > 0
+//   candidate tau (the end of the first symbol): t0 + SL <= tau, tau + SL (N - 1) < t1, tau + SL (N - 1) >= 0 (the packet
+//   ends in this chunk: the look-back never reports a packet twice); symbols bit[tau + SL i]; the first 16 equal sync; the
+//   N symbols packed MSB first into N / 8 bytes whose bit-swapped bytes [2:] have CRC-16-CCITT 0 (rd_parse.h)
+//   one record per run at most: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
+//
+// Kernel.  One workgroup of 256 threads per channel, the channel's runs one after the other (the loop is bounded by the
+// record places, every inner loop by the region).  Per run: the region's bytes go to LDS as they lie (16-byte vectors;
+// t0 and the chunk boundary are multiples of 128); s is linear in p, so with SI, SR the sums of im p, re p over the SL
+// samples (< 2^24: int32; a lane takes a stretch of consecutive outputs and slides both sums along it, one p in and one
+// out per output) s[t] = corr_re SI[t] - corr_im SR[t] - two 32 x 32 -> 64-bit multiplies per sample, exact -
+// goes to LDS as int64 (48 KiB for the longest region, 32 + 16 windows; the bytes 12 KiB); then one lane per tau: the
+// sync word first - all but a few lanes leave there -, the rest of the symbols with byte packing, CRC and margin.  The
+// candidates are reduced by a max over (margin, -tau): a total order, so the fixed tree of shuffles and the four waves'
+// results in LDS give the same record whatever the order - no atomics.  The winner's record is completed by the whole
+// workgroup (sum of p over the packet's N SL samples) and written by thread 0.
+// Output: channel c owns cap = rd_bu_cap(nW) record places, as in the burst slot, and one header (n_msgs, long_runs,
+// chunk): a run gives at most one record, so there is no overflow and no ticket; the channel's records are its first
+// n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  The
+// burst records and the floor row are read from the burst slot where k_chan_bursts, earlier on the same stream, wrote
+// them (system-scope loads).  With the default thresholds there are no runs: the header is written and that is all.
+#include <hip/hip_runtime.h>
+
+#include "rd_internal.h"
+#include "rd_parse.h"
+
+extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
+
+#define RD_BD_THREADS 256
+#define RD_BD_MAX_REGION ((RD_BD_MAX_W + RD_BD_MAX_LOOK_W) * RD_BU_WINDOW)   // outputs of the longest region
+
+static_assert(sizeof(rd_burst_msg) == 64 && sizeof(rd_bd_header) == 16, "the slot layout of rd_bd_* (rd_internal.h)");
+static_assert(RD_BD_MAX_REGION * 10 <= 64 * 1024, "s (int64) and the bytes of the longest region: 60 KiB of LDS");
+
+struct rd_bd_params {
+    int sl, n_sym;             // SL, N
+    uint32_t sync;             // the 16 sync symbols, the first in bit 15
+    int look;                  // LOOK
+    int have_prev;
+    unsigned n_win, cap;
+    uint64_t clock, seq;
+};
+
+template <typename T>
+__device__ __forceinline__ T rd_bd_sys_load(const T *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// p[t0 + j] = z[t0 + j] conj(z[t0 + j - 1]) from the region's bytes in LDS (j >= 1)
+__device__ __forceinline__ void rd_bd_p(const uint16_t *zw, int j, int &re, int &im) {
+    const uint32_t a = zw[j], b = zw[j - 1];
+    const int ai = 2 * (int)(a & 0xFFu) - 255, aq = 2 * (int)(a >> 8) - 255;
+    const int pi = 2 * (int)(b & 0xFFu) - 255, pq = 2 * (int)(b >> 8) - 255;
+    re = ai * pi + aq * pq;
+    im = aq * pi - ai * pq;
+}
+
+// (margin, tau) of lane a is the better candidate than that of lane b; tau = INT32_MAX: none
+__device__ __forceinline__ bool rd_bd_better(uint64_t ma, int ta, uint64_t mb, int tb) {
+    if (tb == INT32_MAX) return true;
+    if (ta == INT32_MAX) return false;
+    return ma > mb || (ma == mb && ta < tb);
+}
+
+__global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
+                                                                     size_t ch_stride, size_t n_out, rd_bd_params P,
+                                                                     const rd_burst *runs, const rd_burst_floor *floor,
+                                                                     rd_burst_msg *recs, rd_bd_header *hdr) {
+    __shared__ int64_t s_s[RD_BD_MAX_REGION];            // s[t0 + i] at i (i >= SL)
+    __shared__ uint4 s_z[RD_BD_MAX_REGION / 8];          // the region's bytes: output t0 + i at bytes 2 i, 2 i + 1
+    __shared__ uint64_t s_m[RD_BD_THREADS / 64];
+    __shared__ int s_t[RD_BD_THREADS / 64];
+    __shared__ int s_fr[RD_BD_THREADS / 64], s_fi[RD_BD_THREADS / 64];
+    __shared__ uint32_t s_run[4];                        // n_bursts; first, windows, flags of the run in hand
+    __shared__ int64_t s_corr[2];
+    const int c = (int)blockIdx.x;
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint8_t *src = cur + (size_t)c * ch_stride;
+    const uint8_t *src_prev = prev ? prev + (size_t)c * ch_stride : nullptr;
+    const rd_burst *mine = runs + (size_t)c * P.cap;
+    rd_burst_msg *out = recs + (size_t)c * P.cap;
+    const uint16_t *zw = (const uint16_t *)s_z;           // output t0 + i: I in the low byte, Q in the high one
+    if (tid == 0u) s_run[0] = rd_bd_sys_load(&floor[c].n_bursts);
+    __syncthreads();
+    uint32_t n_runs = s_run[0];
+    if (n_runs > P.cap) n_runs = P.cap;                   // (k_chan_bursts never writes more)
+    const int SL = P.sl, N = P.n_sym, need = N * SL + 1;
+    uint32_t n_msgs = 0u, n_long = 0u;
+    for (uint32_t r = 0; r < n_runs; r++) {
+        __syncthreads();                                  // the run before has been read out of LDS
+        if (tid == 0u) {                                  // one thread crosses the bus, the workgroup takes it from LDS
+            s_run[1] = rd_bd_sys_load(&mine[r].first);
+            s_run[2] = rd_bd_sys_load(&mine[r].windows);
+            s_run[3] = rd_bd_sys_load(&mine[r].flags);
+            s_corr[0] = rd_bd_sys_load(&mine[r].corr_re);
+            s_corr[1] = rd_bd_sys_load(&mine[r].corr_im);
+        }
+        __syncthreads();
+        const uint32_t first = s_run[1], windows = s_run[2], rflags = s_run[3];   // (workgroup-uniform from here on)
+        const int64_t cr64 = s_corr[0], ci64 = s_corr[1];
+        if (windows > RD_BD_MAX_W) {
+            n_long++;
+            continue;
+        }
+        if (windows == 0u || first >= P.n_win || first + windows > P.n_win) continue;   // (no record of k_chan_bursts)
+        if (cr64 == 0 && ci64 == 0) continue;
+        const bool back = (rflags & 1u) && P.have_prev && src_prev && first == 0u;
+        const int t0 = RD_BU_WINDOW * (int)first - (back ? P.look : 0);
+        const int t1 = RD_BU_WINDOW * (int)(first + windows);
+        const int len = t1 - t0;                          // a multiple of 128, <= RD_BD_MAX_REGION
+        if (len < need || len > RD_BD_MAX_REGION) continue;
+        const int32_t cr = (int32_t)cr64, ci = (int32_t)ci64;   // |corr| <= 32 x 254 x 65025 < 2^30
+        // ---- the region's bytes
+        for (int v = (int)tid; v < len / 8; v += RD_BD_THREADS) {
+            const int t = t0 + 8 * v;                     // (t0 and 0 are multiples of 8: a vector lies in one chunk)
+            const uint8_t *g = t < 0 ? src_prev + 2 * ((long)t + (long)n_out) : src + 2 * (long)t;
+            s_z[v] = *(const uint4 *)g;
+        }
+        __syncthreads();
+        // ---- s[t0 + i], SL <= i < len: a lane takes a stretch of outputs and slides the two window sums along it
+        const int per = (len - SL + RD_BD_THREADS - 1) / RD_BD_THREADS;
+        const int ia = SL + (int)tid * per, ib = min(ia + per, len);
+        if (ia < ib) {
+            int sr = 0, si = 0, re, im;
+            for (int j = ia - SL + 1; j <= ia; j++) {
+                rd_bd_p(zw, j, re, im);
+                sr += re;
+                si += im;
+            }
+            s_s[ia] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
+            for (int i = ia + 1; i < ib; i++) {
+                rd_bd_p(zw, i, re, im);
+                sr += re;
+                si += im;
+                rd_bd_p(zw, i - SL, re, im);          // (i - SL >= 1: its pair lies in the region)
+                sr -= re;
+                si -= im;
+                s_s[i] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
+            }
+        }
+        __syncthreads();
+        // ---- one lane per tau = t0 + i
+        uint64_t best_m = 0ull;
+        int best_t = INT32_MAX;
+        const int i_hi = len - SL * (N - 1);              // i + SL (N - 1) < len
+        for (int i = SL + (int)tid; i < i_hi; i += RD_BD_THREADS) {
+            const int tau = t0 + i;
+            if (tau + SL * (N - 1) < 0) continue;         // the packet ended in the chunk before: reported there
+            uint64_t margin = ~0ull;
+            uint32_t word = 0u, crc = 0u;
+            bool ok = true;
+            for (int k = 0; k < N; k++) {
+                const int64_t v = s_s[i + SL * k];
+                const uint32_t bit = v > 0 ? 1u : 0u;
+                if (k < 16 && bit != ((P.sync >> (15 - k)) & 1u)) {
+                    ok = false;
+                    break;
+                }
+                const uint64_t mag = (uint64_t)(v > 0 ? v : -v);
+                margin = mag < margin ? mag : margin;
+                word = ((word << 1) | bit) & 0xFFu;
+                if ((k & 7) == 7 && k >= 16) crc = rd_crc16_step(crc, rd_swap_bits8(word));
+            }
+            if (ok && crc == 0u && rd_bd_better(margin, tau, best_m, best_t)) {
+                best_m = margin;
+                best_t = tau;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint64_t om = (uint64_t)__shfl_xor((unsigned long long)best_m, off);
+            const int ot = __shfl_xor(best_t, off);
+            if (rd_bd_better(om, ot, best_m, best_t)) {
+                best_m = om;
+                best_t = ot;
+            }
+        }
+        if (lane == 0u) {
+            s_m[wave] = best_m;
+            s_t[wave] = best_t;
+        }
+        __syncthreads();
+        best_m = s_m[0];
+        best_t = s_t[0];
+#pragma unroll
+        for (int wv = 1; wv < RD_BD_THREADS / 64; wv++)
+            if (rd_bd_better(s_m[wv], s_t[wv], best_m, best_t)) {
+                best_m = s_m[wv];
+                best_t = s_t[wv];
+            }
+        if (best_t == INT32_MAX) continue;                // (uniform: every thread read the same four)
+        // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
+        const int i0 = best_t - t0;
+        int fr = 0, fi = 0;                               // |.| <= 2048 x 2 x 255^2 < 2^29
+        for (int j = i0 - SL + 1 + (int)tid; j <= i0 + SL * (N - 1); j += RD_BD_THREADS) {
+            int re, im;
+            rd_bd_p(zw, j, re, im);
+            fr += re;
+            fi += im;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            fr += __shfl_xor(fr, off);
+            fi += __shfl_xor(fi, off);
+        }
+        if (lane == 0u) {
+            s_fr[wave] = fr;
+            s_fi[wave] = fi;
+        }
+        __syncthreads();
+        if (tid == 0u) {                                  // field by field into the slot: no private copy of the record
+            rd_burst_msg *m = &out[n_msgs];
+            m->channel = c;
+            m->first = first;
+            m->tau = best_t;
+            m->flags = back ? 1u : 0u;
+            m->time = P.clock + (uint64_t)(int64_t)best_t;
+            m->margin = best_m;
+            int64_t sfr = 0, sfi = 0;
+            for (int wv = 0; wv < RD_BD_THREADS / 64; wv++) {
+                sfr += s_fr[wv];
+                sfi += s_fi[wv];
+            }
+            m->f_re = sfr;
+            m->f_im = sfi;
+            uint32_t word = 0u, ones = 0u, id = 0u;
+            for (int k = 0; k < N; k++) {
+                const uint32_t bit = s_s[i0 + SL * k] > 0 ? 1u : 0u;
+                ones += bit;
+                word = ((word << 1) | bit) & 0xFFu;
+                if ((k & 7) == 7) m->data[k >> 3] = (uint8_t)word;
+                if (k == 23) id = rd_swap_bits8(word) & 7u;
+            }
+            for (int k = N >> 3; k < RD_BD_DATA_BYTES; k++) m->data[k] = 0;
+            m->ones = (uint8_t)ones;
+            m->id = (uint8_t)id;
+            m->pad[0] = m->pad[1] = m->pad[2] = m->pad[3] = 0;
+        }
+        n_msgs++;
+    }
+    if (tid == 0u) {
+        rd_bd_header h;
+        h.n_msgs = n_msgs;
+        h.long_runs = n_long;
+        h.chunk = (uint32_t)P.seq;
+        h.pad = 0u;
+        hdr[c] = h;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+int rd_bd_look_windows(const rd_config *cfg) {
+    return (cfg->packet_symbols * cfg->symbol_length + 1 + RD_BU_WINDOW - 1) / RD_BU_WINDOW;
+}
+
+int rd_burst_decode_check(const rd_config *cfg) {
+    if (!cfg) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (cfg->preamble_symbols != 16)
+        return rd_fail_msg(RD_ERR_ARG, "burst decode: a sync word of %d symbols, not 16", cfg->preamble_symbols);
+    if (cfg->symbol_length < 1 || cfg->packet_symbols % 8 || cfg->packet_symbols < 40 || cfg->packet_symbols > 8 * RD_BD_DATA_BYTES)
+        return rd_fail_msg(RD_ERR_ARG, "burst decode: packets of %d symbols (a multiple of 8 in 40 .. %d)", cfg->packet_symbols,
+                           8 * RD_BD_DATA_BYTES);
+    if ((long)cfg->packet_symbols * cfg->symbol_length + 1 > RD_BD_MAX_LOOK_W * RD_BU_WINDOW)
+        return rd_fail_msg(RD_ERR_ARG, "burst decode: a packet of %d x %d + 1 outputs, at most %d", cfg->packet_symbols,
+                           cfg->symbol_length, RD_BD_MAX_LOOK_W * RD_BU_WINDOW);
+    if (cfg->block_size < RD_BU_WINDOW * rd_bd_look_windows(cfg))
+        return rd_fail_msg(RD_ERR_ARG, "burst decode: block_size %d is shorter than the look-back of %d outputs", cfg->block_size,
+                           RD_BU_WINDOW * rd_bd_look_windows(cfg));
+    return rd_bursts_check((size_t)cfg->block_size);
+}
+
+int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                           size_t n_out, uint64_t clock, uint64_t seq, const void *burst_slot, void *slot, hipStream_t st) {
+    if (!chan_out || !burst_slot || !slot || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    int rc = rd_burst_decode_check(cfg);
+    if (rc) return rc;
+    if (n_out != (size_t)cfg->block_size || out_stride < 2 * n_out || (out_stride & 15) || ((uintptr_t)chan_out & 15) ||
+        ((uintptr_t)chan_prev & 15) || ((uintptr_t)slot & 15))
+        return rd_fail_msg(RD_ERR_ARG, "burst decode: stride %zu for %zu outputs, or a misaligned buffer", out_stride, n_out);
+    const size_t n_win = n_out / RD_BU_WINDOW;
+    rd_bd_params P;
+    P.sl = cfg->symbol_length;
+    P.n_sym = cfg->packet_symbols;
+    P.sync = 0u;
+    for (int i = 0; i < 16; i++) P.sync = (P.sync << 1) | (cfg->preamble[i] ? 1u : 0u);
+    P.look = RD_BU_WINDOW * rd_bd_look_windows(cfg);
+    P.have_prev = chan_prev ? 1 : 0;
+    P.n_win = (unsigned)n_win;
+    P.cap = (unsigned)rd_bu_cap(n_win);
+    P.clock = clock;
+    P.seq = seq;
+    const uint8_t *bs = (const uint8_t *)burst_slot;
+    uint8_t *base = (uint8_t *)slot;
+    hipLaunchKernelGGL(k_chan_burst_decode, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride, n_out, P,
+                       (const rd_burst *)bs, (const rd_burst_floor *)(bs + rd_bu_floor_offset(n_ch, n_win)), (rd_burst_msg *)base,
+                       (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win)));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_decode: %s", hipGetErrorString(e));
+    return RD_OK;
+}

@@ -256,6 +256,28 @@ static inline size_t rd_bu_thr_offset(int n_ch, size_t n_win) { return rd_bu_flo
 static inline size_t rd_bu_slot_bytes(int n_ch, size_t n_win) { return rd_bu_thr_offset(n_ch, n_win) + (size_t)n_ch * sizeof(uint32_t); }
 int rd_bursts_check(size_t n_out);
 int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_t n_out, uint64_t seq, void *slot, hipStream_t st);
+// Burst decode of a channelized chunk (rd_burst_decode.hip: k_chan_burst_decode; the definition: include/rtldavis_hip.h,
+// BURST DECODE), queued behind rd_bursts_launch on the same stream.  rd_burst_decode_check: the argument rule for a
+// configuration (RD_ERR_ARG with a message, no device work).  rd_burst_decode_launch: chan_out as given to rd_bursts_launch,
+// chan_prev the chunk before laid out alike (null: none, no look-back), clock the absolute time of the chunk's first
+// output; burst_slot: the slot that rd_bursts_launch filled; slot: a device address (mapped host memory) of
+// rd_bd_slot_bytes laid out as
+//   [n_ch][cap] rd_burst_msg | [n_ch] rd_bd_header                                    cap = rd_bu_cap(n_win)
+// The kernel writes every header and, per channel, the first header.n_msgs of its cap record places.
+#define RD_BD_MAX_W 32          /* a run of more windows is counted, not decoded */
+#define RD_BD_MAX_LOOK_W 16     /* packet_symbols * symbol_length + 1 <= 2048 */
+#define RD_BD_DATA_BYTES RD_BURST_MSG_BYTES
+struct rd_bd_header {
+    uint32_t n_msgs, long_runs;
+    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
+    uint32_t pad;
+};
+static inline size_t rd_bd_header_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst_msg); }
+static inline size_t rd_bd_slot_bytes(int n_ch, size_t n_win) { return rd_bd_header_offset(n_ch, n_win) + (size_t)n_ch * sizeof(rd_bd_header); }
+int rd_bd_look_windows(const rd_config *cfg);
+int rd_burst_decode_check(const rd_config *cfg);
+int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                           size_t n_out, uint64_t clock, uint64_t seq, const void *burst_slot, void *slot, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

@@ -42,6 +42,11 @@
 // next submit, like the gains) need no copy and no device table: the submit writes the table into the slot itself, which
 // is free by the argument for the level slot, and the kernel reads it there - host writes made before the launch are
 // visible to it - and echoes what it used in the floor records.
+// Burst decode (rd_wb_set_burst_decode / rd_wb_burst_messages; rd_burst_decode.hip): with decode on, k_chan_burst_decode is
+// queued behind k_chan_bursts, in front of the chunk's demodulator launch.  It reads the burst slot of the chunk's parity
+// (written by the kernel in front of it), d_out[s] and, for a run that begins with the chunk, the end of d_out[s ^ 1]:
+// chunk k-1's channelized bytes, next written by the channelizer of chunk k+1, later on the same stream.  Its records go
+// into a mapped pinned slot of the chunk's parity, which the fetch copies out like the burst records.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -108,6 +113,14 @@ struct rd_wideband {
     uint8_t *h_bu[2] = {nullptr, nullptr};
     std::vector<rd_burst> bu_last;
     std::vector<rd_burst_floor> bf_last;
+    // burst decode: the demodulator's configuration (the kernel's symbol length, packet length and sync word), on / off
+    // (switched on a quiet receiver; never on without bursts), the mapped pinned slots per parity (rd_internal.h:
+    // rd_bd_slot_bytes) and the records the last fetch kept
+    rd_config cfg = {};
+    bool decode = false, last_decode = false;
+    uint8_t *h_bd[2] = {nullptr, nullptr};
+    std::vector<rd_burst_msg> bm_last;
+    std::vector<uint32_t> bl_last;
 };
 #define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
@@ -167,6 +180,7 @@ extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg
     w->dem = dem;
     w->n_ch = ccfg->n_channels;
     w->B = (size_t)cfg->block_size;
+    w->cfg = *cfg;
     w->chunk_bytes = (size_t)rd_chan_bytes_per_sample(ch) * (size_t)ccfg->decim * w->B;
     w->plan.assign(shift_hz, shift_hz + w->n_ch);
     w->shift = w->want = w->plan;
@@ -189,6 +203,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_lv[i]);
             hipHostFree(w->h_sp[i]);
             hipHostFree(w->h_bu[i]);
+            hipHostFree(w->h_bd[i]);
         }
         hipFree(w->d_lvacc);
     }
@@ -267,6 +282,19 @@ static int wb_alloc_bursts(rd_wideband *w) {
     return RD_OK;
 }
 
+// the decoded messages' slots, when decode is first wanted
+static rd_bd_header *wb_bd_header(const rd_wideband *w, int i) {
+    return (rd_bd_header *)(w->h_bd[i] + rd_bd_header_offset(w->n_ch, wb_bu_windows(w)));
+}
+static int wb_alloc_decode(rd_wideband *w) {
+    for (int i = 0; i < 2; i++)
+        if (!w->h_bd[i]) {
+            WCHK(hipHostMalloc((void **)&w->h_bd[i], rd_bd_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
+            memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));   // (a message count no chunk can have)
+        }
+    return RD_OK;
+}
+
 extern "C" int rd_wideband_reset(rd_wideband *w) {
     if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
     int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
@@ -289,6 +317,9 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->last_bursts = false;
     for (int i = 0; i < 2; i++)
         if (w->h_bu[i]) memset(wb_bu_floor(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_burst_floor));
+    w->last_decode = false;       // (the setting stays; n_sub = 0: the first chunk has no look-back)
+    for (int i = 0; i < 2; i++)
+        if (w->h_bd[i]) memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));
     return RD_OK;
 }
 
@@ -357,6 +388,33 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         if (rc) return rc;
     }
     w->bursts = enabled != 0;
+    if (!w->bursts) w->decode = false;   // (the decoder reads the burst records)
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before burst decode is switched", rd_demod_inflight(w->dem));
+    if (enabled) {
+        if (!w->bursts) return rd_fail_msg(RD_ERR_STATE, "burst decode needs bursts on (rd_wb_set_bursts)");
+        int rc = rd_burst_decode_check(&w->cfg);
+        if (rc) return rc;
+    }
+    w->decode = enabled != 0;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (long_runs && n_channels != w->n_ch)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d long-run counts of %d", n_channels, w->n_ch);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_decode) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with burst decode off (rd_wb_set_burst_decode)");
+    *n = (int)w->bm_last.size();
+    if (long_runs) memcpy(long_runs, w->bl_last.data(), (size_t)w->n_ch * sizeof(uint32_t));
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d burst messages, room for %d", *n, cap);
+    if (*n) memcpy(out, w->bm_last.data(), (size_t)*n * sizeof(rd_burst_msg));
     return RD_OK;
 }
 
@@ -384,6 +442,13 @@ extern "C" int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_b
     if (floor) memcpy(floor, w->bf_last.data(), (size_t)w->n_ch * sizeof(rd_burst_floor));
     if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d burst records, room for %d", *n, cap);
     if (*n) memcpy(out, w->bu_last.data(), (size_t)*n * sizeof(rd_burst));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_fetched_chunk(rd_wideband *w, uint64_t *chunk) {
+    if (!w || !chunk) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    *chunk = (uint64_t)w->last;
     return RD_OK;
 }
 
@@ -417,6 +482,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (w->levels && (rc = wb_alloc_levels(w))) return rc;
     if (w->spec_n && (rc = wb_alloc_spectrum(w))) return rc;
     if (w->bursts && (rc = wb_alloc_bursts(w))) return rc;
+    if (w->decode && (rc = wb_alloc_decode(w))) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
     const int s = (int)(w->n_sub & 1);
@@ -461,6 +527,14 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
         WCHK(hipHostGetDevicePointer(&bu, w->h_bu[s], 0));
         rc = rd_bursts_launch(w->d_out[s], 2 * w->B, w->n_ch, w->B, (uint64_t)w->n_sub, bu, w->st);
         if (rc) return rc;
+        if (w->decode) {
+            // decode slot s: free by the argument for the level slot; d_out[s ^ 1] holds chunk k-1 (header comment)
+            void *bd = nullptr;
+            WCHK(hipHostGetDevicePointer(&bd, w->h_bd[s], 0));
+            rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
+                                        w->clock, (uint64_t)w->n_sub, bu, bd, w->st);
+            if (rc) return rc;
+        }
     }
     w->clock += w->B;
     w->n_sub++;
@@ -473,6 +547,25 @@ static int wb_fetched(rd_wideband *w, int rc) {
     w->last_levels = false;
     w->last_spec = false;
     w->last_bursts = false;
+    w->last_decode = false;
+    if (w->decode) {
+        // as the burst records below: k_chan_burst_decode ran before the demodulator launch that has reported.  Every
+        // header carries the chunk's number; a channel's messages are the first n_msgs of its record places.
+        const size_t cap_c = rd_bu_cap(wb_bu_windows(w));
+        const rd_burst_msg *recs = (const rd_burst_msg *)w->h_bd[w->last & 1];
+        const rd_bd_header *hd = wb_bd_header(w, (int)(w->last & 1));
+        w->bm_last.clear();
+        w->bl_last.assign(w->n_ch, 0u);
+        for (int c = 0; c < w->n_ch; c++) {
+            const rd_bd_header h = hd[c];
+            if (h.chunk != (uint32_t)w->last || h.n_msgs > cap_c)
+                return rd_fail_msg(RD_ERR_DEVICE, "burst message header of channel %d belongs to chunk %u (%u messages), not %ld", c,
+                                   h.chunk, h.n_msgs, w->last);
+            w->bl_last[c] = h.long_runs;
+            w->bm_last.insert(w->bm_last.end(), recs + (size_t)c * cap_c, recs + (size_t)c * cap_c + h.n_msgs);
+        }
+        w->last_decode = true;
+    }
     if (w->bursts) {
         // as the level records below: k_chan_bursts ran before the demodulator launch that has reported.  Every floor
         // record carries the chunk's number; a channel's runs are the first n_bursts of its record places.

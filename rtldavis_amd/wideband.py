@@ -64,6 +64,23 @@ class Bursts(NamedTuple):
     chunk: int
 
 
+# burst_messages(): one row per decoded burst - the layout of rd_burst_msg
+BURST_MSG_DTYPE = np.dtype([("channel", np.int32), ("first", np.uint32), ("tau", np.int32), ("flags", np.uint32),
+                            ("time", np.uint64), ("margin", np.uint64), ("f_re", np.int64), ("f_im", np.int64),
+                            ("data", np.uint8, (_lib.RD_BURST_MSG_BYTES,)), ("ones", np.uint8), ("id", np.uint8),
+                            ("pad", np.uint8, (4,))])
+BURST_DECODE_MAX_WINDOWS = 32          # a longer run is counted in ``long_runs``, not decoded
+
+
+class BurstMessages(NamedTuple):
+    """``WidebandReceiver.burst_messages()``: ``records`` (structured array of ``BURST_MSG_DTYPE``, one row per burst that
+    carried a CRC-valid message, channels ascending, a channel's runs ascending), ``long_runs`` (uint32 per channel: runs
+    of more than 32 windows, which are not decoded) and ``chunk``, the chunk's number since construction / ``reset()``."""
+    records: np.ndarray
+    long_runs: np.ndarray
+    chunk: int
+
+
 class Spectrum(NamedTuple):
     """``WidebandReceiver.spectrum()`` / ``Channelizer.spectrum()``: ``power`` (float64 [n_bins], ascending frequency,
     1.0 = a full-scale complex tone on a bin centre), ``freqs_hz`` (float64 [n_bins], the bins' absolute RF centres:
@@ -326,6 +343,42 @@ class WidebandReceiver:
             rc = L.rd_wb_bursts(self._h, recs.ctypes.data, recs.size, C.byref(n), floor.ctypes.data, floor.size)
         _lib.check(rc)
         return Bursts(recs[: n.value].copy(), floor, int(floor["chunk"][0]))
+
+    def set_burst_decode(self, on: bool = True) -> None:
+        """From the next chunk on, decode every burst ``bursts()`` reports on the device (one more kernel behind the
+        burst kernel): the discriminator is sliced around the burst's own mean frequency, so a packet decodes at any
+        offset the channel filter passes, and sync word plus CRC prove that it is a message; ``burst_messages()``
+        returns the records.  Needs a receiver with nothing in flight and ``set_bursts(True)`` (RuntimeError;
+        ``set_bursts(False)`` switches it off too); ValueError unless the configuration has 16 preamble symbols,
+        ``packet_symbols`` a multiple of 8 in 40 .. 80, ``packet_symbols * symbol_length + 1 <= 2048`` and ``block_size``
+        at least that, rounded up to whole windows of 128.  Off (the default): nothing is launched."""
+        _lib.check(_lib.lib().rd_wb_set_burst_decode(self._h, 1 if on else 0))
+
+    def burst_messages(self) -> "BurstMessages":
+        """Messages of the chunk the last ``fetch()`` returned - later chunks may be in flight - as exact integers.  Per
+        run of ``bursts()`` of at most 32 windows (a run that begins with the chunk is extended LOOK_W windows back - a packet's
+        length + 1 in whole windows, 9 for 14 samples per symbol, 6 for 8 - into the
+        chunk before), at most one row: ``channel``, ``first`` (the run's), ``tau`` (the output at which the first symbol
+        ends, relative to the chunk's first output - negative when the packet began in the chunk before; the packet ends
+        in this chunk), ``flags`` (bit 0: the region reached into the previous chunk), ``time`` (``tau`` on the receiver's
+        absolute output clock), ``margin`` (the least |matched filter output| among the symbols), ``f_re`` / ``f_im`` (the
+        lag-1 correlation summed over the packet: ``acquire.burst_message_offset_hz`` turns it into a frequency),
+        ``data`` (the on-air bytes, as ``Packet.data``: ``dsp.parse_packet`` takes them), ``ones`` and ``id``.  A burst
+        the demodulator decodes as well is reported here and in ``parsed()``: dedupe by channel, chunk and data.
+        RuntimeError before any fetch and when decode was off for that chunk."""
+        L = _lib.lib()
+        long_runs = np.empty(self.n_channels, np.uint32)
+        n = C.c_int(0)
+        recs = np.empty(self._burst_cap, BURST_MSG_DTYPE)
+        rc = L.rd_wb_burst_messages(self._h, recs.ctypes.data, recs.size, C.byref(n), long_runs.ctypes.data, long_runs.size)
+        if rc == _lib.RD_ERR_CAPACITY:  # nothing is lost: the handle keeps the records
+            self._burst_cap = max(2 * self._burst_cap, n.value)
+            recs = np.empty(self._burst_cap, BURST_MSG_DTYPE)
+            rc = L.rd_wb_burst_messages(self._h, recs.ctypes.data, recs.size, C.byref(n), long_runs.ctypes.data, long_runs.size)
+        _lib.check(rc)
+        chunk = C.c_uint64(0)                            # the chunk whose headers the fetch checked
+        _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
+        return BurstMessages(recs[: n.value].copy(), long_runs, int(chunk.value))
 
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel

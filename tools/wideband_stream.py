@@ -10,7 +10,8 @@ around work that ends in a fetch:
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own.
 
     python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
-                                    [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]] [--json OUT]
+                                    [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]]
+                                    [--burst-decode [--burst-decode-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -24,6 +25,10 @@ after every fetch and handed to agc.GainControl.update, whose gains go into set_
 every chunk's channelizer; bursts() read after every fetch, its floor turned into the next thresholds and its records handed
 to acquire.Acquisition.update - a proposed retune is counted, not applied).  "Off" is the baseline of the same run; both go
 into --bursts-out (default profiles/wideband_bursts.txt).  The kernel's own time: the rocprofv3 run above.
+--burst-decode: as --bursts, but the two windows of every repeat are burst detection on, and burst detection plus burst
+decode on (WidebandReceiver.set_burst_decode: k_chan_burst_decode behind k_chan_bursts; burst_messages() read after
+every fetch and handed to Acquisition.update with the rest).  Both go into --burst-decode-out (default
+profiles/wideband_burst_decode.txt); the comparison outside this run is the commit before with --bursts.
 """
 import argparse
 import json
@@ -53,10 +58,18 @@ def main():
     ap.add_argument("--bursts", action="store_true", help="time every window with burst detection off and on; write --bursts-out")
     ap.add_argument("--bursts-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                          "wideband_bursts.txt"))
+    ap.add_argument("--burst-decode", action="store_true",
+                    help="time every window with bursts on, and with bursts and burst decode on; write --burst-decode-out")
+    ap.add_argument("--burst-decode-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                               "wideband_burst_decode.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
         raise SystemExit("--chunks >= 1, --repeats >= 1 and --capture-chunks >= 3")
+    if args.bursts and args.burst_decode:
+        raise SystemExit("--bursts or --burst-decode: each run compares two windows")
+    decode = args.burst_decode
+    args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
     off = [f - CZ.DEFAULT_CENTRE_HZ for f in CZ.US_CHANNELS_HZ]
@@ -83,7 +96,7 @@ def main():
     moved = np.zeros(rx.n_channels, np.int64)
     moved[[25] if args.retune == "one" else slice(None)] = 1
 
-    bursts_on = [False]
+    bursts_on, decode_on, n_dmsgs = [False], [False], [0]
 
     def meter():
         if ctl is not None:
@@ -94,7 +107,11 @@ def main():
             b = rx.bursts()
             n_bursts[0] += len(b.records)
             rx.set_burst_threshold(acq.thresholds(b.floor))
-            n_asked[0] += acq.update(b, rx.parsed() if args.parse else (), rx.submitted) is not None
+            msgs = None
+            if decode_on[0]:
+                msgs = rx.burst_messages()
+                n_dmsgs[0] += len(msgs.records)
+            n_asked[0] += acq.update(b, rx.parsed() if args.parse else (), rx.submitted, msgs) is not None
 
     def run(n):
         """n chunks round and round through submit / fetch, two in flight; per-chunk latency and packets."""
@@ -126,8 +143,10 @@ def main():
         for on in ((False, True) if args.bursts else (False,)):
             rx.reset()
             if args.bursts:
-                rx.set_bursts(on)
-                bursts_on[0] = on
+                rx.set_bursts(on or decode)
+                rx.set_burst_decode(on and decode)
+                bursts_on[0], decode_on[0] = on or decode, on and decode
+                n_dmsgs[0] = 0
                 acq.reset()
                 rx.set_burst_threshold(thr0)
                 n_bursts[0] = n_asked[0] = 0
@@ -171,7 +190,19 @@ def main():
             f"  all windows, wall s: off {' '.join(f'{r[0]:.3f}' for r in runs_off)}; on {' '.join(f'{w:.3f}' for w in walls)}",
             f"  last window on: {n_bursts[0]} burst records, {n_asked[0]} retunes proposed",
         ]
-        with open(args.bursts_out, "w") as fh:
+        if decode:
+            res["burst_decode"] = {"messages_last_window": n_dmsgs[0]}
+            lines = [
+                "WidebandReceiver burst decode (k_chan_burst_decode), bursts + decode on against bursts on in the same run: "
+                "tools/wideband_stream.py --burst-decode" + (" --parse" if args.parse else ""),
+                lines[1],
+                f"  bursts on:           {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(burst_messages() read and handed to Acquisition.update per chunk)",
+                f"  all windows, wall s: bursts {' '.join(f'{r[0]:.3f}' for r in runs_off)}; bursts + decode {' '.join(f'{w:.3f}' for w in walls)}",
+                f"  last window with decode: {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages, {n_asked[0]} retunes proposed",
+            ]
+        with open(args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
