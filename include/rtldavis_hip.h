@@ -540,12 +540,24 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  *   5. candidate tau, the end of the first symbol: t0 + SL <= tau and tau + SL (N - 1) < t1; symbols bit[tau + SL i],
  *      i < N; the first 16 equal sync; the N symbols, packed MSB first into N / 8 on-air bytes, pass the CRC gate of
  *      rd_parse_packet (CRC-16-CCITT over the bit-swapped bytes [2:] is 0); and the packet ends in this chunk,
- *      tau + SL (N - 1) >= 0 - a message is reported with the chunk in which its packet ends, as the demodulator does, so
- *      the look-back never reports one twice.
+ *      tau + SL (N - 1) >= 0 - a message is reported with the chunk in which its packet ends, as the demodulator does.
+ *      This rule alone does not keep the look-back from reporting a packet twice: a packet has about SL - 2 adjacent
+ *      valid taus, so when its last symbol ends within SL outputs of the chunk boundary, chunk k can report a tau that
+ *      ends before the boundary and chunk k+1 one that ends after it.  Step 7 drops the second report.
  *   6. at most one record per run: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
+ *   7. on the host, when the fetch of chunk k+1 copies the records out: a record with flags & 1 is dropped when its
+ *      channel and data equal those of a record that the fetch of chunk k delivered (after its own drop) and its time
+ *      differs from that record's by less than SL.  The device cannot do this: chunk k slices with another run's
+ *      correlation sum and may not have decoded the packet at all.  n_msgs and the records rd_wb_burst_messages hands out
+ *      are those after the drop; rd_wideband_reset forgets the previous chunk's records; a chunk that was never fetched
+ *      (dropped after a timeout) delivered none.
+ * A rd_burst that k_chan_bursts never writes - windows = 0, first >= nW, first + windows > nW, or a place past the
+ * channel's ceil(nW / 2) - is skipped (after step 1).
  * Records: channels ascending, a channel's runs ascending.  The same chunks and thresholds give the same bits on every run.
  * Not solved here: a packet of which only the last few outputs reach into a chunk whose window 0 stays OFF is missed; a run
- * of more than 32 windows is not decoded.  A burst the demodulator decodes too is reported by both paths (rd_wb_parsed and
+ * of more than 32 windows is not decoded; a packet that ends a few outputs (5 .. 11 at SL 14) into a chunk whose run
+ * holds nothing but the transmission's trailing symbols is missed too - that run's correlation sum lies a deviation off
+ * the carrier, and the chunk before cannot reach the packet's end.  A burst the demodulator decodes too is reported by both paths (rd_wb_parsed and
  * here): the caller dedupes by channel, chunk and data.
  * rd_wb_set_burst_decode: on / off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE otherwise),
  * like rd_wb_set_bursts, and bursts on (RD_ERR_STATE otherwise; rd_wb_set_bursts(w, 0) switches decode off too).
@@ -597,6 +609,21 @@ void rd_debug_mfma_taps8s(uint16_t *vals, uint32_t *idx);
 int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_samples, int hist_mode,
                         uint32_t hist_bytes, float *g_out, uint32_t *bits_out, uint32_t *fix_out,
                         uint32_t fix_cap, uint32_t *n_fix);
+/* Test hooks of the burst kernels (rd_bursts.hip, rd_burst_decode.hip), not part of the drop-in surface either:
+ * tests/test_burst_kernels_crafted.py puts exact bytes, ties and offsets in front of each kernel alone.  Host arrays in, host
+ * arrays out; the bytes are uploaded, the slot is mapped host memory as the receiver allocates it, filled with 0xA5, written
+ * by one launch through the product's launch function and copied out WHOLE - cap = ceil(nW / 2) places per channel, those
+ * past n_bursts / n_msgs still 0xA5.  No receiver is involved.
+ * rd_debug_bursts: chan = n_ch x stride bytes (channel c's 2 n_out bytes at c * stride, stride a multiple of 16);
+ * RD_ERR_ARG with nothing launched for an n_out that rd_wb_set_bursts refuses.
+ * rd_debug_burst_decode: n_out = cfg->block_size; cur / prev laid out alike (prev NULL: no chunk before); runs[n_ch][cap]
+ * and n_runs[n_ch] are written into a burst slot as they are - records k_chan_bursts never writes included; per channel
+ * the header comes back in n_msgs, long_runs and chunk. */
+int rd_debug_bursts(const uint8_t *chan, size_t stride, int n_ch, size_t n_out, const uint32_t *thr, uint64_t seq,
+                    rd_burst *recs_out, rd_burst_floor *floor_out);
+int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                          uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs,
+                          rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
 
 #ifdef __cplusplus
 }

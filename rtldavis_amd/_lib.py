@@ -214,6 +214,9 @@ SIGNATURES = {
     "rd_debug_mfma_taps8s": (None, [_P, _P]),
     "rd_debug_demod_mfma": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_int, C.c_uint32, _P, _P, _P, C.c_uint32,
                                       C.POINTER(C.c_uint32)]),
+    "rd_debug_bursts": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_size_t, _P, C.c_uint64, _P, _P]),
+    "rd_debug_burst_decode": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, _P,
+                                        _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -8,12 +8,15 @@
 // LOOK_W = ceil((N SL + 1) / 128), LOOK = 128 LOOK_W, MAX_W = 32).  Channel c of chunk k: b = its channelized bytes,
 // continued to t < 0 by chunk k-1's (t + block_size); a = 2 b - 255, z[t] = aI[t] + j aQ[t], p[t] = z[t] conj(z[t-1])
 // (|re p|, |im p| <= 2 x 255^2 < 2^18).  For every rd_burst (first, windows, flags, corr) of the channel, in order:
-//   windows > MAX_W: counted in long_runs, not decoded.  corr = 0: skipped.
+//   windows > MAX_W: counted in long_runs, not decoded.  corr = 0: skipped.  A record k_chan_bursts never writes
+//   (windows = 0, first >= nW, first + windows > nW; places past cap) is skipped.
 //   region  t0 = 128 first - (LOOK if (flags & 1) and have_prev), t1 = 128 (first + windows); t1 - t0 < N SL + 1: skipped
 //   d[t] = im p[t] corr_re - re p[t] corr_im   (t0 < t < t1)      Im(p conj(corr)); |corr| < 2^30 at MAX_W: |d| < 2^48
 //   s[t] = sum_{i < SL} d[t - i]               (t0 + SL <= t < t1), bit[t] = s[t] > 0
 //   candidate tau (the end of the first symbol): t0 + SL <= tau, tau + SL (N - 1) < t1, tau + SL (N - 1) >= 0 (the packet
-//   ends in this chunk: the look-back never reports a packet twice); symbols bit[tau + SL i]; the first 16 equal sync; the
+//   ends in this chunk.  A packet has about SL - 2 adjacent valid taus, so one that ends within SL outputs of the chunk
+//   boundary can still be reported on both sides of it: the host drops the second report when it copies the records
+//   out, step 7 of the header, rd_wideband.hip); symbols bit[tau + SL i]; the first 16 equal sync; the
 //   N symbols packed MSB first into N / 8 bytes whose bit-swapped bytes [2:] have CRC-16-CCITT 0 (rd_parse.h)
 //   one record per run at most: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
 //
@@ -32,6 +35,8 @@
 // n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  The
 // burst records and the floor row are read from the burst slot where k_chan_bursts, earlier on the same stream, wrote
 // them (system-scope loads).  With the default thresholds there are no runs: the header is written and that is all.
+#include <cstring>
+
 #include <hip/hip_runtime.h>
 
 #include "rd_internal.h"
@@ -312,4 +317,62 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_decode: %s", hipGetErrorString(e));
     return RD_OK;
+}
+
+// Test hook (tests/test_burst_kernels_crafted.py): k_chan_burst_decode alone on host bytes, through
+// rd_burst_decode_launch and mapped host slots as the receiver allocates them.  The caller's runs ([n_ch][cap]) and
+// n_runs go into a burst slot of the product's layout - records k_chan_bursts never writes included -; the message slot
+// is filled with 0xA5 before the launch and copied out whole, so the caller sees which places the kernel left alone.
+extern "C" int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                     uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs,
+                                     rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+    if (!cfg || !cur || !runs || !n_runs || !msgs_out || !n_msgs || !long_runs || !chunk || n_ch < 1)
+        return rd_fail_msg(RD_ERR_ARG, "null argument");
+    int rc = rd_burst_decode_check(cfg);
+    if (rc) return rc;                               // (nothing allocated, nothing launched)
+    const size_t n_out = (size_t)cfg->block_size;
+    if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "burst decode: stride %zu for %zu outputs", stride, n_out);
+    rc = rd_ensure_device_public();
+    if (rc) return rc;
+    const size_t n_win = n_out / RD_BU_WINDOW, bu_bytes = rd_bu_slot_bytes(n_ch, n_win), bd_bytes = rd_bd_slot_bytes(n_ch, n_win);
+    uint8_t *d_cur = nullptr, *d_prev = nullptr, *bu = nullptr, *bd = nullptr;
+    void *d_bu = nullptr, *d_bd = nullptr;
+#define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
+    RD_DBG_CHK(hipMalloc(&d_cur, (size_t)n_ch * stride));
+    RD_DBG_CHK(hipMemcpy(d_cur, cur, (size_t)n_ch * stride, hipMemcpyHostToDevice));
+    if (prev) {
+        RD_DBG_CHK(hipMalloc(&d_prev, (size_t)n_ch * stride));
+        RD_DBG_CHK(hipMemcpy(d_prev, prev, (size_t)n_ch * stride, hipMemcpyHostToDevice));
+    }
+    RD_DBG_CHK(hipHostMalloc((void **)&bu, bu_bytes, hipHostMallocMapped));
+    RD_DBG_CHK(hipHostMalloc((void **)&bd, bd_bytes, hipHostMallocMapped));
+    memset(bu, 0xA5, bu_bytes);
+    memset(bd, 0xA5, bd_bytes);
+    memcpy(bu, runs, rd_bu_floor_offset(n_ch, n_win));
+    for (int c = 0; c < n_ch; c++) {
+        rd_burst_floor f = {};
+        f.n_bursts = n_runs[c];
+        f.chunk = (uint32_t)seq;
+        memcpy(bu + rd_bu_floor_offset(n_ch, n_win) + (size_t)c * sizeof f, &f, sizeof f);
+    }
+    RD_DBG_CHK(hipHostGetDevicePointer(&d_bu, bu, 0));
+    RD_DBG_CHK(hipHostGetDevicePointer(&d_bd, bd, 0));
+    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, d_bu, d_bd, nullptr);
+    if (rc) goto out;
+    RD_DBG_CHK(hipDeviceSynchronize());
+    memcpy(msgs_out, bd, rd_bd_header_offset(n_ch, n_win));
+    for (int c = 0; c < n_ch; c++) {
+        rd_bd_header h;
+        memcpy(&h, bd + rd_bd_header_offset(n_ch, n_win) + (size_t)c * sizeof h, sizeof h);
+        n_msgs[c] = h.n_msgs;
+        long_runs[c] = h.long_runs;
+        chunk[c] = h.chunk;
+    }
+out:
+#undef RD_DBG_CHK
+    if (bu) hipHostFree(bu);
+    if (bd) hipHostFree(bd);
+    if (d_cur) hipFree(d_cur);
+    if (d_prev) hipFree(d_prev);
+    return rc;
 }

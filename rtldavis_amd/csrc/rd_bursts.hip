@@ -238,3 +238,36 @@ int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_bursts: %s", hipGetErrorString(e));
     return RD_OK;
 }
+
+// Test hook (tests/test_burst_kernels_crafted.py): k_chan_bursts alone on host bytes, through rd_bursts_launch and a
+// mapped host slot as the receiver allocates it.  The slot is filled with 0xA5 before the launch and copied out whole -
+// all cap record places of every channel -, so the caller sees which places the kernel left alone.
+extern "C" int rd_debug_bursts(const uint8_t *chan, size_t stride, int n_ch, size_t n_out, const uint32_t *thr, uint64_t seq,
+                               rd_burst *recs_out, rd_burst_floor *floor_out) {
+    if (!chan || !thr || !recs_out || !floor_out || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    int rc = rd_bursts_check(n_out);
+    if (rc) return rc;                               // (nothing allocated, nothing launched)
+    if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "bursts: stride %zu for %zu outputs", stride, n_out);
+    rc = rd_ensure_device_public();
+    if (rc) return rc;
+    const size_t n_win = n_out / RD_BU_WINDOW, bytes = rd_bu_slot_bytes(n_ch, n_win);
+    uint8_t *d_chan = nullptr, *slot = nullptr;
+    void *d_slot = nullptr;
+#define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
+    RD_DBG_CHK(hipMalloc(&d_chan, (size_t)n_ch * stride));
+    RD_DBG_CHK(hipMemcpy(d_chan, chan, (size_t)n_ch * stride, hipMemcpyHostToDevice));
+    RD_DBG_CHK(hipHostMalloc((void **)&slot, bytes, hipHostMallocMapped));
+    memset(slot, 0xA5, bytes);
+    memcpy(slot + rd_bu_thr_offset(n_ch, n_win), thr, (size_t)n_ch * sizeof(uint32_t));
+    RD_DBG_CHK(hipHostGetDevicePointer(&d_slot, slot, 0));
+    rc = rd_bursts_launch(d_chan, stride, n_ch, n_out, seq, d_slot, nullptr);
+    if (rc) goto out;
+    RD_DBG_CHK(hipDeviceSynchronize());
+    memcpy(recs_out, slot, rd_bu_floor_offset(n_ch, n_win));
+    memcpy(floor_out, slot + rd_bu_floor_offset(n_ch, n_win), (size_t)n_ch * sizeof(rd_burst_floor));
+out:
+#undef RD_DBG_CHK
+    if (slot) hipHostFree(slot);
+    if (d_chan) hipFree(d_chan);
+    return rc;
+}

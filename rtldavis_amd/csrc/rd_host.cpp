@@ -225,3 +225,13 @@ bool rd_waiter::relax() {
     }
     return true;
 }
+
+bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
+    if (!(m.flags & 1u) || sl <= 0) return false;
+    for (size_t i = 0; i < n_delivered; i++) {
+        const rd_burst_msg &q = delivered[i];
+        const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
+        if (q.channel == m.channel && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
+    }
+    return false;
+}

@@ -45,6 +45,11 @@ uint32_t rd_ord_bucket_cap(long n_samples);
 // uint8: NS * 2B bytes), else RD_ERR_ARG with *expected set
 int rd_check_block_count(int is_complex, size_t count, size_t B, size_t NS, size_t *expected);
 
+// BURST DECODE step 7 (include/rtldavis_hip.h): record m reports again a packet that the fetch of the chunk before
+// delivered - m looked back (flags & 1), and one of `delivered` has its channel and data and a time less than sl
+// outputs from m's on the 64-bit clock.  The fetch drops such a record (rd_wideband.hip).
+bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
+
 // Host waits poll (the runtime's blocking waits add 10-20 ms of wake-up latency on this platform).  A wait spins on
 // `pause` for the first ~50 us, then yields the core, then sleeps 50 us at a time; it gives up at its deadline.
 struct rd_waiter {

@@ -121,6 +121,10 @@ struct rd_wideband {
     uint8_t *h_bd[2] = {nullptr, nullptr};
     std::vector<rd_burst_msg> bm_last;
     std::vector<uint32_t> bl_last;
+    // step 7 of the definition: what the fetch of chunk bm_chunk delivered (bm_last), and during the next fetch what the
+    // fetch before it delivered (bm_prev), against which a look-back record is a second report of the same packet
+    std::vector<rd_burst_msg> bm_prev;
+    long bm_chunk = -1;
 };
 #define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
@@ -318,6 +322,8 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     for (int i = 0; i < 2; i++)
         if (w->h_bu[i]) memset(wb_bu_floor(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_burst_floor));
     w->last_decode = false;       // (the setting stays; n_sub = 0: the first chunk has no look-back)
+    w->bm_chunk = -1;             // (... and no chunk before it whose records its own could repeat)
+    w->bm_prev.clear();
     for (int i = 0; i < 2; i++)
         if (w->h_bd[i]) memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));
     return RD_OK;
@@ -554,6 +560,12 @@ static int wb_fetched(rd_wideband *w, int rc) {
         const size_t cap_c = rd_bu_cap(wb_bu_windows(w));
         const rd_burst_msg *recs = (const rd_burst_msg *)w->h_bd[w->last & 1];
         const rd_bd_header *hd = wb_bd_header(w, (int)(w->last & 1));
+        // Step 7 (include/rtldavis_hip.h, BURST DECODE): a look-back record that repeats - same channel, same data, less
+        // than SL outputs apart - a record the fetch of the chunk before DELIVERED is the second report of a packet that
+        // ends at the boundary, and is dropped.  A chunk that was never fetched delivered nothing.
+        if (w->bm_chunk == w->last - 1) w->bm_prev.swap(w->bm_last);
+        else w->bm_prev.clear();
+        w->bm_chunk = -1;
         w->bm_last.clear();
         w->bl_last.assign(w->n_ch, 0u);
         for (int c = 0; c < w->n_ch; c++) {
@@ -562,8 +574,12 @@ static int wb_fetched(rd_wideband *w, int rc) {
                 return rd_fail_msg(RD_ERR_DEVICE, "burst message header of channel %d belongs to chunk %u (%u messages), not %ld", c,
                                    h.chunk, h.n_msgs, w->last);
             w->bl_last[c] = h.long_runs;
-            w->bm_last.insert(w->bm_last.end(), recs + (size_t)c * cap_c, recs + (size_t)c * cap_c + h.n_msgs);
+            for (uint32_t i = 0; i < h.n_msgs; i++) {
+                const rd_burst_msg m = recs[(size_t)c * cap_c + i];
+                if (!rd_bd_repeats(m, w->bm_prev.data(), w->bm_prev.size(), w->cfg.symbol_length)) w->bm_last.push_back(m);
+            }
         }
+        w->bm_chunk = w->last;
         w->last_decode = true;
     }
     if (w->bursts) {

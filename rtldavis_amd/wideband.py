@@ -365,6 +365,9 @@ class WidebandReceiver:
         lag-1 correlation summed over the packet: ``acquire.burst_message_offset_hz`` turns it into a frequency),
         ``data`` (the on-air bytes, as ``Packet.data``: ``dsp.parse_packet`` takes them), ``ones`` and ``id``.  A burst
         the demodulator decodes as well is reported here and in ``parsed()``: dedupe by channel, chunk and data.
+        A packet that ends within ``symbol_length`` outputs of a chunk boundary can be found by both chunks; the fetch
+        drops the later chunk's look-back row when the fetch before it delivered the same ``channel`` and ``data`` less
+        than ``symbol_length`` outputs away in ``time``, so the rows here hold every packet once.
         RuntimeError before any fetch and when decode was off for that chunk."""
         L = _lib.lib()
         long_runs = np.empty(self.n_channels, np.uint32)

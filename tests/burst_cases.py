@@ -85,6 +85,153 @@ def assert_equals_model(got, block, thr, chunk):
         assert np.array_equal(got.records[f], recs[f]), (chunk, f)
 
 
+# ------------------------------------------------------------------------------------------ crafted bytes
+# Inputs for k_chan_bursts alone (the hook rd_debug_bursts): exact bytes, exact thresholds.  Every case names the edge it
+# is built for as a condition on the model of its own bytes, asserted when the case is built - an input that misses its
+# edge fails instead of passing quietly.
+FILL = 0xA5                                                  # what the hook leaves in a place the kernel did not write
+P_MAX = 256 * 65025                                          # p_w of saturated bytes (the kernel's header comment)
+R_MAX = 254 * 65025                                          # |re r_w| or |im r_w| at most
+GAP = 16                                                     # bytes between channels in the cases with a wider stride
+
+
+def cap_of(n_win):
+    return (n_win + 1) // 2
+
+
+def quiet_bytes(rng, n_out):
+    """Noise near 127: bytes 126 .. 129 (a = -3 .. 3), p_w <= 128 x 18."""
+    return rng.integers(126, 130, 2 * n_out).astype(np.uint8)
+
+
+def saturated(kind, n_out):
+    """2 n_out bytes of 0 and 255 only: "zeros", "ones" (all 255), "flip" (outputs (255, 255), (0, 0) alternating: every
+    pair gives -2 x 65025), "rot+" / "rot-" (z turns by +-90 degrees per output: every pair gives +-2 x 65025 j)."""
+    t = np.arange(n_out)
+    if kind == "zeros":
+        i = q = np.zeros(n_out, np.int64)
+    elif kind == "ones":
+        i = q = np.full(n_out, 255)
+    elif kind == "flip":
+        i = q = 255 * (1 - t % 2)
+    else:
+        quad = t % 4 if kind == "rot+" else (-t) % 4         # (a, a), (-a, a), (-a, -a), (a, -a)
+        i, q = 255 * np.isin(quad, (0, 3)), 255 * np.isin(quad, (0, 1))
+    out = np.empty(2 * n_out, np.uint8)
+    out[0::2], out[1::2] = i, q
+    return out
+
+
+def crafted(name, rows, thr, seq=3, gap=0, check=None):
+    """One launch: ``rows`` (one uint8 [2 n_out] per channel) laid out with ``gap`` bytes of 255 behind every channel."""
+    rows = np.stack([np.asarray(r, np.uint8) for r in rows])
+    n_ch, n2 = rows.shape
+    chan = np.full((n_ch, n2 + gap), 255, np.uint8)
+    chan[:, :n2] = rows
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thr, np.uint64), (n_ch,)).astype(np.uint32))
+    cs = SimpleNamespace(name=name, rows=rows, chan=chan, stride=n2 + gap, n_ch=n_ch, n_out=n2 // 2, n_win=n2 // (2 * W),
+                         thr=thr, seq=seq)
+    cs.records, cs.floor = burst_model(rows, thr, seq & 0xFFFFFFFF)
+    if check is not None:
+        check(cs)
+    return cs
+
+
+def slot_model(cs):
+    """The whole slot the hook hands back: [n_ch][cap] record places - the channel's runs first, FILL behind them - and
+    the floor rows."""
+    cap = cap_of(cs.n_win)
+    recs = np.frombuffer(bytes([FILL]) * (cs.n_ch * cap * BURST_DTYPE.itemsize), BURST_DTYPE).reshape(cs.n_ch, cap).copy()
+    for c in range(cs.n_ch):
+        mine = cs.records[cs.records["channel"] == c]
+        assert mine.size == cs.floor["n_bursts"][c] <= cap
+        recs[c, : mine.size] = mine
+    return recs, cs.floor
+
+
+def _groups_between(rec):
+    """Whole groups of 64 windows inside the run that are neither its first nor its last."""
+    a, e = int(rec["first"]), int(rec["first"]) + int(rec["windows"]) - 1
+    return [g for g in range(a // 64 + 1, e // 64) if 64 * g >= a and 64 * g + 63 <= e]
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_small():
+    """Every crafted case but the largest chunk (which the GPU test alone launches; crafted_largest)."""
+    rng = np.random.default_rng(20260)
+    uni = lambda n_out: rng.integers(0, 256, 2 * n_out).astype(np.uint8)
+    out = []
+    # window counts around the 16 windows of a pass, the 64 of a group and the carried run: uniform bytes, median thresholds
+    for n_win in (1, 15, 16, 17, 63, 64, 65, 129, 192, 193):
+        rows = [uni(W * n_win) for _ in range(3)]
+        out.append(crafted(f"uniform_w{n_win}", rows, median_thresholds(np.stack(rows)), seq=n_win,
+                           gap=GAP if n_win in (17, 65, 193) else 0))
+    # designed runs: a carried run is carried again (c_win, c_pow, c_re, c_im accumulate)
+    def long_check(cs):
+        for c in range(cs.n_ch):
+            mine = cs.records[cs.records["channel"] == c]
+            assert mine.size == 1 and _groups_between(mine[0]), (cs.name, c, mine)
+    for n_win in (193, 256):
+        rows = []
+        for a, e in ((10, 140), (0, 192), (63, 128)):
+            r = quiet_bytes(rng, W * n_win)
+            r[2 * W * a: 2 * W * (e + 1)] = uni(W * (e + 1 - a))
+            rows.append(r)
+        cs = crafted(f"long_runs_w{n_win}", rows, 100000, gap=GAP if n_win == 193 else 0, check=long_check)
+        assert [(int(r["first"]), int(r["windows"])) for r in cs.records] == [(10, 131), (0, 193), (63, 66)]
+        out.append(cs)
+    # alternating ON / OFF: every record place of the channel that starts ON is filled
+    def alt_check(cs):
+        assert cs.floor["n_bursts"][0] == cap_of(cs.n_win) and cs.floor["n_bursts"][1] == cs.n_win // 2
+        assert np.all(cs.records["windows"] == 1)
+    for n_win in (64, 65, 129):
+        rows = []
+        for start_on in (1, 0):
+            r = quiet_bytes(rng, W * n_win).reshape(n_win, 2 * W)
+            on = (np.arange(n_win) % 2) != start_on
+            r[on] = rng.integers(0, 256, (int(on.sum()), 2 * W))
+            rows.append(r.reshape(-1))
+        out.append(crafted(f"alternating_w{n_win}", rows, 100000, check=alt_check))
+    # saturated bytes: the int32 / uint32 bounds of the kernel's header comment, per window and per lane
+    def sat_check(want):
+        def check(cs):
+            p, re, im = window_sums(cs.rows)
+            assert np.all(p == P_MAX), cs.name
+            for c, (wr, wi) in enumerate(want):
+                assert np.all(re[c] == wr * R_MAX) and np.all(im[c] == wi * R_MAX), (cs.name, c)
+                assert cs.records[c]["windows"] == cs.n_win and cs.records[c]["flags"] == 3
+        return check
+    out.append(crafted("saturated_re", [saturated(k, 64 * W) for k in ("zeros", "ones", "flip")], 0,
+                       check=sat_check([(1, 0), (1, 0), (-1, 0)])))
+    out.append(crafted("saturated_im", [saturated(k, 64 * W) for k in ("rot+", "rot-")], 0, gap=GAP,
+                       check=sat_check([(0, 1), (0, -1)])))
+    # the threshold at exactly p_w (the >=), one above it, 0 and 2^32 - 1, on the same bytes
+    def thr_check(cs):
+        on = [set(w for r in cs.records[cs.records["channel"] == c] for w in range(int(r["first"]), int(r["first"]) + int(r["windows"])))
+              for c in range(cs.n_ch)]
+        assert 5 in on[0] and 5 not in on[1] and on[0] - on[1] == {5}
+        assert on[2] == set(range(cs.n_win)) and on[3] == set() and cs.floor["windows_off"][3] == cs.n_win
+    row = uni(17 * W)
+    p5 = int(window_sums(row)[0][0, 5])
+    out.append(crafted("threshold_at_p_w", [row] * 4, [p5, p5 + 1, 0, 2 ** 32 - 1], check=thr_check))
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def crafted_largest():
+    """nW = 4096, the most rd_bursts_check admits: all of the kernel's LDS, one run of 4096 windows per channel, 64-bit
+    sums of 4096 saturated windows."""
+    def check(cs):
+        assert cs.records.size == 3 and np.all(cs.records["windows"] == 4096) and np.all(cs.records["flags"] == 3)
+        assert [int(x) for x in cs.records["power"]] == [68183654400] * 3 == [4096 * P_MAX] * 3
+        assert [int(x) for x in cs.records["corr_re"]] == [67650969600, -67650969600, 0]
+        assert [int(x) for x in cs.records["corr_im"]] == [0, 0, 4096 * R_MAX]
+    return crafted("largest_w4096", [saturated(k, 4096 * W) for k in ("ones", "flip", "rot+")], 0, seq=2 ** 32 + 9, check=check)
+
+
+BAD_N_OUT = (0, 127, 129, 4097 * W)                          # what rd_bursts_check refuses
+
+
 # ------------------------------------------------------------------------------------------ acquisition
 @functools.lru_cache(maxsize=None)
 def acq_capture(planted):

@@ -7,6 +7,7 @@
 //   host_asan file <in> <out> <S>      rd_packet records from <in>, kept indices (uint32) to <out>
 //   host_asan config <rounds> <seed>   rd_make_devcfg / rd_check_block_count / rd_ord_bucket_cap on random and extreme input
 //   host_asan waiter                   rd_waiter: deadline 0, a short deadline, the override hook
+//   host_asan repeats <msgs> <delivered> <out> <SL>   rd_burst_msg records through rd_bd_repeats, kept indices (uint32) to <out>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -153,7 +154,28 @@ static int waiter() {
     return 0;
 }
 
+// BURST DECODE step 7: rd_burst_msg records from <msgs> against those of <delivered>; the indices (uint32) of the records
+// rd_bd_repeats keeps go to <out>
+static int repeats_mode(const char *msgs, const char *delivered, const char *out, int sl) {
+    std::vector<rd_burst_msg> m, d;
+    for (int k = 0; k < 2; k++) {
+        FILE *f = fopen(k ? delivered : msgs, "rb");
+        if (!f) return fail("cannot open the records");
+        rd_burst_msg r;
+        while (fread(&r, sizeof r, 1, f) == 1) (k ? d : m).push_back(r);
+        fclose(f);
+    }
+    FILE *f = fopen(out, "wb");
+    if (!f) return fail("cannot open the output");
+    for (uint32_t i = 0; i < (uint32_t)m.size(); i++)
+        if (!rd_bd_repeats(m[i], d.data(), d.size(), sl)) fwrite(&i, sizeof i, 1, f);
+    fclose(f);
+    printf("repeats ok\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 6 && !strcmp(argv[1], "repeats")) return repeats_mode(argv[2], argv[3], argv[4], atoi(argv[5]));
     if (argc >= 4 && !strcmp(argv[1], "soak")) return soak(atoi(argv[2]), (unsigned)atoi(argv[3]));
     if (argc >= 5 && !strcmp(argv[1], "file")) return file_mode(argv[2], argv[3], atoi(argv[4]));
     if (argc >= 4 && !strcmp(argv[1], "config")) return config(atoi(argv[2]), (unsigned)atoi(argv[3]));

@@ -308,3 +308,90 @@ def test_symbols_layouts_and_the_ctypes_table():
     assert [getattr(ctype, f).offset for f in names] == [dtype.fields[f][1] for f in names]
     assert [C.sizeof(t) for _, t in ctype._fields_] == [dtype.fields[f][0].itemsize for f in names]
     assert dtype.fields["data"][1] == 48 and dtype.fields["ones"][1] == 58 and dtype.fields["id"][1] == 59
+
+
+# ------------------------------------------------------------------------------------------ crafted bytes and the seam
+def test_crafted_launches_reach_their_edges():
+    """burst_decode_cases builds every launch of the hook tests with its condition asserted on the model; here what spans
+    launches, and the second implementation of steps 4 .. 6 (candidates(), sample by sample in Python integers) against
+    decode_run on every run that gave a record."""
+    launches = DC.hook_launches()
+    assert len({L.name for L in launches}) == len(launches) == 11 + len(DC.GRID) and len(DC.GRID) == 13
+    assert {(L.cfg.packet_symbols, L.cfg.symbol_length) for L in launches} >= set(DC.GRID)
+    for L in launches:
+        cap = BC.cap_of(L.cfg.block_size // 128)
+        assert L.msgs.shape == (L.n_ch, cap) and L.runs.shape == (L.n_ch, cap)
+        for c in range(L.n_ch):
+            n = int(L.n_msgs[c])
+            assert L.msgs[c, n:].tobytes() == bytes([DC.FILL]) * ((cap - n) * BURST_MSG_DTYPE.itemsize)
+            assert np.all(L.msgs[c, :n]["channel"] == c) and not L.msgs[c, :n]["pad"].any()
+    for L in (DC.tie_launch(), DC.range_launch(), DC.need_launch(), DC.several_launch(), DC.overflow_launch(), DC.grid_launch(40, 1)):
+        for c in range(L.n_ch):
+            got = []
+            for r in range(min(int(L.n_runs[c]), L.runs.shape[1])):
+                cand = L.candidates(c, r)
+                if cand:
+                    best = max(m for _, m in cand)
+                    got.append((min(t for t, m in cand if m == best), best))
+            assert got == [(int(r["tau"]), int(r["margin"])) for r in L.records(c)], (L.name, c)
+    # the longest region, and both sides of MAX_W and of need
+    L = DC.longest_launch()
+    assert 128 * int(L.runs[0, 0]["windows"]) + DC.shape(L.cfg)[3] == 6144
+
+
+def test_the_seam_reports_a_packet_once_with_step_7_and_twice_without():
+    """A noise-free burst whose last output lies at boundary - SL .. boundary + SL: decode_model per chunk - the kernel's
+    definition, steps 1 .. 6 - reports the packet in both chunks for some positions; decode_stream, with the host's
+    step 7, exactly once for every position."""
+    data, b0, b1 = DC.seam_rows()
+    cfg = DC.config(DC.SEAM_SL, DC.SEAM_N, DC.SEAM_BS)
+    first, back, _ = DC.seam_launches()
+    twice = [last for c, last in enumerate(DC.SEAM_LAST) if first.n_msgs[c] and back.n_msgs[c]]
+    print(f"\n[seam model] reported by both chunks without step 7 at last = {twice}: {len(twice)} of {len(DC.SEAM_LAST)} positions")
+    assert len(twice) >= 1
+    for c in twice:                                          # (the same packet, a few outputs apart)
+        j = DC.SEAM_LAST.index(c)
+        a, b = first.msgs[j, 0], back.msgs[j, 0]
+        assert bytes(a["data"]) == bytes(b["data"]) == data and 0 < int(b["time"]) - int(a["time"]) < DC.SEAM_SL
+    out = DC.decode_stream([b0, b1], DC.THR, cfg)
+    for c, last in enumerate(DC.SEAM_LAST):
+        rows = [(k, r) for k, (_, m) in enumerate(out) for r in m.records if r["channel"] == c]
+        assert [bytes(r["data"]) for _, r in rows] == [data], (last, rows)
+        assert rows[0][0] == (0 if first.n_msgs[c] else 1)   # the chunk that found it first keeps it
+    # without flags & 1, or SL or more away, or after other data, nothing is dropped
+    m = out[1][1]
+    keep = DC.decode_model(b1, b0, out[1][0], cfg, True, DC.SEAM_BS)
+    far = keep.records.copy()
+    far["time"] += DC.SEAM_SL
+    assert DC.drop_repeats(keep, far, DC.SEAM_SL).records.size == keep.records.size > m.records.size
+    assert DC.drop_repeats(keep, out[0][1].records, 1).records.size == keep.records.size
+
+
+def test_debug_burst_decode_refuses_what_the_check_refuses():
+    """The hook's argument rule is rd_burst_decode_check's, before any device work: no GPU needed."""
+    from rtldavis_amd import _lib, dsp
+    L = _lib.lib()
+    cur = np.full(2 * 2048, 127, np.uint8)
+    runs, n_runs = np.zeros(8, BC.BURST_DTYPE), np.zeros(1, np.uint32)
+    msgs, out = np.zeros(8, BURST_MSG_DTYPE), np.zeros(3, np.uint32)
+
+    def call(cfg, stride=4096, cur_p=cur.ctypes.data):
+        rc = _lib.make_config(cfg.bit_rate, cfg.symbol_length, cfg.preamble_symbols, cfg.packet_symbols, cfg.preamble, cfg.block_size)
+        return L.rd_debug_burst_decode(C.byref(rc), cur_p, None, stride, 1, 0, 0, runs.ctypes.data, n_runs.ctypes.data,
+                                       msgs.ctypes.data, out[0:].ctypes.data, out[1:].ctypes.data, out[2:].ctypes.data)
+
+    P = RC.PREAMBLE
+    for cfg in (dsp.PacketConfig(19200, 14, 16, 88, P, 2048), dsp.PacketConfig(19200, 26, 16, 80, P, 4096), RC.packet_config(1024),
+                dsp.PacketConfig(19200, 51, 16, 64, P, 4096), dsp.PacketConfig(19200, 14, 16, 32, P, 2048)):
+        assert call(cfg) == _lib.RD_ERR_ARG and "burst decode" in _lib.last_error()
+    assert call(RC.packet_config(2048), stride=4096 - 16) == _lib.RD_ERR_ARG
+    assert call(RC.packet_config(2048), cur_p=None) == _lib.RD_ERR_ARG
+    assert not msgs.tobytes().strip(b"\0") and not out.any()
+
+
+def test_hook_prototypes_and_the_ctypes_table():
+    from rtldavis_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rtldavis_hip.h")).read(), flags=re.S)
+    for name, n_args in (("rd_debug_bursts", 8), ("rd_debug_burst_decode", 13)):
+        m = re.search(r"int\s+%s\s*\((.*?)\)\s*;" % name, src, flags=re.S)
+        assert m and len(m.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name][1]) and hasattr(_lib.lib(), name)

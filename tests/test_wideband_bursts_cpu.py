@@ -430,3 +430,47 @@ def test_symbols_layouts_and_the_ctypes_table():
         assert C.sizeof(ctype) == dtype.itemsize == size
         assert [getattr(ctype, f).offset for f in names] == [dtype.fields[f][1] for f in names]
         assert [C.sizeof(t) for _, t in ctype._fields_] == [dtype.fields[f][0].itemsize for f in names]
+
+
+# ------------------------------------------------------------------------------------------ crafted bytes
+def test_crafted_cases_reach_their_edges():
+    """burst_cases.crafted_small / crafted_largest build every case with its condition asserted on the model; here the
+    conditions that span cases, and the slot the hook must hand back."""
+    cases = {cs.name: cs for cs in BC.crafted_small() + (BC.crafted_largest(),)}
+    assert {cs.n_win for cs in cases.values()} >= {1, 15, 16, 17, 63, 64, 65, 129, 192, 193, 256, 4096}
+    assert any(cs.stride == 2 * cs.n_out + 16 and np.all(cs.chan[:, 2 * cs.n_out:] == 255) for cs in cases.values())
+    assert all(2 <= cs.n_ch <= 4 for cs in cases.values())
+    for cs in cases.values():
+        recs, floor = BC.slot_model(cs)
+        cap = BC.cap_of(cs.n_win)
+        assert recs.shape == (cs.n_ch, cap) and floor.shape == (cs.n_ch,)
+        for c in range(cs.n_ch):
+            n = int(floor["n_bursts"][c])
+            assert np.all(recs[c, :n]["channel"] == c) and np.all(np.diff(recs[c, :n]["first"].astype(np.int64)) > 1)
+            assert recs[c, n:].tobytes() == bytes([BC.FILL]) * ((cap - n) * BURST_DTYPE.itemsize)
+            assert int(floor["windows_off"][c]) + int(recs[c, :n]["windows"].sum()) == cs.n_win
+    # an odd window count with every place filled, and a carried run that is carried again in every long-run channel
+    assert cases["alternating_w129"].floor["n_bursts"][0] == 65 == BC.cap_of(129)
+    assert all(BC._groups_between(r) for n in (193, 256) for r in cases[f"long_runs_w{n}"].records)
+    # the largest sums: 32 bits are not enough for a run's power, 2^31 not for its correlation
+    big = cases["largest_w4096"]
+    assert int(big.records["power"][0]) == 68183654400 > 2 ** 32 and int(big.records["corr_re"][1]) == -67650969600 < -2 ** 31
+    assert big.floor["chunk"][0] == 9                        # the low 32 bits of seq
+
+
+def test_debug_bursts_refuses_what_rd_bursts_check_refuses():
+    """The hook's argument rule is rd_bursts_check's, before any device work: no GPU needed."""
+    from rtldavis_amd import _lib
+    L = _lib.lib()
+    chan = np.full(4096, 127, np.uint8)
+    thr = np.zeros(1, np.uint32)
+    recs, floor = np.zeros(8, BURST_DTYPE), np.zeros(1, BURST_FLOOR_DTYPE)
+    for n_out in BC.BAD_N_OUT:
+        stride = max(16, 2 * n_out + (-2 * n_out) % 16)
+        assert L.rd_debug_bursts(chan.ctypes.data, stride, 1, n_out, thr.ctypes.data, 0, recs.ctypes.data,
+                                 floor.ctypes.data) == _lib.RD_ERR_ARG, n_out
+        assert "bursts" in _lib.last_error()
+    assert L.rd_debug_bursts(chan.ctypes.data, 256 + 8, 1, 128, thr.ctypes.data, 0, recs.ctypes.data, floor.ctypes.data) == _lib.RD_ERR_ARG
+    assert L.rd_debug_bursts(chan.ctypes.data, 240, 1, 128, thr.ctypes.data, 0, recs.ctypes.data, floor.ctypes.data) == _lib.RD_ERR_ARG
+    assert L.rd_debug_bursts(None, 256, 1, 128, thr.ctypes.data, 0, recs.ctypes.data, floor.ctypes.data) == _lib.RD_ERR_ARG
+    assert not recs.tobytes().strip(b"\0") and not floor.tobytes().strip(b"\0")      # nothing was written
