@@ -605,7 +605,9 @@ void rd_debug_mfma_taps8s(uint16_t *vals, uint32_t *idx);
 /* Run k_demod_mfma alone on host data: g_out float [n_streams * tiles][2048][2] (kernel units),
  * bits_out the packed signs BEFORE the exact fix-up (words per stream = ceil(n_samples / 32)),
  * fix_out / n_fix the fix-up list it produced ((word index << 4) | group mask).  hist_mode: every
- * stream is preceded by hist_bytes of history (stride = hist_bytes + 2 n_samples, multiples of 16). */
+ * stream is preceded by hist_bytes of history (stride = hist_bytes + 2 n_samples, multiples of 16).
+ * With g_out the kernel instantiation that also dumps g runs; g_out == NULL launches the instantiation the
+ * product uses (no dump, the one global fix-up list) and returns bits_out, fix_out and n_fix alone. */
 int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_samples, int hist_mode,
                         uint32_t hist_bytes, float *g_out, uint32_t *bits_out, uint32_t *fix_out,
                         uint32_t fix_cap, uint32_t *n_fix);

@@ -44,7 +44,7 @@
 // predecessor exchange: three buffers of 64 x 16 B, then two carry slots (tile parity)
 // + the offset constant (four copies); a multiple of 32 so that XOR 16 toggles between the two carry slots
 #define RD_MF_XB_BYTES (3 * 1024 + 32 + 32)
-#define RD_MF_PEND 32        // entries a wave keeps before it appends them to the list (or to the groups' buckets)
+#define RD_MF_PEND 64        // a wave's pending entries: one tile can add 64 (a flagged word per lane), so a row holds a whole tile
 // tiles whose words are stored together (a multiple of 4 that divides the default chunk)
 #ifndef RD_MF_STAGE_TILES
 #define RD_MF_STAGE_TILES 4
@@ -717,6 +717,9 @@ __global__ __launch_bounds__(RD_MF_WG, RD_MF_MINWAVES) void k_demod_mfma(rd_layo
         if (DBG == 1 || DBG == 2 || DBG == 6) gmask = 0;
         const uint64_t fm = (any_flag || !carry) ? __ballot(gmask != 0) : 0;
         if (fm) {
+            // nf <= 64 = RD_MF_PEND: after the flush the tile's entries fit the wave's own row whatever their number (a row
+            // of 32 let a dense tile write into the next wave's: tests/test_gpu_near_ties.py)
+            static_assert(RD_MF_PEND >= 64, "a tile can list one word per lane");
             const uint32_t nf = (uint32_t)__popcll(fm);
             if (npend + nf > RD_MF_PEND) {
                 rd_mf_flush(mypend, npend, fix_list, fix_cap, counters, (uint32_t)lay.bits_stride, bucket_cnt);
@@ -910,6 +913,7 @@ bool rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix
 // (tile-major, [tiles][2048][2] floats in the kernel's units), the packed bits BEFORE any fix-up and
 // the fix-up list.  iq_host holds n_streams x n_samples x 2 bytes; hist_bytes >= 0 bytes of history
 // precede every stream when hist_mode is set (stream stride = 2 n_samples + hist_bytes).
+// g_out == NULL: the launch the product makes (k_demod_mfma<0, false>, one global list, no dump of g).
 extern "C" int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_samples, int hist_mode,
                                    uint32_t hist_bytes, float *g_out, uint32_t *bits_out, uint32_t *fix_out,
                                    uint32_t fix_cap, uint32_t *n_fix) {
@@ -933,8 +937,10 @@ extern "C" int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32
     RD_DBG_CHK(hipMalloc(&d_fix, (size_t)fix_cap * 4 + 4));
     RD_DBG_CHK(hipMalloc(&d_cnt, RD_CNT_TOTAL * 4));
     RD_DBG_CHK(hipMemset(d_cnt, 0, RD_CNT_TOTAL * 4));
-    RD_DBG_CHK(hipMalloc(&d_g, g_floats * 4));
-    RD_DBG_CHK(hipMemset(d_g, 0, g_floats * 4));
+    if (g_out) {
+        RD_DBG_CHK(hipMalloc(&d_g, g_floats * 4));
+        RD_DBG_CHK(hipMemset(d_g, 0, g_floats * 4));
+    }
     {
         rd_layout lay;
         lay.iq = d_iq + (hist_mode ? hist_bytes : 0);
@@ -948,7 +954,7 @@ extern "C" int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32
         rd_launch_demod_mfma(lay, d_fix, fix_cap, d_cnt, nullptr, nullptr, nullptr, d_g);
     }
     RD_DBG_CHK(hipDeviceSynchronize());
-    RD_DBG_CHK(hipMemcpy(g_out, d_g, g_floats * 4, hipMemcpyDeviceToHost));
+    if (g_out) RD_DBG_CHK(hipMemcpy(g_out, d_g, g_floats * 4, hipMemcpyDeviceToHost));
     RD_DBG_CHK(hipMemcpy(bits_out, d_bits, words * n_streams * 4, hipMemcpyDeviceToHost));
     {
         uint32_t cnt[RD_CNT_SLOTS];

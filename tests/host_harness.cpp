@@ -76,4 +76,10 @@ void hh_f64_stream(const uint8_t *iq, long n, double *filt, double *disc) {
 }
 
 float hh_threshold(float F) { return rd_run_threshold(F); }
+
+// the float64 form of the exact decision (k_fixup, k_tail) on given FIR outputs n = f[t-1], np = f[t] (integers as doubles)
+uint32_t hh_exact_bit_f64(double nx, double ny, double npx, double npy) {
+    rd_dd2 n = {nx, ny}, np = {npx, npy};
+    return rd_exact_bit_f64(n, np);
+}
 }

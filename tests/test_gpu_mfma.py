@@ -18,7 +18,8 @@ from rtldavis_amd.synth import synth_stream  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def run_kernel(streams: np.ndarray, hist: np.ndarray | None = None):
+def run_kernel(streams: np.ndarray, hist: np.ndarray | None = None, want_g: bool = True):
+    """want_g = False: the hook launches the instantiation the product uses (no dump of g); g comes back as None."""
     ns, nbytes = streams.shape
     n = nbytes // 2
     if hist is None:
@@ -28,12 +29,12 @@ def run_kernel(streams: np.ndarray, hist: np.ndarray | None = None):
         buf = np.ascontiguousarray(np.concatenate([hist, streams], axis=1))
     tiles = (n + M.TILE - 1) // M.TILE
     words = (n + 31) // 32
-    g = np.zeros((ns, tiles * M.TILE, 2), dtype=np.float32)
+    g = np.zeros((ns, tiles * M.TILE, 2), dtype=np.float32) if want_g else None
     bits = np.zeros((ns, words), dtype=np.uint32)
     cap = ns * words
     fix = np.zeros(cap, dtype=np.uint32)
     nfix = C.c_uint32(0)
-    rc = _lib.lib().rd_debug_demod_mfma(buf.ctypes.data, ns, n, hm, hb, g.ctypes.data, bits.ctypes.data,
+    rc = _lib.lib().rd_debug_demod_mfma(buf.ctypes.data, ns, n, hm, hb, g.ctypes.data if want_g else None, bits.ctypes.data,
                                         fix.ctypes.data, cap, C.byref(nfix))
     _lib.check(rc)
     assert nfix.value <= cap
@@ -51,8 +52,9 @@ def flagged_groups(fix: np.ndarray, ns: int, words: int) -> np.ndarray:
     return out
 
 
-def check(streams: np.ndarray, hist=None, chunk=6):
-    g, bits, fix = run_kernel(streams, hist)
+def check(streams: np.ndarray, hist=None, chunk=6, want_g=True, want_bits=False):
+    """want_bits: also return the packed words (tests/test_gpu_near_ties.py goes on from them)"""
+    g, bits, fix = run_kernel(streams, hist, want_g)
     ns, n = streams.shape[0], streams.shape[1] // 2
     words = (n + 31) // 32
     fl = flagged_groups(fix, ns, words)
@@ -61,15 +63,16 @@ def check(streams: np.ndarray, hist=None, chunk=6):
         # exact values in kernel units, index t = 0..n; without history the first outputs see made-up bytes
         gd = M.g_direct(streams[s], h if h is not None else np.full(18, 127, np.uint8)) * M.UNIT
         want = np.stack([gd.real, gd.imag], axis=1).astype(np.float32)  # one rounding, like the kernel's fma
-        got = g[s]
-        tl = np.arange(got.shape[0]) % M.TILE
-        t = np.arange(got.shape[0])
-        ok = (tl >= 1) & (t < n)   # the kernel computes outputs 1..2047 of a tile (2048 is the next tile's 0)
-        if hist is None:
-            ok &= t >= 9               # earlier outputs see the zero state, which the kernel leaves to the fix-up
-        else:
-            ok &= (t >= 1)
-        assert np.array_equal(got[ok], want[t[ok]]), f"stream {s}: g differs"
+        if want_g:
+            got = g[s]
+            tl = np.arange(got.shape[0]) % M.TILE
+            t = np.arange(got.shape[0])
+            ok = (tl >= 1) & (t < n)   # the kernel computes outputs 1..2047 of a tile (2048 is the next tile's 0)
+            if hist is None:
+                ok &= t >= 9               # earlier outputs see the zero state, which the kernel leaves to the fix-up
+            else:
+                ok &= (t >= 1)
+            assert np.array_equal(got[ok], want[t[ok]]), f"stream {s}: g differs"
         # signs
         if hist is None:
             _, _, ob = O.demod_stream_oneshot(streams[s])
@@ -89,6 +92,8 @@ def check(streams: np.ndarray, hist=None, chunk=6):
             assert fl[s][:4].all(), "first run of a stream must be re-evaluated exactly"
         else:
             assert fl[s][0]
+    if want_bits:
+        return fix, fl, bits
     return fix, fl
 
 
