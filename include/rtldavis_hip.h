@@ -545,6 +545,30 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  *      valid taus, so when its last symbol ends within SL outputs of the chunk boundary, chunk k can report a tau that
  *      ends before the boundary and chunk k+1 one that ends after it.  Step 7 drops the second report.
  *   6. at most one record per run: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
+ *   Repair (rd_wb_set_burst_repair; off by default, and then nothing below applies).  R = max_flips is 0, 1 or 2,
+ *   L = RD_BD_REPAIR_L = 8.  The CRC of rd_parse.h has init 0, so it is linear over GF(2): for 16 <= k < N, E[k] is the
+ *   CRC-16 of the bit-swapped bytes [2:] of the packet whose only set symbol is k, and flipping the symbols of a set F
+ *   turns a packet of syndrome S (the CRC of step 5, S != 0) into a valid one exactly when the E[k], k in F, XOR to S.
+ *   5a. a candidate tau that meets every condition of step 5 except the CRC gate is repairable when R > 0 and a flip set
+ *       exists by 5b.  The first 16 symbols must still equal sync exactly: sync symbols are never flipped.
+ *   5b. the flip set: rank the payload symbols k = 16 .. N-1 by |s[tau + SL k]| ascending, ties to the smaller k;
+ *       r_0 .. r_7 are the first L.  Subsets are tried in this order: the singles {r_a}, a ascending; then, if R = 2, the
+ *       pairs {r_a, r_b}, a < b, ordered by (a, b).  The flip set is the first subset whose E values XOR to S.  The order
+ *       is fixed because the answer is not unique: the generator x^16 + x^12 + x^5 + 1 is itself a codeword of weight
+ *       4, so two different pairs can share a syndrome.
+ *   6'. replaces step 6: at most one record per run; the candidates are ordered by (flips ascending, margin descending,
+ *       tau ascending), flips = 0 for a candidate that passes the CRC as it is; the margin of a repaired candidate is
+ *       the minimum of |s| over the symbols that were NOT flipped.  An exact candidate always beats a repaired one: a run
+ *       that yields a record at R = 0 yields the same record, bit for bit, at any R.
+ *   The record of a repaired candidate: flags bit 1 (RD_BURST_MSG_REPAIRED) is set; pad[0] = the number of flips, pad[1]
+ *   and pad[2] the flipped symbol indices ascending (pad[2] = 0 for one flip), pad[3] = 0; data, ones and id come from the
+ *   corrected symbols; tau, time, f_re, f_im and first are as for any record.  An unrepaired record has pad = 0 and bit 1
+ *   clear.  Step 7 is unchanged: it compares the corrected data and tests flags & 1 only.
+ *   What a repaired record proves: less than a CRC-proven one.  Against a random syndrome a candidate is accepted with
+ *   probability at most 8 / 65535 at R = 1 (8 singles) and at most 36 / 65535 at R = 2 (8 singles + 28 pairs), where an
+ *   exact candidate has 1 / 65536; and a real packet has about SL - 2 adjacent candidates, each with its own list.  Bit 1
+ *   is there so that the caller can treat the two classes differently (rtldavis_amd/acquire.py ignores repaired rows
+ *   unless asked).  Not repaired: flips inside the sync word, more than two flips, symbols outside the list.
  *   7. on the host, when the fetch of chunk k+1 copies the records out: a record with flags & 1 is dropped when its
  *      channel and data equal those of a record that the fetch of chunk k delivered (after its own drop) and its time
  *      differs from that record's by less than SL.  The device cannot do this: chunk k slices with another run's
@@ -566,22 +590,32 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  * rd_wb_burst_messages: the records of the chunk the last fetch returned, kept by that fetch - valid with later chunks in
  * flight, until the next fetch.  *n = the number of records; with cap < *n: RD_ERR_CAPACITY, nothing is lost, call again
  * (out may be NULL with cap = 0).  long_runs: NULL, or room for n_channels counts.  RD_ERR_STATE before any fetch and when
- * that chunk was submitted with decode off. */
+ * that chunk was submitted with decode off.
+ * rd_wb_set_burst_repair: max_flips = R for the chunks submitted from now on; 0 (the default) is the behaviour without
+ * repair, byte for byte.  RD_ERR_ARG outside 0 .. 2; RD_ERR_STATE unless the receiver is quiet and burst decode is on;
+ * rd_wb_set_burst_decode(w, 0) and rd_wb_set_bursts(w, 0) put it back to 0, rd_wideband_reset keeps it.  A chunk's records
+ * come from the value in force when it was submitted.  No device work (safe before fork).  rd_wb_burst_repair: the value
+ * the next submitted chunk will use. */
 #define RD_BURST_MSG_BYTES 10    /* packet_symbols / 8 at most */
+#define RD_BURST_MSG_REPAIRED 2u /* rd_burst_msg.flags: the symbols pad[1] (and pad[2]) were flipped to satisfy the CRC */
+#define RD_BD_REPAIR_L 8         /* the least reliable payload symbols a repair may flip */
 typedef struct rd_burst_msg {
     int32_t  channel;
     uint32_t first;          /* the run's first window (its rd_burst) */
     int32_t  tau;            /* the end of the first symbol, relative to the chunk's first output; may be negative */
-    uint32_t flags;          /* bit 0: the region reached into the previous chunk */
+    uint32_t flags;          /* bit 0: the region reached into the previous chunk; bit 1 (RD_BURST_MSG_REPAIRED): repaired */
     uint64_t time;           /* the chunk's absolute output clock + tau */
-    uint64_t margin;         /* min_i |s[tau + SL i]| */
+    uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped */
     int64_t  f_re, f_im;     /* sum of p[t] over the packet's N SL outputs tau - SL + 1 .. tau + SL (N - 1) */
     uint8_t  data[RD_BURST_MSG_BYTES];   /* on-air bytes, as rd_packet.data */
     uint8_t  ones;           /* symbols that are 1 */
     uint8_t  id;             /* transmitter id: bit-swapped data[2] & 7 */
-    uint8_t  pad[4];
+    uint8_t  pad[4];         /* all 0, or for a repaired record: pad[0] = flips (1, 2), pad[1] < pad[2] the flipped symbols
+                                (pad[2] = 0 for one flip), pad[3] = 0 */
 } rd_burst_msg;
 int rd_wb_set_burst_decode(rd_wideband *w, int enabled);
+int rd_wb_set_burst_repair(rd_wideband *w, int max_flips);
+int rd_wb_burst_repair(rd_wideband *w, int *max_flips);
 int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
@@ -620,12 +654,17 @@ int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_sample
  * RD_ERR_ARG with nothing launched for an n_out that rd_wb_set_bursts refuses.
  * rd_debug_burst_decode: n_out = cfg->block_size; cur / prev laid out alike (prev NULL: no chunk before); runs[n_ch][cap]
  * and n_runs[n_ch] are written into a burst slot as they are - records k_chan_bursts never writes included; per channel
- * the header comes back in n_msgs, long_runs and chunk. */
+ * the header comes back in n_msgs, long_runs and chunk.
+ * rd_debug_burst_decode_repair: the same with max_flips (0 .. 2, else RD_ERR_ARG before any device work);
+ * rd_debug_burst_decode is it with max_flips = 0. */
 int rd_debug_bursts(const uint8_t *chan, size_t stride, int n_ch, size_t n_out, const uint32_t *thr, uint64_t seq,
                     rd_burst *recs_out, rd_burst_floor *floor_out);
 int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                           uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs,
                           rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
+int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                 uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
+                                 rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,8 @@ SIGNATURES = {
     "rd_wb_bursts": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
     "rd_wb_set_burst_decode": (C.c_int, [_P, C.c_int]),
     "rd_wb_burst_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
+    "rd_wb_set_burst_repair": (C.c_int, [_P, C.c_int]),
+    "rd_wb_burst_repair": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
@@ -217,6 +219,8 @@ SIGNATURES = {
     "rd_debug_bursts": (C.c_int, [_P, C.c_size_t, C.c_int, C.c_size_t, _P, C.c_uint64, _P, _P]),
     "rd_debug_burst_decode": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, _P,
                                         _P, _P, _P, _P]),
+    "rd_debug_burst_decode_repair": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, _P,
+                                               C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

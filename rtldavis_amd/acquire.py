@@ -25,6 +25,10 @@ enough for a proposal - no ``need``, no waiting chunk, and a burst of any other 
     ...
     new = acq.update(b, rx.parsed(), rx.submitted, rx.burst_messages())
 
+With ``set_burst_repair`` some rows of ``burst_messages()`` are repaired ones (``repaired``, ``flipped_symbols``): the CRC
+was made to pass by flipping one or two weak symbols, which a random candidate survives up to 36 times as often as the
+CRC alone.  ``update`` ignores those rows unless the ``Acquisition`` was built with ``use_repaired=True``.
+
 Pure Python on the records' exact integers: the same records give the same decisions, on any machine; nothing here
 touches a device.
 """
@@ -38,6 +42,7 @@ import numpy as np
 WINDOW = 128                 # outputs per window of a burst record (wideband.BURST_WINDOW)
 THRESHOLD_OFF = 2 ** 32 - 1  # wideband.BURST_THRESHOLD_OFF
 FLAG_FIRST, FLAG_LAST = 1, 2
+MSG_REPAIRED = 2             # wideband.BURST_MSG_REPAIRED: bit 1 of a burst message's flags
 
 
 def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
@@ -60,6 +65,20 @@ def burst_message_offset_hz(row, out_rate: int, if_hz: int, deviation_hz: float 
     ``deviation_hz * (2 ones - packet_symbols) / packet_symbols`` above its carrier on average, and the bits are known."""
     f = math.atan2(int(row["f_im"]), int(row["f_re"])) * float(out_rate) / (2.0 * math.pi) - float(if_hz)
     return f - float(deviation_hz) * (2 * int(row["ones"]) - int(packet_symbols)) / float(packet_symbols)
+
+
+def repaired(records) -> np.ndarray:
+    """Boolean mask over ``burst_messages().records`` (or a ``BurstMessages``): the rows whose CRC passes only after the
+    flips in ``pad`` (``flags`` bit 1).  With ``set_burst_repair`` never called it is all False."""
+    recs = np.asarray(getattr(records, "records", records))
+    return (recs["flags"] & MSG_REPAIRED) != 0
+
+
+def flipped_symbols(row) -> Tuple[int, ...]:
+    """The symbol indices (0 = the first sync symbol) a repaired row had flipped, ascending: a tuple of 0, 1 or 2."""
+    if not int(row["flags"]) & MSG_REPAIRED:
+        return ()
+    return tuple(int(k) for k in row["pad"][1: 1 + int(row["pad"][0])])
 
 
 def merge(tail, bursts) -> Tuple[np.ndarray, np.ndarray]:
@@ -113,14 +132,15 @@ class Acquisition:
       optional - without it everything is as above): while not
       locked, a chunk ``>= valid_from`` that brings rows is proposed from at once, ``offset + round(median of
       burst_message_offset_hz over its rows)``; the CRC is the proof, so there is no ``need`` and no waiting chunk.
-      ``valid_from`` becomes ``submitted``, candidates and estimates are forgotten.
+      ``valid_from`` becomes ``submitted``, candidates and estimates are forgotten.  Repaired rows (``repaired``) are
+      left out unless ``use_repaired`` is set: they are not CRC-proven.
     - Once a CRC-valid message arrives, on any channel, the receiver is within reach of the AFC (``parsed()`` ->
       ``retune``): ``locked`` is set, the candidates and estimates are dropped - that channel's own burst among them - and
       nothing is proposed any more, until ``reset()``.
     """
 
     def __init__(self, n_channels: int, cfg, factor: int = 4, need: int = 3, min_windows: Optional[int] = None,
-                 max_windows: Optional[int] = None, if_hz: Optional[int] = None) -> None:
+                 max_windows: Optional[int] = None, if_hz: Optional[int] = None, use_repaired: bool = False) -> None:
         if int(n_channels) < 1 or int(factor) < 1 or int(need) < 1:
             raise ValueError("n_channels, factor and need must be positive")
         self.n_channels = int(n_channels)
@@ -130,6 +150,7 @@ class Acquisition:
         self.if_hz = -self.out_rate // 4 if if_hz is None else int(if_hz)     # (channelizer.plan_channels' default)
         self.factor = int(factor)
         self.need = int(need)
+        self.use_repaired = bool(use_repaired)
         self.min_windows = int(cfg.packet_symbols) * int(cfg.symbol_length) // WINDOW if min_windows is None else int(min_windows)
         self.max_windows = 2 * self.min_windows + 2 if max_windows is None else int(max_windows)
         if not 1 <= self.min_windows <= self.max_windows:
@@ -183,6 +204,8 @@ class Acquisition:
             self._forget()
             return None
         rows = [] if messages is None else np.asarray(getattr(messages, "records", messages))
+        if len(rows) and not self.use_repaired:
+            rows = rows[~repaired(rows)]
         if len(rows):
             est = [burst_message_offset_hz(r, self.out_rate, self.if_hz, self.deviation_hz, self.packet_symbols) for r in rows]
             self.offset += int(round(float(np.median(est))))

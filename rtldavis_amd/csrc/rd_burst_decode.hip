@@ -35,6 +35,16 @@
 // n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  The
 // burst records and the floor row are read from the burst slot where k_chan_bursts, earlier on the same stream, wrote
 // them (system-scope loads).  With the default thresholds there are no runs: the header is written and that is all.
+//
+// Repair (steps 5a, 5b, 6' of the header; rd_wb_set_burst_repair).  The kernel is a template on it: k_chan_burst_decode<false>
+// is the code above and is what max_flips = 0 launches; k_chan_burst_decode<true> adds, behind the sync test and the CRC
+// of a tau - where all but a few lanes have left -, for a candidate with syndrome S != 0: the L = 8 smallest (|s|, k) of
+// the payload symbols, kept sorted in registers by an unrolled insertion (64-bit magnitudes, ties to the smaller k); the
+// singles, then the pairs in (a, b) order against S through E[k], the CRC of the packet whose only set symbol is k - the
+// CRC has init 0 and is linear -, which the workgroup builds once into LDS (N x 16 bits); and the margin again without
+// the flipped symbols.  The reduction carries (flips, k1, k2) in one word beside (margin, tau) and orders by
+// (flips ascending, margin descending, tau ascending): still a total order, the same tree, the same four slots.  Thread 0
+// writes the corrected symbols.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -48,7 +58,9 @@ extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_
 #define RD_BD_MAX_REGION ((RD_BD_MAX_W + RD_BD_MAX_LOOK_W) * RD_BU_WINDOW)   // outputs of the longest region
 
 static_assert(sizeof(rd_burst_msg) == 64 && sizeof(rd_bd_header) == 16, "the slot layout of rd_bd_* (rd_internal.h)");
-static_assert(RD_BD_MAX_REGION * 10 <= 64 * 1024, "s (int64) and the bytes of the longest region: 60 KiB of LDS");
+static_assert(RD_BD_MAX_REGION * 10 + 2 * 8 * RD_BD_DATA_BYTES + 256 <= 64 * 1024,
+              "s (int64) and the bytes of the longest region, 60 KiB; the E table of the repair; 256 bytes of per-wave slots: under 64 KiB of LDS");
+static_assert(RD_BD_REPAIR_L == 8, "the pair loop and the record's pad[] are written for a list of 8");
 
 struct rd_bd_params {
     int sl, n_sym;             // SL, N
@@ -56,6 +68,7 @@ struct rd_bd_params {
     int look;                  // LOOK
     int have_prev;
     unsigned n_win, cap;
+    int max_flips;             // R (k_chan_burst_decode<true> alone reads it)
     uint64_t clock, seq;
 };
 
@@ -80,6 +93,16 @@ __device__ __forceinline__ bool rd_bd_better(uint64_t ma, int ta, uint64_t mb, i
     return ma > mb || (ma == mb && ta < tb);
 }
 
+// the same with the flips of step 6' in front: f = count | k1 << 8 | k2 << 16, 0 for an exact candidate
+__device__ __forceinline__ bool rd_bd_better_r(uint32_t fa, uint64_t ma, int ta, uint32_t fb, uint64_t mb, int tb) {
+    if (tb == INT32_MAX) return true;
+    if (ta == INT32_MAX) return false;
+    const uint32_t na = fa & 0xFFu, nb = fb & 0xFFu;
+    if (na != nb) return na < nb;
+    return ma > mb || (ma == mb && ta < tb);
+}
+
+template <bool REPAIR>
 __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
                                                                      size_t ch_stride, size_t n_out, rd_bd_params P,
                                                                      const rd_burst *runs, const rd_burst_floor *floor,
@@ -91,6 +114,8 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
     __shared__ int s_fr[RD_BD_THREADS / 64], s_fi[RD_BD_THREADS / 64];
     __shared__ uint32_t s_run[4];                        // n_bursts; first, windows, flags of the run in hand
     __shared__ int64_t s_corr[2];
+    __shared__ uint16_t s_E[8 * RD_BD_DATA_BYTES];       // (REPAIR) E[k], 16 <= k < N
+    __shared__ uint32_t s_f[RD_BD_THREADS / 64];         // (REPAIR) the waves' flips
     const int c = (int)blockIdx.x;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint8_t *src = cur + (size_t)c * ch_stride;
@@ -99,6 +124,14 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
     rd_burst_msg *out = recs + (size_t)c * P.cap;
     const uint16_t *zw = (const uint16_t *)s_z;           // output t0 + i: I in the low byte, Q in the high one
     if (tid == 0u) s_run[0] = rd_bd_sys_load(&floor[c].n_bursts);
+    if constexpr (REPAIR) {
+        // E[k]: symbol k is bit 7 - (k & 7) of on-air byte k >> 3, bit k & 7 of the bit-swapped byte
+        if ((int)tid >= 16 && (int)tid < P.n_sym) {
+            uint32_t crc = 0u;
+            for (int b = 2; b < P.n_sym >> 3; b++) crc = rd_crc16_step(crc, b == (int)(tid >> 3) ? 1u << (tid & 7u) : 0u);
+            s_E[tid] = (uint16_t)crc;
+        }
+    }
     __syncthreads();
     uint32_t n_runs = s_run[0];
     if (n_runs > P.cap) n_runs = P.cap;                   // (k_chan_bursts never writes more)
@@ -160,6 +193,7 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
         // ---- one lane per tau = t0 + i
         uint64_t best_m = 0ull;
         int best_t = INT32_MAX;
+        uint32_t best_f = 0u;
         const int i_hi = len - SL * (N - 1);              // i + SL (N - 1) < len
         for (int i = SL + (int)tid; i < i_hi; i += RD_BD_THREADS) {
             const int tau = t0 + i;
@@ -179,33 +213,112 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
                 word = ((word << 1) | bit) & 0xFFu;
                 if ((k & 7) == 7 && k >= 16) crc = rd_crc16_step(crc, rd_swap_bits8(word));
             }
-            if (ok && crc == 0u && rd_bd_better(margin, tau, best_m, best_t)) {
-                best_m = margin;
-                best_t = tau;
+            if constexpr (!REPAIR) {
+                if (ok && crc == 0u && rd_bd_better(margin, tau, best_m, best_t)) {
+                    best_m = margin;
+                    best_t = tau;
+                }
+            } else {
+                if (!ok) continue;
+                uint32_t fl = 0u;
+                if (crc != 0u) {                          // steps 5a, 5b: the syndrome S = crc
+                    uint64_t lm[RD_BD_REPAIR_L];          // the list, ascending in (|s|, k)
+                    int lk[RD_BD_REPAIR_L];
+#pragma unroll
+                    for (int a = 0; a < RD_BD_REPAIR_L; a++) {
+                        lm[a] = ~0ull;
+                        lk[a] = INT32_MAX;
+                    }
+                    for (int k = 16; k < N; k++) {
+                        const int64_t v = s_s[i + SL * k];
+                        uint64_t cm = (uint64_t)(v > 0 ? v : -v);
+                        int ck = k;
+#pragma unroll
+                        for (int a = 0; a < RD_BD_REPAIR_L; a++)
+                            if (cm < lm[a] || (cm == lm[a] && ck < lk[a])) {   // the entry moves in, the one it displaces goes on
+                                const uint64_t tm = lm[a];
+                                const int tk = lk[a];
+                                lm[a] = cm;
+                                lk[a] = ck;
+                                cm = tm;
+                                ck = tk;
+                            }
+                    }
+                    uint32_t e[RD_BD_REPAIR_L];
+#pragma unroll
+                    for (int a = 0; a < RD_BD_REPAIR_L; a++) e[a] = s_E[lk[a]];   // (N >= 40: 24 payload symbols, the list is full)
+#pragma unroll
+                    for (int a = 0; a < RD_BD_REPAIR_L; a++)
+                        if (fl == 0u && e[a] == crc) fl = 1u | ((uint32_t)lk[a] << 8);
+                    if (P.max_flips >= 2) {
+#pragma unroll
+                        for (int a = 0; a < RD_BD_REPAIR_L; a++)
+#pragma unroll
+                            for (int b = a + 1; b < RD_BD_REPAIR_L; b++)
+                                if (fl == 0u && (e[a] ^ e[b]) == crc) {
+                                    const uint32_t ka = (uint32_t)lk[a], kb = (uint32_t)lk[b];
+                                    fl = 2u | ((ka < kb ? ka : kb) << 8) | ((ka < kb ? kb : ka) << 16);
+                                }
+                    }
+                    if (fl == 0u) continue;
+                    const int k1 = (int)((fl >> 8) & 0xFFu), k2 = (fl & 0xFFu) == 2u ? (int)(fl >> 16) : -1;
+                    margin = ~0ull;                       // step 6': over the symbols that were not flipped
+                    for (int k = 0; k < N; k++) {
+                        if (k == k1 || k == k2) continue;
+                        const int64_t v = s_s[i + SL * k];
+                        const uint64_t mag = (uint64_t)(v > 0 ? v : -v);
+                        margin = mag < margin ? mag : margin;
+                    }
+                }
+                if (rd_bd_better_r(fl, margin, tau, best_f, best_m, best_t)) {
+                    best_f = fl;
+                    best_m = margin;
+                    best_t = tau;
+                }
             }
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const uint64_t om = (uint64_t)__shfl_xor((unsigned long long)best_m, off);
             const int ot = __shfl_xor(best_t, off);
-            if (rd_bd_better(om, ot, best_m, best_t)) {
-                best_m = om;
-                best_t = ot;
+            if constexpr (!REPAIR) {
+                if (rd_bd_better(om, ot, best_m, best_t)) {
+                    best_m = om;
+                    best_t = ot;
+                }
+            } else {
+                const uint32_t of = (uint32_t)__shfl_xor((int)best_f, off);
+                if (rd_bd_better_r(of, om, ot, best_f, best_m, best_t)) {
+                    best_f = of;
+                    best_m = om;
+                    best_t = ot;
+                }
             }
         }
         if (lane == 0u) {
             s_m[wave] = best_m;
             s_t[wave] = best_t;
+            if constexpr (REPAIR) s_f[wave] = best_f;
         }
         __syncthreads();
         best_m = s_m[0];
         best_t = s_t[0];
+        if constexpr (REPAIR) best_f = s_f[0];
 #pragma unroll
-        for (int wv = 1; wv < RD_BD_THREADS / 64; wv++)
-            if (rd_bd_better(s_m[wv], s_t[wv], best_m, best_t)) {
-                best_m = s_m[wv];
-                best_t = s_t[wv];
+        for (int wv = 1; wv < RD_BD_THREADS / 64; wv++) {
+            if constexpr (!REPAIR) {
+                if (rd_bd_better(s_m[wv], s_t[wv], best_m, best_t)) {
+                    best_m = s_m[wv];
+                    best_t = s_t[wv];
+                }
+            } else {
+                if (rd_bd_better_r(s_f[wv], s_m[wv], s_t[wv], best_f, best_m, best_t)) {
+                    best_f = s_f[wv];
+                    best_m = s_m[wv];
+                    best_t = s_t[wv];
+                }
             }
+        }
         if (best_t == INT32_MAX) continue;                // (uniform: every thread read the same four)
         // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
         const int i0 = best_t - t0;
@@ -231,7 +344,14 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             m->channel = c;
             m->first = first;
             m->tau = best_t;
-            m->flags = back ? 1u : 0u;
+            uint32_t n_flip = 0u;
+            int k1 = -1, k2 = -1;                         // the flipped symbols (REPAIR; none: -1)
+            if constexpr (REPAIR) {
+                n_flip = best_f & 0xFFu;
+                if (n_flip >= 1u) k1 = (int)((best_f >> 8) & 0xFFu);
+                if (n_flip == 2u) k2 = (int)((best_f >> 16) & 0xFFu);
+            }
+            m->flags = (back ? 1u : 0u) | (n_flip ? RD_BURST_MSG_REPAIRED : 0u);
             m->time = P.clock + (uint64_t)(int64_t)best_t;
             m->margin = best_m;
             int64_t sfr = 0, sfi = 0;
@@ -243,7 +363,8 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             m->f_im = sfi;
             uint32_t word = 0u, ones = 0u, id = 0u;
             for (int k = 0; k < N; k++) {
-                const uint32_t bit = s_s[i0 + SL * k] > 0 ? 1u : 0u;
+                uint32_t bit = s_s[i0 + SL * k] > 0 ? 1u : 0u;
+                if constexpr (REPAIR) bit ^= (k == k1 || k == k2) ? 1u : 0u;
                 ones += bit;
                 word = ((word << 1) | bit) & 0xFFu;
                 if ((k & 7) == 7) m->data[k >> 3] = (uint8_t)word;
@@ -252,7 +373,10 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             for (int k = N >> 3; k < RD_BD_DATA_BYTES; k++) m->data[k] = 0;
             m->ones = (uint8_t)ones;
             m->id = (uint8_t)id;
-            m->pad[0] = m->pad[1] = m->pad[2] = m->pad[3] = 0;
+            m->pad[0] = (uint8_t)n_flip;
+            m->pad[1] = (uint8_t)(n_flip >= 1u ? k1 : 0);
+            m->pad[2] = (uint8_t)(n_flip == 2u ? k2 : 0);
+            m->pad[3] = 0;
         }
         n_msgs++;
     }
@@ -290,7 +414,10 @@ int rd_burst_decode_check(const rd_config *cfg) {
 }
 
 int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
-                           size_t n_out, uint64_t clock, uint64_t seq, const void *burst_slot, void *slot, hipStream_t st) {
+                           size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const void *burst_slot, void *slot,
+                           hipStream_t st) {
+    if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
+        return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
     if (!chan_out || !burst_slot || !slot || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = rd_burst_decode_check(cfg);
     if (rc) return rc;
@@ -309,11 +436,19 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     P.cap = (unsigned)rd_bu_cap(n_win);
     P.clock = clock;
     P.seq = seq;
+    P.max_flips = max_flips;
     const uint8_t *bs = (const uint8_t *)burst_slot;
     uint8_t *base = (uint8_t *)slot;
-    hipLaunchKernelGGL(k_chan_burst_decode, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride, n_out, P,
-                       (const rd_burst *)bs, (const rd_burst_floor *)(bs + rd_bu_floor_offset(n_ch, n_win)), (rd_burst_msg *)base,
-                       (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win)));
+    const rd_burst *runs = (const rd_burst *)bs;
+    const rd_burst_floor *floor = (const rd_burst_floor *)(bs + rd_bu_floor_offset(n_ch, n_win));
+    rd_burst_msg *recs = (rd_burst_msg *)base;
+    rd_bd_header *hdr = (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win));
+    if (max_flips == 0)                               // today's kernel, instruction for instruction
+        hipLaunchKernelGGL(k_chan_burst_decode<false>, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride,
+                           n_out, P, runs, floor, recs, hdr);
+    else
+        hipLaunchKernelGGL(k_chan_burst_decode<true>, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride,
+                           n_out, P, runs, floor, recs, hdr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_decode: %s", hipGetErrorString(e));
     return RD_OK;
@@ -323,9 +458,12 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
 // rd_burst_decode_launch and mapped host slots as the receiver allocates them.  The caller's runs ([n_ch][cap]) and
 // n_runs go into a burst slot of the product's layout - records k_chan_bursts never writes included -; the message slot
 // is filled with 0xA5 before the launch and copied out whole, so the caller sees which places the kernel left alone.
-extern "C" int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
-                                     uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs,
-                                     rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+// rd_debug_burst_decode_repair (tests/test_burst_repair.py) is the same with max_flips; rd_debug_burst_decode is it at 0.
+extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                            uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
+                                            rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+    if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
+        return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
     if (!cfg || !cur || !runs || !n_runs || !msgs_out || !n_msgs || !long_runs || !chunk || n_ch < 1)
         return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = rd_burst_decode_check(cfg);
@@ -357,7 +495,7 @@ extern "C" int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, c
     }
     RD_DBG_CHK(hipHostGetDevicePointer(&d_bu, bu, 0));
     RD_DBG_CHK(hipHostGetDevicePointer(&d_bd, bd, 0));
-    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, d_bu, d_bd, nullptr);
+    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, max_flips, d_bu, d_bd, nullptr);
     if (rc) goto out;
     RD_DBG_CHK(hipDeviceSynchronize());
     memcpy(msgs_out, bd, rd_bd_header_offset(n_ch, n_win));
@@ -375,4 +513,10 @@ out:
     if (d_cur) hipFree(d_cur);
     if (d_prev) hipFree(d_prev);
     return rc;
+}
+
+extern "C" int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                     uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs,
+                                     rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+    return rd_debug_burst_decode_repair(cfg, cur, prev, stride, n_ch, clock, seq, runs, n_runs, 0, msgs_out, n_msgs, long_runs, chunk);
 }

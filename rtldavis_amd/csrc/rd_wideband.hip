@@ -46,7 +46,9 @@
 // queued behind k_chan_bursts, in front of the chunk's demodulator launch.  It reads the burst slot of the chunk's parity
 // (written by the kernel in front of it), d_out[s] and, for a run that begins with the chunk, the end of d_out[s ^ 1]:
 // chunk k-1's channelized bytes, next written by the channelizer of chunk k+1, later on the same stream.  Its records go
-// into a mapped pinned slot of the chunk's parity, which the fetch copies out like the burst records.
+// into a mapped pinned slot of the chunk's parity, which the fetch copies out like the burst records.  Repair
+// (rd_wb_set_burst_repair) is one integer the handle keeps and every submit hands to the launch, which picks the kernel
+// instantiation by it: no table, no copy, and with 0 the launch of a receiver that never heard of it.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -118,6 +120,7 @@ struct rd_wideband {
     // rd_bd_slot_bytes) and the records the last fetch kept
     rd_config cfg = {};
     bool decode = false, last_decode = false;
+    int repair = 0;                                // max_flips of the chunks submitted from now on (0 whenever decode is off)
     uint8_t *h_bd[2] = {nullptr, nullptr};
     std::vector<rd_burst_msg> bm_last;
     std::vector<uint32_t> bl_last;
@@ -394,7 +397,10 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         if (rc) return rc;
     }
     w->bursts = enabled != 0;
-    if (!w->bursts) w->decode = false;   // (the decoder reads the burst records)
+    if (!w->bursts) {                    // (the decoder reads the burst records)
+        w->decode = false;
+        w->repair = 0;
+    }
     return RD_OK;
 }
 
@@ -408,6 +414,24 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
         if (rc) return rc;
     }
     w->decode = enabled != 0;
+    if (!w->decode) w->repair = 0;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_repair(rd_wideband *w, int max_flips) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
+        return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before burst repair is switched", rd_demod_inflight(w->dem));
+    if (!w->decode) return rd_fail_msg(RD_ERR_STATE, "burst repair needs burst decode on (rd_wb_set_burst_decode)");
+    w->repair = max_flips;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_repair(rd_wideband *w, int *max_flips) {
+    if (!w || !max_flips) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *max_flips = w->repair;
     return RD_OK;
 }
 
@@ -538,7 +562,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
             void *bd = nullptr;
             WCHK(hipHostGetDevicePointer(&bd, w->h_bd[s], 0));
             rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
-                                        w->clock, (uint64_t)w->n_sub, bu, bd, w->st);
+                                        w->clock, (uint64_t)w->n_sub, w->repair, bu, bd, w->st);
             if (rc) return rc;
         }
     }

@@ -70,6 +70,9 @@ BURST_MSG_DTYPE = np.dtype([("channel", np.int32), ("first", np.uint32), ("tau",
                             ("data", np.uint8, (_lib.RD_BURST_MSG_BYTES,)), ("ones", np.uint8), ("id", np.uint8),
                             ("pad", np.uint8, (4,))])
 BURST_DECODE_MAX_WINDOWS = 32          # a longer run is counted in ``long_runs``, not decoded
+BURST_MSG_REPAIRED = 2                 # ``flags`` bit 1: ``pad[1]`` (and ``pad[2]``) were flipped to satisfy the CRC
+BURST_REPAIR_LIST = 8                  # the least reliable payload symbols a repair may flip
+BURST_REPAIR_MAX_FLIPS = 2
 
 
 class BurstMessages(NamedTuple):
@@ -354,6 +357,30 @@ class WidebandReceiver:
         at least that, rounded up to whole windows of 128.  Off (the default): nothing is launched."""
         _lib.check(_lib.lib().rd_wb_set_burst_decode(self._h, 1 if on else 0))
 
+    def set_burst_repair(self, max_flips: int) -> None:
+        """From the next chunk on, a burst whose sync word is right and whose CRC fails is repaired when flipping one
+        (``max_flips`` 1) or up to two (2) of its 8 least reliable payload symbols - those with the smallest |matched
+        filter output| - makes the CRC pass: singles first, then pairs, weakest first.  0 (the default) is the receiver
+        without repair, byte for byte.  A repaired row of ``burst_messages()`` has ``flags`` bit 1 set
+        (``BURST_MSG_REPAIRED``), ``pad[0]`` flips, ``pad[1] < pad[2]`` the flipped symbols, and ``data``, ``ones`` and
+        ``id`` corrected; ``acquire.repaired`` and ``acquire.flipped_symbols`` read them.  An exact candidate of a run
+        always wins over a repaired one, so every row without bit 1 is the row ``max_flips = 0`` gives.  A repaired row
+        proves less than a CRC-proven one: a random candidate passes with up to 8 / 65535 (one flip) or 36 / 65535 (two)
+        instead of 1 / 65536 - keep the two classes apart.  Needs a receiver with nothing in flight and
+        ``set_burst_decode(True)`` (RuntimeError; switching decode or bursts off puts it back to 0, ``reset()`` keeps
+        it); ValueError outside 0 .. 2 and for a bool."""
+        if isinstance(max_flips, (bool, np.bool_)) or not isinstance(max_flips, (int, np.integer)):
+            raise ValueError("max_flips: an integer in 0 .. 2")
+        if not 0 <= int(max_flips) <= BURST_REPAIR_MAX_FLIPS:
+            raise ValueError(f"max_flips {int(max_flips)}: 0 .. {BURST_REPAIR_MAX_FLIPS}")
+        _lib.check(_lib.lib().rd_wb_set_burst_repair(self._h, int(max_flips)))
+
+    def burst_repair(self) -> int:
+        """``max_flips`` the next submitted chunk will use (0: repair off)."""
+        r = C.c_int(0)
+        _lib.check(_lib.lib().rd_wb_burst_repair(self._h, C.byref(r)))
+        return int(r.value)
+
     def burst_messages(self) -> "BurstMessages":
         """Messages of the chunk the last ``fetch()`` returned - later chunks may be in flight - as exact integers.  Per
         run of ``bursts()`` of at most 32 windows (a run that begins with the chunk is extended LOOK_W windows back - a packet's
@@ -363,7 +390,8 @@ class WidebandReceiver:
         in this chunk), ``flags`` (bit 0: the region reached into the previous chunk), ``time`` (``tau`` on the receiver's
         absolute output clock), ``margin`` (the least |matched filter output| among the symbols), ``f_re`` / ``f_im`` (the
         lag-1 correlation summed over the packet: ``acquire.burst_message_offset_hz`` turns it into a frequency),
-        ``data`` (the on-air bytes, as ``Packet.data``: ``dsp.parse_packet`` takes them), ``ones`` and ``id``.  A burst
+        ``data`` (the on-air bytes, as ``Packet.data``: ``dsp.parse_packet`` takes them), ``ones`` and ``id``; ``pad`` is
+        zero unless ``set_burst_repair`` is on and the row was repaired (``flags`` bit 1).  A burst
         the demodulator decodes as well is reported here and in ``parsed()``: dedupe by channel, chunk and data.
         A packet that ends within ``symbol_length`` outputs of a chunk boundary can be found by both chunks; the fetch
         drops the later chunk's look-back row when the fetch before it delivered the same ``channel`` and ``data`` less

@@ -11,7 +11,8 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its 
 
     python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
                                     [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]]
-                                    [--burst-decode [--burst-decode-out FILE]] [--json OUT]
+                                    [--burst-decode [--burst-decode-out FILE]]
+                                    [--burst-repair N [--burst-repair-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -29,6 +30,12 @@ into --bursts-out (default profiles/wideband_bursts.txt).  The kernel's own time
 decode on (WidebandReceiver.set_burst_decode: k_chan_burst_decode behind k_chan_bursts; burst_messages() read after
 every fetch and handed to Acquisition.update with the rest).  Both go into --burst-decode-out (default
 profiles/wideband_burst_decode.txt); the comparison outside this run is the commit before with --bursts.
+--burst-repair N (1 or 2): as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts +
+decode + WidebandReceiver.set_burst_repair(N) on, and every channel's burst is DAMAGED: its payload is the CRC-invalid
+twin of a packet (synth.make_packet(..., flip_bit=...): one payload symbol wrong at full strength), so that every tau that
+passes the sync word runs the whole search of the repair - the list, the 8 singles, the 28 pairs - and, the wrong symbol
+being a strong one, mostly finds nothing.  Both go into --burst-repair-out (default profiles/wideband_burst_repair.txt),
+with the spread of the windows beside the difference.  The kernel's own time is not measured here.
 """
 import argparse
 import json
@@ -62,19 +69,31 @@ def main():
                     help="time every window with bursts on, and with bursts and burst decode on; write --burst-decode-out")
     ap.add_argument("--burst-decode-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                "wideband_burst_decode.txt"))
+    ap.add_argument("--burst-repair", type=int, default=0, choices=[0, 1, 2],
+                    help="time every window with bursts + decode on, and with repair of N flips on top, on damaged bursts; write --burst-repair-out")
+    ap.add_argument("--burst-repair-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                               "wideband_burst_repair.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
         raise SystemExit("--chunks >= 1, --repeats >= 1 and --capture-chunks >= 3")
     if args.bursts and args.burst_decode:
         raise SystemExit("--bursts or --burst-decode: each run compares two windows")
-    decode = args.burst_decode
+    repair = args.burst_repair
+    if repair and (args.bursts or args.burst_decode):
+        raise SystemExit("--burst-repair alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
     off = [f - CZ.DEFAULT_CENTRE_HZ for f in CZ.US_CHANNELS_HZ]
+    damaged = whole = None
+    if repair:                        # a CRC-invalid twin per channel: sync-valid, one payload symbol wrong
+        body = [bytes([(37 * c + j) & 0xFF for j in range(6)]) for c in range(len(off))]
+        damaged = [synth.make_packet(c % 8, body[c], flip_bit=(7 * c) % 64).hex() for c in range(len(off))]
+        whole = [synth.make_packet(c % 8, body[c]) for c in range(len(off))]     # what a right repair gives back
     raw, info = synth.synth_wideband(range(200, 200 + len(off)), off, nk * B, amplitude=0.05,
-                                     sample_format=args.sample_format)
+                                     sample_format=args.sample_format, **({"payloads": damaged} if repair else {}))
     rx = wideband.WidebandReceiver(cfg, sample_format=args.sample_format)
     rx.set_parse(args.parse)
     ctl = None
@@ -96,7 +115,7 @@ def main():
     moved = np.zeros(rx.n_channels, np.int64)
     moved[[25] if args.retune == "one" else slice(None)] = 1
 
-    bursts_on, decode_on, n_dmsgs = [False], [False], [0]
+    bursts_on, decode_on, n_dmsgs, n_repaired, n_right, base_msgs = [False], [False], [0], [0], [0], [0]
 
     def meter():
         if ctl is not None:
@@ -111,6 +130,10 @@ def main():
             if decode_on[0]:
                 msgs = rx.burst_messages()
                 n_dmsgs[0] += len(msgs.records)
+                if repair:
+                    rep = msgs.records[acquire.repaired(msgs.records)]
+                    n_repaired[0] += len(rep)
+                    n_right[0] += sum(bytes(r["data"]) == whole[int(r["channel"])] for r in rep)
             n_asked[0] += acq.update(b, rx.parsed() if args.parse else (), rx.submitted, msgs) is not None
 
     def run(n):
@@ -144,14 +167,18 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode(on and decode)
-                bursts_on[0], decode_on[0] = on or decode, on and decode
-                n_dmsgs[0] = 0
+                rx.set_burst_decode((on and decode) or repair > 0)
+                if repair:
+                    rx.set_burst_repair(repair if on else 0)
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0
+                n_dmsgs[0] = n_repaired[0] = n_right[0] = 0
                 acq.reset()
                 rx.set_burst_threshold(thr0)
                 n_bursts[0] = n_asked[0] = 0
             n_msgs[0] = 0
             (runs if on or not args.bursts else runs_off).append(run(args.chunks))
+            if not on:
+                base_msgs[0] = n_dmsgs[0]
     walls = [r[0] for r in runs]
     wall, lat, pk = sorted(runs, key=lambda r: r[0])[len(runs) // 2]   # the median window
     # the first pass over the capture (chunks 0 .. nk-1 after the reset): every channel's burst where it was injected
@@ -202,7 +229,29 @@ def main():
                 f"  all windows, wall s: bursts {' '.join(f'{r[0]:.3f}' for r in runs_off)}; bursts + decode {' '.join(f'{w:.3f}' for w in walls)}",
                 f"  last window with decode: {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages, {n_asked[0]} retunes proposed",
             ]
-        with open(args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        if repair:
+            res["burst_repair"] = {"max_flips": repair, "messages_last_window": n_dmsgs[0], "repaired_last_window": n_repaired[0],
+                                   "repaired_right_last_window": n_right[0], "messages_last_window_without": base_msgs[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            lines = [
+                f"WidebandReceiver burst repair (k_chan_burst_decode<true>, max_flips {repair}), bursts + decode + repair on against bursts + "
+                f"decode on in the same run: tools/wideband_stream.py --burst-repair {repair}" + (" --parse" if args.parse else ""),
+                lines[1] + "; every channel's burst is a CRC-invalid twin (one payload symbol wrong, full strength)",
+                f"  bursts + decode on:           {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + repair on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(burst_messages() read and handed to Acquisition.update per chunk)",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + repair {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: repair {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with repair: {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages of which {n_repaired[0]} repaired "
+                f"({n_right[0]} of those with the channel's undamaged payload), {n_asked[0]} retunes proposed; last window without: "
+                f"{base_msgs[0]} burst messages - the difference includes the host's handling of the additional rows",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
+        with open(args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
