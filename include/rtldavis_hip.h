@@ -569,6 +569,28 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  *   exact candidate has 1 / 65536; and a real packet has about SL - 2 adjacent candidates, each with its own list.  Bit 1
  *   is there so that the caller can treat the two classes differently (rtldavis_amd/acquire.py ignores repaired rows
  *   unless asked).  Not repaired: flips inside the sync word, more than two flips, symbols outside the list.
+ *   Narrow-band filter (rd_wb_set_burst_narrow; off by default, and then nothing below applies).  The channel filter
+ *   passes +-110 kHz because the carrier may be anywhere in it; a burst occupies about +-15 kHz, and the discriminator of
+ *   step 4 multiplies all of that noise with itself.  With the filter on, step 4 is replaced by 4n; steps 1 - 3, 5, 5a,
+ *   5b, 6, 6' and 7 run unchanged on the new s[t].  It needs SL >= 4.  G = RD_BD_NB_GRID = 64, T = 2 SL + 5 taps,
+ *   M = SL + 2.  Tables, designed on the host in float64 (rd_bd_narrow_table, rd_host.cpp), k = -M .. M:
+ *     w[k] = 0.54 + 0.46 cos(2 pi k / (T - 1));  h[k] = sinc(1.8 k / SL) w[k] / sum, sinc(x) = sin(pi x) / (pi x), the sum
+ *     (over k ascending) making sum_k h[k] = 1: a low-pass with its cutoff at 0.9 symbol rates;
+ *     H[g][k] = (rint(2^14 h[k] cos(a)), rint(2^14 h[k] sin(a))), a = 2 pi ((g k) mod 64) / 64 - the product reduced in
+ *     integers to 0 .. 63 before the call -, an int16 pair;  C[g] = (rint(2^14 cos(2 pi g / 64)), rint(2^14 sin(2 pi g / 64))).
+ *   4n. per run, after steps 1 - 3: sh = max(0, bitlength(max(|corr_re|, |corr_im|)) - 15), ca = corr_re >> sh,
+ *       cb = corr_im >> sh (arithmetic shifts: floor; not both 0, each in -2^15 .. 2^15 - 1); g = the smallest g that
+ *       maximises ca C[g].re + cb C[g].im (|score| < 2^30).  z[t] as above for t0 <= t < t1 and 0 outside the region - no
+ *       state, no load beyond the region.  acc[t] = sum_{k = -M .. M} H[g][k] z[t - k] (complex);
+ *       y[t] = (acc[t] + 2^10) >> 11 per component (RD_BD_NB_SHIFT, arithmetic shift).  The largest
+ *       sum_k (|H.re| + |H.im|) over g is 25633 at SL 4, 24727 at 8, 23986 at 14, 23471 at 25 and 23181 at 51, so
+ *       |acc| <= 255 x 25633 < 2^23 and |y| <= 3192 per component.  p'[t] = y[t] conj(y[t-1]) for t0 < t < t1 (components
+ *       < 2^25);  d[t] = im p'[t] ca - re p'[t] cb;  s[t] = sum_{i < SL} d[t - i] for t0 + SL <= t < t1: the SL-sums of p'
+ *       stay below 2^31 and |s| < 2^47;  bit[t] = s[t] > 0.
+ *   The record of a run decoded this way: flags bit 2 (RD_BURST_MSG_NARROW) is set; pad[3] = g; f_re, f_im = the sum of
+ *   p' over the packet's N SL outputs (< 2^36); margin is in the units of the new s - not comparable with a record
+ *   without bit 2; everything else as for any record.  Repair composes with it: pad = (flips, k1, k2, g),
+ *   flags = 4 | 2 | back.
  *   7. on the host, when the fetch of chunk k+1 copies the records out: a record with flags & 1 is dropped when its
  *      channel and data equal those of a record that the fetch of chunk k delivered (after its own drop) and its time
  *      differs from that record's by less than SL.  The device cannot do this: chunk k slices with another run's
@@ -595,27 +617,44 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  * repair, byte for byte.  RD_ERR_ARG outside 0 .. 2; RD_ERR_STATE unless the receiver is quiet and burst decode is on;
  * rd_wb_set_burst_decode(w, 0) and rd_wb_set_bursts(w, 0) put it back to 0, rd_wideband_reset keeps it.  A chunk's records
  * come from the value in force when it was submitted.  No device work (safe before fork).  rd_wb_burst_repair: the value
- * the next submitted chunk will use. */
+ * the next submitted chunk will use.
+ * rd_wb_set_burst_narrow: step 4n on / off for the chunks submitted from now on; off (the default) is the behaviour
+ * without it, byte for byte.  RD_ERR_STATE unless the receiver is quiet and burst decode is on; RD_ERR_ARG when switched
+ * on with symbol_length < 4; rd_wb_set_burst_decode(w, 0) and rd_wb_set_bursts(w, 0) switch it off, rd_wideband_reset
+ * keeps it.  A chunk's records come from the value in force when it was submitted.  No device work (safe before fork):
+ * the next submit uploads the tables.  rd_wb_burst_narrow: the value the next submitted chunk will use. */
 #define RD_BURST_MSG_BYTES 10    /* packet_symbols / 8 at most */
 #define RD_BURST_MSG_REPAIRED 2u /* rd_burst_msg.flags: the symbols pad[1] (and pad[2]) were flipped to satisfy the CRC */
 #define RD_BD_REPAIR_L 8         /* the least reliable payload symbols a repair may flip */
+#define RD_BURST_MSG_NARROW 4u   /* rd_burst_msg.flags: decoded behind the narrow-band filter of step 4n, pad[3] = g */
+#define RD_BD_NB_GRID 64         /* G: the centre frequencies of step 4n, g / 64 cycles per output */
+#define RD_BD_NB_SHIFT 11        /* y = (acc + 2^10) >> 11 */
+#define RD_BD_NB_MIN_SL 4        /* step 4n needs symbol_length >= 4 ... */
+#define RD_BD_NB_MAX_SL 51       /* ... and N SL + 1 <= 2048 with N >= 40 leaves no more: 2 SL + 5 <= 107 taps */
 typedef struct rd_burst_msg {
     int32_t  channel;
     uint32_t first;          /* the run's first window (its rd_burst) */
     int32_t  tau;            /* the end of the first symbol, relative to the chunk's first output; may be negative */
-    uint32_t flags;          /* bit 0: the region reached into the previous chunk; bit 1 (RD_BURST_MSG_REPAIRED): repaired */
+    uint32_t flags;          /* bit 0: the region reached into the previous chunk; bit 1 (RD_BURST_MSG_REPAIRED): repaired;
+                                bit 2 (RD_BURST_MSG_NARROW): step 4n */
     uint64_t time;           /* the chunk's absolute output clock + tau */
-    uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped */
-    int64_t  f_re, f_im;     /* sum of p[t] over the packet's N SL outputs tau - SL + 1 .. tau + SL (N - 1) */
+    uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped; in
+                                the units of step 4n when bit 2 is set: not comparable across the two kinds */
+    int64_t  f_re, f_im;     /* sum of p[t] (bit 2: of p'[t]) over the packet's N SL outputs tau - SL + 1 .. tau + SL (N - 1) */
     uint8_t  data[RD_BURST_MSG_BYTES];   /* on-air bytes, as rd_packet.data */
     uint8_t  ones;           /* symbols that are 1 */
     uint8_t  id;             /* transmitter id: bit-swapped data[2] & 7 */
-    uint8_t  pad[4];         /* all 0, or for a repaired record: pad[0] = flips (1, 2), pad[1] < pad[2] the flipped symbols
-                                (pad[2] = 0 for one flip), pad[3] = 0 */
+    uint8_t  pad[4];         /* pad[0 .. 2]: all 0, or for a repaired record pad[0] = flips (1, 2), pad[1] < pad[2] the flipped
+                                symbols (pad[2] = 0 for one flip); pad[3]: 0, or g of step 4n when flags bit 2 is set */
 } rd_burst_msg;
 int rd_wb_set_burst_decode(rd_wideband *w, int enabled);
 int rd_wb_set_burst_repair(rd_wideband *w, int max_flips);
 int rd_wb_burst_repair(rd_wideband *w, int *max_flips);
+int rd_wb_set_burst_narrow(rd_wideband *w, int on);
+int rd_wb_burst_narrow(rd_wideband *w, int *on);
+/* The tables of step 4n for symbol_length sl, designed on the host (no device is touched): taps = int16 [64][2 sl + 5][2],
+ * H[g][k] at [g][k + sl + 2] as (re, im); centres = int16 [64][2], C[g].  RD_ERR_ARG for sl outside 4 .. 51 or a null pointer. */
+int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres);
 int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
@@ -656,7 +695,9 @@ int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_sample
  * and n_runs[n_ch] are written into a burst slot as they are - records k_chan_bursts never writes included; per channel
  * the header comes back in n_msgs, long_runs and chunk.
  * rd_debug_burst_decode_repair: the same with max_flips (0 .. 2, else RD_ERR_ARG before any device work);
- * rd_debug_burst_decode is it with max_flips = 0. */
+ * rd_debug_burst_decode is it with max_flips = 0.
+ * rd_debug_burst_decode_narrow: the same with `narrow` (0 or 1, else RD_ERR_ARG; 1 with symbol_length < 4: RD_ERR_ARG), all
+ * before any device work; with narrow = 0 it hands back rd_debug_burst_decode_repair's bytes. */
 int rd_debug_bursts(const uint8_t *chan, size_t stride, int n_ch, size_t n_out, const uint32_t *thr, uint64_t seq,
                     rd_burst *recs_out, rd_burst_floor *floor_out);
 int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
@@ -665,6 +706,9 @@ int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_
 int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                                  uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
                                  rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
+int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                 uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
+                                 int narrow, rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,10 @@ With ``set_burst_repair`` some rows of ``burst_messages()`` are repaired ones (`
 was made to pass by flipping one or two weak symbols, which a random candidate survives up to 36 times as often as the
 CRC alone.  ``update`` ignores those rows unless the ``Acquisition`` was built with ``use_repaired=True``.
 
+With ``set_burst_narrow`` the rows are decoded behind a narrow-band filter at the burst's own frequency (``narrowband``):
+far more bursts decode in noise, and the rows are used like any others - the carrier estimate needs only the angle of
+``(f_re, f_im)``.
+
 Pure Python on the records' exact integers: the same records give the same decisions, on any machine; nothing here
 touches a device.
 """
@@ -43,6 +47,7 @@ WINDOW = 128                 # outputs per window of a burst record (wideband.BU
 THRESHOLD_OFF = 2 ** 32 - 1  # wideband.BURST_THRESHOLD_OFF
 FLAG_FIRST, FLAG_LAST = 1, 2
 MSG_REPAIRED = 2             # wideband.BURST_MSG_REPAIRED: bit 1 of a burst message's flags
+MSG_NARROW = 4               # wideband.BURST_MSG_NARROW: bit 2
 
 
 def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
@@ -72,6 +77,16 @@ def repaired(records) -> np.ndarray:
     flips in ``pad`` (``flags`` bit 1).  With ``set_burst_repair`` never called it is all False."""
     recs = np.asarray(getattr(records, "records", records))
     return (recs["flags"] & MSG_REPAIRED) != 0
+
+
+def narrowband(records) -> np.ndarray:
+    """Boolean mask over ``burst_messages().records`` (or a ``BurstMessages``): the rows decoded behind the narrow-band
+    filter (``flags`` bit 2; ``pad[3]`` is the filter's centre in 64ths of a cycle per output).  Their ``margin``, ``f_re``
+    and ``f_im`` are in the filter's units: ``burst_message_offset_hz`` uses only the angle of ``(f_re, f_im)`` and holds
+    for both kinds, and nothing in this module compares ``margin``.  With ``set_burst_narrow`` never called it is all
+    False."""
+    recs = np.asarray(getattr(records, "records", records))
+    return (recs["flags"] & MSG_NARROW) != 0
 
 
 def flipped_symbols(row) -> Tuple[int, ...]:

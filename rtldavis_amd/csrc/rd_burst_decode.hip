@@ -45,7 +45,24 @@
 // the flipped symbols.  The reduction carries (flips, k1, k2) in one word beside (margin, tau) and orders by
 // (flips ascending, margin descending, tau ascending): still a total order, the same tree, the same four slots.  Thread 0
 // writes the corrected symbols.
+//
+// Narrow-band filter (step 4n of the header; rd_wb_set_burst_narrow).  The second template argument: the two <*, false>
+// forms are the code above, the two <*, true> forms put, between the region's bytes and the sliding sums: the grid choice
+// - every wave scores the 64 centres, lane g its own, against (ca, cb) and reduces over (score, -g) by the fixed tree of
+// shuffles: a max over a total order, the same g in all four waves, no LDS, no atomics -; the T = 2 SL + 5 taps of H[g]
+// from the device table into LDS, as the two int16 pairs (re, -im) and (im, re) a complex product wants; the region as
+// int16 pairs (zi, zq) with SL + 2 zeros on both sides (the zero extension: no bounds test per tap) in the place of s,
+// which is not yet live; then y: a lane takes outputs tid + 256 j, four at a time in registers, per tap two LDS
+// broadcasts of the tap and, per output, one LDS word and two packed 16-bit dot products (v_dot2_i32_i16) - 4 T integer
+// multiply-adds per output, |acc| < 2^23 -; y = (acc + 2^10) >> 11 goes to LDS as a packed int16 pair, 24 KiB of its own
+// for the longest region, because p' reads y while s is written and the record's f sum reads it again.  That takes the
+// <*, true> forms to 85 KiB of static LDS (87024 and 87200 bytes) - one workgroup per CU where the others fit two; the grid is one workgroup per
+// channel, far fewer than the chip has CUs, so nothing waits for the second.  The sliding sums, the candidates and the
+// reduction then run as they are on p' = y conj(y[-1]) (components < 2^25, SL-sums < 2^31: int32) with (ca, cb) for the
+// correlation sum, |s| < 2^47; the record's f sum is widened to 64 bits before the lanes are added (< 2^36).
 #include <cstring>
+#include <type_traits>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -61,6 +78,11 @@ static_assert(sizeof(rd_burst_msg) == 64 && sizeof(rd_bd_header) == 16, "the slo
 static_assert(RD_BD_MAX_REGION * 10 + 2 * 8 * RD_BD_DATA_BYTES + 256 <= 64 * 1024,
               "s (int64) and the bytes of the longest region, 60 KiB; the E table of the repair; 256 bytes of per-wave slots: under 64 KiB of LDS");
 static_assert(RD_BD_REPAIR_L == 8, "the pair loop and the record's pad[] are written for a list of 8");
+#define RD_BD_NB_MAX_T (2 * RD_BD_NB_MAX_SL + 5)
+static_assert(RD_BD_NB_GRID == 64, "one lane of a wave per centre");
+static_assert((RD_BD_MAX_REGION + RD_BD_NB_MAX_T - 1) * 4 <= RD_BD_MAX_REGION * 8, "the padded int16 region lies in s's place");
+static_assert(RD_BD_MAX_REGION * 14 + 2 * 8 * RD_BD_DATA_BYTES + 2 * 4 * RD_BD_NB_MAX_T + 512 <= 160 * 1024,
+              "narrow: y (4 bytes per output) and the taps beside the rest, under gfx950's 160 KiB of LDS");
 
 struct rd_bd_params {
     int sl, n_sym;             // SL, N
@@ -86,6 +108,34 @@ __device__ __forceinline__ void rd_bd_p(const uint16_t *zw, int j, int &re, int 
     im = aq * pi - ai * pq;
 }
 
+// p'[t0 + j] = y[t0 + j] conj(y[t0 + j - 1]) from y in LDS, an int16 pair per word (j >= 1); |y| <= 3192: below 2^25
+__device__ __forceinline__ void rd_bd_pn(const uint32_t *y, int j, int &re, int &im) {
+    const uint32_t a = y[j], b = y[j - 1];
+    const int ar = (int)(int16_t)(a & 0xFFFFu), ai = (int)a >> 16;
+    const int br = (int)(int16_t)(b & 0xFFFFu), bi = (int)b >> 16;
+    re = ar * br + ai * bi;
+    im = ai * br - ar * bi;
+}
+
+// p at t0 + j, or p' behind the filter
+template <bool NARROW>
+__device__ __forceinline__ void rd_bd_pp(const uint16_t *zw, const uint32_t *y, int j, int &re, int &im) {
+    if constexpr (NARROW) rd_bd_pn(y, j, re, im);
+    else rd_bd_p(zw, j, re, im);
+}
+
+__device__ __forceinline__ uint32_t rd_bd_pack16(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+
+// c + a.lo b.lo + a.hi b.hi over int16 pairs, exact in int32
+typedef short rd_short2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int rd_bd_dot2(uint32_t a, uint32_t b, int c) {
+#if __has_builtin(__builtin_amdgcn_sdot2)
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(rd_short2, a), __builtin_bit_cast(rd_short2, b), c, false);
+#else
+    return c + (int)(int16_t)(a & 0xFFFFu) * (int)(int16_t)(b & 0xFFFFu) + ((int)a >> 16) * ((int)b >> 16);
+#endif
+}
+
 // (margin, tau) of lane a is the better candidate than that of lane b; tau = INT32_MAX: none
 __device__ __forceinline__ bool rd_bd_better(uint64_t ma, int ta, uint64_t mb, int tb) {
     if (tb == INT32_MAX) return true;
@@ -102,11 +152,12 @@ __device__ __forceinline__ bool rd_bd_better_r(uint32_t fa, uint64_t ma, int ta,
     return ma > mb || (ma == mb && ta < tb);
 }
 
-template <bool REPAIR>
+template <bool REPAIR, bool NARROW>
 __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
                                                                      size_t ch_stride, size_t n_out, rd_bd_params P,
                                                                      const rd_burst *runs, const rd_burst_floor *floor,
-                                                                     rd_burst_msg *recs, rd_bd_header *hdr) {
+                                                                     rd_burst_msg *recs, rd_bd_header *hdr,
+                                                                     const uint32_t *__restrict__ nb_tab) {
     __shared__ int64_t s_s[RD_BD_MAX_REGION];            // s[t0 + i] at i (i >= SL)
     __shared__ uint4 s_z[RD_BD_MAX_REGION / 8];          // the region's bytes: output t0 + i at bytes 2 i, 2 i + 1
     __shared__ uint64_t s_m[RD_BD_THREADS / 64];
@@ -116,6 +167,9 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
     __shared__ int64_t s_corr[2];
     __shared__ uint16_t s_E[8 * RD_BD_DATA_BYTES];       // (REPAIR) E[k], 16 <= k < N
     __shared__ uint32_t s_f[RD_BD_THREADS / 64];         // (REPAIR) the waves' flips
+    __shared__ uint32_t s_y[RD_BD_MAX_REGION];           // (NARROW) y[t0 + i] at i: re in the low half, im in the high one
+    __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // (NARROW) H[g][kk - M] as (re, -im) and (im, re)
+    __shared__ int64_t s_fr64[RD_BD_THREADS / 64], s_fi64[RD_BD_THREADS / 64];   // (NARROW) in the place of s_fr, s_fi
     const int c = (int)blockIdx.x;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint8_t *src = cur + (size_t)c * ch_stride;
@@ -160,7 +214,14 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
         const int t1 = RD_BU_WINDOW * (int)(first + windows);
         const int len = t1 - t0;                          // a multiple of 128, <= RD_BD_MAX_REGION
         if (len < need || len > RD_BD_MAX_REGION) continue;
-        const int32_t cr = (int32_t)cr64, ci = (int32_t)ci64;   // |corr| <= 32 x 254 x 65025 < 2^30
+        int nb_sh = 0, nb_g = 0;                          // (NARROW) sh and g of step 4n
+        if constexpr (NARROW) {
+            const int64_t mr = cr64 < 0 ? -cr64 : cr64, mi = ci64 < 0 ? -ci64 : ci64;
+            const int bl = 64 - __clzll((long long)(mr > mi ? mr : mi));   // (not both 0: at least 1)
+            nb_sh = bl > 15 ? bl - 15 : 0;
+        }
+        // |corr| <= 32 x 254 x 65025 < 2^30; NARROW: (ca, cb), in -2^15 .. 2^15 - 1
+        const int32_t cr = NARROW ? (int32_t)(cr64 >> nb_sh) : (int32_t)cr64, ci = NARROW ? (int32_t)(ci64 >> nb_sh) : (int32_t)ci64;
         // ---- the region's bytes
         for (int v = (int)tid; v < len / 8; v += RD_BD_THREADS) {
             const int t = t0 + 8 * v;                     // (t0 and 0 are multiples of 8: a vector lies in one chunk)
@@ -168,22 +229,85 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             s_z[v] = *(const uint4 *)g;
         }
         __syncthreads();
+        if constexpr (NARROW) {
+            const int T = 2 * SL + 5, M = SL + 2;
+            // ---- g: the smallest centre with the largest ca C.re + cb C.im (|score| < 2^30), the same in every wave
+            {
+                const uint32_t cw = nb_tab[RD_BD_NB_GRID * T + (int)lane];
+                int sc = cr * (int)(int16_t)(cw & 0xFFFFu) + ci * ((int)cw >> 16);
+                nb_g = (int)lane;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int os = __shfl_xor(sc, off), og = __shfl_xor(nb_g, off);
+                    if (os > sc || (os == sc && og < nb_g)) {
+                        sc = os;
+                        nb_g = og;
+                    }
+                }
+            }
+            if ((int)tid < T) {
+                const uint32_t hw = nb_tab[nb_g * T + (int)tid];
+                const int hr = (int)(int16_t)(hw & 0xFFFFu), hi = (int)hw >> 16;
+                s_hA[tid] = rd_bd_pack16(hr, -hi);
+                s_hB[tid] = rd_bd_pack16(hi, hr);
+            }
+            // ---- z as int16 pairs, output t0 + i at word i + M, zeros in front of the region and behind it
+            uint32_t *z16 = (uint32_t *)s_s;
+            for (int i = (int)tid; i < len + 2 * M; i += RD_BD_THREADS) {
+                const int j = i - M;
+                uint32_t zv = 0u;
+                if (j >= 0 && j < len) {
+                    const uint32_t a = zw[j];
+                    zv = rd_bd_pack16(2 * (int)(a & 0xFFu) - 255, 2 * (int)(a >> 8) - 255);
+                }
+                z16[i] = zv;
+            }
+            __syncthreads();
+            // ---- y[t0 + i] = (sum_kk H[g][kk - M] z[t0 + i - (kk - M)] + 2^10) >> 11: z[..] lies at word i + T - 1 - kk
+            for (int base = (int)tid; base < len; base += 4 * RD_BD_THREADS) {
+                int at[4], ar[4], ai[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int i = base + q * RD_BD_THREADS;
+                    at[q] = (i < len ? i : base) + T - 1;    // (an output past the region repeats the lane's first and is not stored)
+                    ar[q] = 0;
+                    ai[q] = 0;
+                }
+                for (int kk = 0; kk < T; kk++) {
+                    const uint32_t hA = s_hA[kk], hB = s_hB[kk];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const uint32_t zv = z16[at[q] - kk];
+                        ar[q] = rd_bd_dot2(hA, zv, ar[q]);
+                        ai[q] = rd_bd_dot2(hB, zv, ai[q]);
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int i = base + q * RD_BD_THREADS;
+                    if (i < len)
+                        s_y[i] = rd_bd_pack16((ar[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT,
+                                              (ai[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT);
+                }
+            }
+            __syncthreads();                              // y is whole, and z16 has been read: s may be written
+        }
         // ---- s[t0 + i], SL <= i < len: a lane takes a stretch of outputs and slides the two window sums along it
         const int per = (len - SL + RD_BD_THREADS - 1) / RD_BD_THREADS;
         const int ia = SL + (int)tid * per, ib = min(ia + per, len);
         if (ia < ib) {
             int sr = 0, si = 0, re, im;
             for (int j = ia - SL + 1; j <= ia; j++) {
-                rd_bd_p(zw, j, re, im);
+                rd_bd_pp<NARROW>(zw, s_y, j, re, im);
                 sr += re;
                 si += im;
             }
             s_s[ia] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
             for (int i = ia + 1; i < ib; i++) {
-                rd_bd_p(zw, i, re, im);
+                rd_bd_pp<NARROW>(zw, s_y, i, re, im);
                 sr += re;
                 si += im;
-                rd_bd_p(zw, i - SL, re, im);          // (i - SL >= 1: its pair lies in the region)
+                rd_bd_pp<NARROW>(zw, s_y, i - SL, re, im);          // (i - SL >= 1: its pair lies in the region)
                 sr -= re;
                 si -= im;
                 s_s[i] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
@@ -322,10 +446,11 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
         if (best_t == INT32_MAX) continue;                // (uniform: every thread read the same four)
         // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
         const int i0 = best_t - t0;
-        int fr = 0, fi = 0;                               // |.| <= 2048 x 2 x 255^2 < 2^29
+        // |.| <= 2048 x 2 x 255^2 < 2^29; NARROW: a lane's 8 terms of p' < 2^28, the packet's 2047 < 2^36
+        std::conditional_t<NARROW, long long, int> fr = 0, fi = 0;
         for (int j = i0 - SL + 1 + (int)tid; j <= i0 + SL * (N - 1); j += RD_BD_THREADS) {
             int re, im;
-            rd_bd_p(zw, j, re, im);
+            rd_bd_pp<NARROW>(zw, s_y, j, re, im);
             fr += re;
             fi += im;
         }
@@ -335,8 +460,13 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             fi += __shfl_xor(fi, off);
         }
         if (lane == 0u) {
-            s_fr[wave] = fr;
-            s_fi[wave] = fi;
+            if constexpr (NARROW) {
+                s_fr64[wave] = fr;
+                s_fi64[wave] = fi;
+            } else {
+                s_fr[wave] = fr;
+                s_fi[wave] = fi;
+            }
         }
         __syncthreads();
         if (tid == 0u) {                                  // field by field into the slot: no private copy of the record
@@ -351,13 +481,18 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
                 if (n_flip >= 1u) k1 = (int)((best_f >> 8) & 0xFFu);
                 if (n_flip == 2u) k2 = (int)((best_f >> 16) & 0xFFu);
             }
-            m->flags = (back ? 1u : 0u) | (n_flip ? RD_BURST_MSG_REPAIRED : 0u);
+            m->flags = (back ? 1u : 0u) | (n_flip ? RD_BURST_MSG_REPAIRED : 0u) | (NARROW ? RD_BURST_MSG_NARROW : 0u);
             m->time = P.clock + (uint64_t)(int64_t)best_t;
             m->margin = best_m;
             int64_t sfr = 0, sfi = 0;
             for (int wv = 0; wv < RD_BD_THREADS / 64; wv++) {
-                sfr += s_fr[wv];
-                sfi += s_fi[wv];
+                if constexpr (NARROW) {
+                    sfr += s_fr64[wv];
+                    sfi += s_fi64[wv];
+                } else {
+                    sfr += s_fr[wv];
+                    sfi += s_fi[wv];
+                }
             }
             m->f_re = sfr;
             m->f_im = sfi;
@@ -376,7 +511,7 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
             m->pad[0] = (uint8_t)n_flip;
             m->pad[1] = (uint8_t)(n_flip >= 1u ? k1 : 0);
             m->pad[2] = (uint8_t)(n_flip == 2u ? k2 : 0);
-            m->pad[3] = 0;
+            m->pad[3] = (uint8_t)nb_g;                     // (0 without NARROW)
         }
         n_msgs++;
     }
@@ -413,14 +548,34 @@ int rd_burst_decode_check(const rd_config *cfg) {
     return rd_bursts_check((size_t)cfg->block_size);
 }
 
+int rd_bd_narrow_upload(int sl, uint32_t **d_tab) {
+    if (!d_tab) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (sl < RD_BD_NB_MIN_SL || sl > RD_BD_NB_MAX_SL)
+        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, not %d .. %d", sl, RD_BD_NB_MIN_SL, RD_BD_NB_MAX_SL);
+    const size_t T = 2 * (size_t)sl + 5, n = RD_BD_NB_GRID * T + RD_BD_NB_GRID;
+    std::vector<int16_t> tab(2 * n);                    // taps, then centres: (re, im) is one little-endian word
+    int rc = rd_bd_narrow_table(sl, tab.data(), tab.data() + 2 * RD_BD_NB_GRID * T);
+    if (rc) return rd_fail_msg(rc, "narrow-band filter: no table for symbol_length %d", sl);
+    uint32_t *d = nullptr;
+    if (hipMalloc(&d, n * sizeof(uint32_t)) != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "hipMalloc of the narrow-band table failed");
+    if (hipMemcpy(d, tab.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return rd_fail_msg(RD_ERR_DEVICE, "hipMemcpy of the narrow-band table failed");
+    }
+    *d_tab = d;
+    return RD_OK;
+}
+
 int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
-                           size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const void *burst_slot, void *slot,
-                           hipStream_t st) {
+                           size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const uint32_t *narrow_tab,
+                           const void *burst_slot, void *slot, hipStream_t st) {
     if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
         return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
     if (!chan_out || !burst_slot || !slot || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = rd_burst_decode_check(cfg);
     if (rc) return rc;
+    if (narrow_tab && cfg->symbol_length < RD_BD_NB_MIN_SL)   // (at most RD_BD_NB_MAX_SL by the check above)
+        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
     if (n_out != (size_t)cfg->block_size || out_stride < 2 * n_out || (out_stride & 15) || ((uintptr_t)chan_out & 15) ||
         ((uintptr_t)chan_prev & 15) || ((uintptr_t)slot & 15))
         return rd_fail_msg(RD_ERR_ARG, "burst decode: stride %zu for %zu outputs, or a misaligned buffer", out_stride, n_out);
@@ -443,12 +598,17 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     const rd_burst_floor *floor = (const rd_burst_floor *)(bs + rd_bu_floor_offset(n_ch, n_win));
     rd_burst_msg *recs = (rd_burst_msg *)base;
     rd_bd_header *hdr = (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win));
-    if (max_flips == 0)                               // today's kernel, instruction for instruction
-        hipLaunchKernelGGL(k_chan_burst_decode<false>, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride,
-                           n_out, P, runs, floor, recs, hdr);
-    else
-        hipLaunchKernelGGL(k_chan_burst_decode<true>, dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, out_stride,
-                           n_out, P, runs, floor, recs, hdr);
+#define RD_BD_LAUNCH(REPAIR, NARROW)                                                                                          \
+    hipLaunchKernelGGL((k_chan_burst_decode<REPAIR, NARROW>), dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, \
+                       out_stride, n_out, P, runs, floor, recs, hdr, narrow_tab)
+    if (!narrow_tab) {
+        if (max_flips == 0) RD_BD_LAUNCH(false, false);   // the kernels from before step 4n, instruction for instruction
+        else RD_BD_LAUNCH(true, false);
+    } else {
+        if (max_flips == 0) RD_BD_LAUNCH(false, true);
+        else RD_BD_LAUNCH(true, true);
+    }
+#undef RD_BD_LAUNCH
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_decode: %s", hipGetErrorString(e));
     return RD_OK;
@@ -459,11 +619,17 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
 // n_runs go into a burst slot of the product's layout - records k_chan_bursts never writes included -; the message slot
 // is filled with 0xA5 before the launch and copied out whole, so the caller sees which places the kernel left alone.
 // rd_debug_burst_decode_repair (tests/test_burst_repair.py) is the same with max_flips; rd_debug_burst_decode is it at 0.
-extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+// rd_debug_burst_decode_narrow (tests/test_burst_narrow.py) is the same with `narrow`: 1 uploads the table of step 4n for
+// the launch; rd_debug_burst_decode_repair is it at 0.
+extern "C" int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                                             uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
-                                            rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+                                            int narrow, rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs,
+                                            uint32_t *chunk) {
     if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
         return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
+    if (narrow != 0 && narrow != 1) return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: narrow %d, not 0 or 1", narrow);
+    if (narrow && cfg && cfg->symbol_length < RD_BD_NB_MIN_SL)
+        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
     if (!cfg || !cur || !runs || !n_runs || !msgs_out || !n_msgs || !long_runs || !chunk || n_ch < 1)
         return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = rd_burst_decode_check(cfg);
@@ -474,6 +640,7 @@ extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t 
     if (rc) return rc;
     const size_t n_win = n_out / RD_BU_WINDOW, bu_bytes = rd_bu_slot_bytes(n_ch, n_win), bd_bytes = rd_bd_slot_bytes(n_ch, n_win);
     uint8_t *d_cur = nullptr, *d_prev = nullptr, *bu = nullptr, *bd = nullptr;
+    uint32_t *d_nb = nullptr;
     void *d_bu = nullptr, *d_bd = nullptr;
 #define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
     RD_DBG_CHK(hipMalloc(&d_cur, (size_t)n_ch * stride));
@@ -495,7 +662,8 @@ extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t 
     }
     RD_DBG_CHK(hipHostGetDevicePointer(&d_bu, bu, 0));
     RD_DBG_CHK(hipHostGetDevicePointer(&d_bd, bd, 0));
-    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, max_flips, d_bu, d_bd, nullptr);
+    if (narrow && (rc = rd_bd_narrow_upload(cfg->symbol_length, &d_nb))) goto out;
+    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, max_flips, d_nb, d_bu, d_bd, nullptr);
     if (rc) goto out;
     RD_DBG_CHK(hipDeviceSynchronize());
     memcpy(msgs_out, bd, rd_bd_header_offset(n_ch, n_win));
@@ -512,7 +680,15 @@ out:
     if (bd) hipHostFree(bd);
     if (d_cur) hipFree(d_cur);
     if (d_prev) hipFree(d_prev);
+    if (d_nb) hipFree(d_nb);
     return rc;
+}
+
+extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                                            uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
+                                            rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk) {
+    return rd_debug_burst_decode_narrow(cfg, cur, prev, stride, n_ch, clock, seq, runs, n_runs, max_flips, 0, msgs_out, n_msgs,
+                                        long_runs, chunk);
 }
 
 extern "C" int rd_debug_burst_decode(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,

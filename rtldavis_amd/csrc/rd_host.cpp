@@ -3,6 +3,7 @@
 #include "rd_host.h"
 #include "rd_parse.h"
 
+#include <math.h>
 #include <sched.h>
 #include <stdlib.h>
 #include <string.h>
@@ -234,4 +235,34 @@ bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
         if (q.channel == m.channel && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
     }
     return false;
+}
+
+// BURST DECODE step 4n (include/rtldavis_hip.h): designed in float64, every product and quotient in the order written
+// there - tests/burst_narrow_cases.py evaluates the same expressions in NumPy and must get the same integers.
+extern "C" int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres) {
+    if (sl < RD_BD_NB_MIN_SL || sl > RD_BD_NB_MAX_SL || !taps || !centres) return RD_ERR_ARG;
+    const int T = 2 * sl + 5, M = sl + 2;
+    const double pi = 3.141592653589793;
+    std::vector<double> h((size_t)T);
+    double sum = 0.0;
+    for (int k = -M; k <= M; k++) {
+        const double w = 0.54 + 0.46 * cos(2.0 * pi * (double)k / (double)(T - 1));
+        const double x = 1.8 * (double)k / (double)sl;
+        const double sinc = k == 0 ? 1.0 : sin(pi * x) / (pi * x);
+        h[(size_t)(k + M)] = sinc * w;
+        sum += h[(size_t)(k + M)];
+    }
+    for (int k = 0; k < T; k++) h[(size_t)k] /= sum;
+    for (int g = 0; g < RD_BD_NB_GRID; g++) {
+        for (int k = -M; k <= M; k++) {
+            const int m = (((g * k) % RD_BD_NB_GRID) + RD_BD_NB_GRID) % RD_BD_NB_GRID;   // reduced in integers
+            const double a = 2.0 * pi * (double)m / (double)RD_BD_NB_GRID, hk = 16384.0 * h[(size_t)(k + M)];
+            taps[2 * ((size_t)g * (size_t)T + (size_t)(k + M))] = (int16_t)rint(hk * cos(a));
+            taps[2 * ((size_t)g * (size_t)T + (size_t)(k + M)) + 1] = (int16_t)rint(hk * sin(a));
+        }
+        const double a = 2.0 * pi * (double)g / (double)RD_BD_NB_GRID;
+        centres[2 * g] = (int16_t)rint(16384.0 * cos(a));
+        centres[2 * g + 1] = (int16_t)rint(16384.0 * sin(a));
+    }
+    return RD_OK;
 }

@@ -265,7 +265,10 @@ int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_
 //   [n_ch][cap] rd_burst_msg | [n_ch] rd_bd_header                                    cap = rd_bu_cap(n_win)
 // The kernel writes every header and, per channel, the first header.n_msgs of its cap record places.
 // max_flips: R of the header's steps 5a / 5b / 6' (0 .. RD_BD_MAX_FLIPS, else RD_ERR_ARG and nothing launched); 0 launches
-// the kernel without repair.
+// the kernel without repair.  narrow_tab: null, or the device table of rd_bd_narrow_upload for cfg's symbol_length - then
+// step 4n runs (RD_ERR_ARG with symbol_length < RD_BD_NB_MIN_SL).  rd_bd_narrow_upload: *d_tab = a device buffer of
+// 64 x (2 sl + 5) taps and 64 centres, an int16 pair (re low, im high) per uint32, filled from rd_bd_narrow_table by a
+// blocking copy; the caller frees it with hipFree.
 #define RD_BD_MAX_W 32          /* a run of more windows is counted, not decoded */
 #define RD_BD_MAX_LOOK_W 16     /* packet_symbols * symbol_length + 1 <= 2048 */
 #define RD_BD_DATA_BYTES RD_BURST_MSG_BYTES
@@ -280,8 +283,9 @@ static inline size_t rd_bd_slot_bytes(int n_ch, size_t n_win) { return rd_bd_hea
 int rd_bd_look_windows(const rd_config *cfg);
 int rd_burst_decode_check(const rd_config *cfg);
 int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
-                           size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const void *burst_slot, void *slot,
-                           hipStream_t st);
+                           size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const uint32_t *narrow_tab,
+                           const void *burst_slot, void *slot, hipStream_t st);
+int rd_bd_narrow_upload(int sl, uint32_t **d_tab);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

@@ -48,7 +48,10 @@
 // chunk k-1's channelized bytes, next written by the channelizer of chunk k+1, later on the same stream.  Its records go
 // into a mapped pinned slot of the chunk's parity, which the fetch copies out like the burst records.  Repair
 // (rd_wb_set_burst_repair) is one integer the handle keeps and every submit hands to the launch, which picks the kernel
-// instantiation by it: no table, no copy, and with 0 the launch of a receiver that never heard of it.
+// instantiation by it: no table, no copy, and with 0 the launch of a receiver that never heard of it.  The narrow-band
+// filter (rd_wb_set_burst_narrow) is one flag kept the same way and one device table (rd_bd_narrow_upload: 64 x (2 SL + 5)
+// taps and the 64 centres, designed on the host) that the first submit with the flag set uploads, as the spectrum's tables
+// are; the launch gets the table when the flag is set and a null pointer otherwise, and picks the instantiation by it.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -121,6 +124,8 @@ struct rd_wideband {
     rd_config cfg = {};
     bool decode = false, last_decode = false;
     int repair = 0;                                // max_flips of the chunks submitted from now on (0 whenever decode is off)
+    bool narrow = false;                           // step 4n for the chunks submitted from now on (false whenever decode is off)
+    uint32_t *d_nb = nullptr;                      // its tables on the device, once a submit has needed them
     uint8_t *h_bd[2] = {nullptr, nullptr};
     std::vector<rd_burst_msg> bm_last;
     std::vector<uint32_t> bl_last;
@@ -213,6 +218,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_bd[i]);
         }
         hipFree(w->d_lvacc);
+        hipFree(w->d_nb);
     }
     rd_spec_destroy(w->spec);   // (checks the owning process itself)
     rd_chan_destroy(w->chan);
@@ -299,6 +305,7 @@ static int wb_alloc_decode(rd_wideband *w) {
             WCHK(hipHostMalloc((void **)&w->h_bd[i], rd_bd_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
             memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));   // (a message count no chunk can have)
         }
+    if (w->narrow && !w->d_nb) return rd_bd_narrow_upload(w->cfg.symbol_length, &w->d_nb);
     return RD_OK;
 }
 
@@ -400,6 +407,7 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
     if (!w->bursts) {                    // (the decoder reads the burst records)
         w->decode = false;
         w->repair = 0;
+        w->narrow = false;
     }
     return RD_OK;
 }
@@ -414,7 +422,10 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
         if (rc) return rc;
     }
     w->decode = enabled != 0;
-    if (!w->decode) w->repair = 0;
+    if (!w->decode) {
+        w->repair = 0;
+        w->narrow = false;
+    }
     return RD_OK;
 }
 
@@ -432,6 +443,23 @@ extern "C" int rd_wb_set_burst_repair(rd_wideband *w, int max_flips) {
 extern "C" int rd_wb_burst_repair(rd_wideband *w, int *max_flips) {
     if (!w || !max_flips) return rd_fail_msg(RD_ERR_ARG, "null argument");
     *max_flips = w->repair;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_narrow(rd_wideband *w, int on) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before the narrow-band filter is switched", rd_demod_inflight(w->dem));
+    if (!w->decode) return rd_fail_msg(RD_ERR_STATE, "the narrow-band filter needs burst decode on (rd_wb_set_burst_decode)");
+    if (on && w->cfg.symbol_length < RD_BD_NB_MIN_SL)
+        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, at least %d", w->cfg.symbol_length, RD_BD_NB_MIN_SL);
+    w->narrow = on != 0;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_narrow(rd_wideband *w, int *on) {
+    if (!w || !on) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *on = w->narrow ? 1 : 0;
     return RD_OK;
 }
 
@@ -562,7 +590,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
             void *bd = nullptr;
             WCHK(hipHostGetDevicePointer(&bd, w->h_bd[s], 0));
             rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
-                                        w->clock, (uint64_t)w->n_sub, w->repair, bu, bd, w->st);
+                                        w->clock, (uint64_t)w->n_sub, w->repair, w->narrow ? w->d_nb : nullptr, bu, bd, w->st);
             if (rc) return rc;
         }
     }

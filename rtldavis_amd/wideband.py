@@ -73,6 +73,9 @@ BURST_DECODE_MAX_WINDOWS = 32          # a longer run is counted in ``long_runs`
 BURST_MSG_REPAIRED = 2                 # ``flags`` bit 1: ``pad[1]`` (and ``pad[2]``) were flipped to satisfy the CRC
 BURST_REPAIR_LIST = 8                  # the least reliable payload symbols a repair may flip
 BURST_REPAIR_MAX_FLIPS = 2
+BURST_MSG_NARROW = 4                   # ``flags`` bit 2: decoded behind the narrow-band filter, ``pad[3]`` its centre g
+BURST_NARROW_GRID = 64                 # the filter's centre is g / 64 cycles per output
+BURST_NARROW_MIN_SL = 4
 
 
 class BurstMessages(NamedTuple):
@@ -381,6 +384,26 @@ class WidebandReceiver:
         _lib.check(_lib.lib().rd_wb_burst_repair(self._h, C.byref(r)))
         return int(r.value)
 
+    def set_burst_narrow(self, on: bool = True) -> None:
+        """From the next chunk on, every burst is band-passed at its own frequency before the discriminator: a filter
+        of ``2 * symbol_length + 5`` integer taps, 0.9 symbol rates wide, centred on the nearest of 64 frequencies to the
+        run's correlation sum (the kernel chooses, the row's ``pad[3]`` says which).  The channel filter passes +-110 kHz
+        and a burst occupies +-15 kHz; without the filter the discriminator multiplies all of that noise with itself.  On
+        the project's model of noisy bursts the noise level at which half of them decode rises from about 0.09 to about
+        0.25 (profiles/burst_narrow_gain.txt).  Rows decoded this way have ``flags`` bit 2 set (``BURST_MSG_NARROW``;
+        ``acquire.narrowband``); their ``margin`` and ``f_re`` / ``f_im`` are in the filter's units - do not compare a
+        ``margin`` across the two kinds; ``acquire.burst_message_offset_hz`` uses the angle alone and holds for both.
+        Repair composes with it.  Off (the default) is the receiver without it, byte for byte.  Needs a receiver with
+        nothing in flight and ``set_burst_decode(True)`` (RuntimeError; switching decode or bursts off switches it off,
+        ``reset()`` keeps it); ValueError for ``symbol_length`` below 4."""
+        _lib.check(_lib.lib().rd_wb_set_burst_narrow(self._h, 1 if on else 0))
+
+    def burst_narrow(self) -> bool:
+        """Whether the next submitted chunk will be decoded behind the narrow-band filter."""
+        r = C.c_int(0)
+        _lib.check(_lib.lib().rd_wb_burst_narrow(self._h, C.byref(r)))
+        return bool(r.value)
+
     def burst_messages(self) -> "BurstMessages":
         """Messages of the chunk the last ``fetch()`` returned - later chunks may be in flight - as exact integers.  Per
         run of ``bursts()`` of at most 32 windows (a run that begins with the chunk is extended LOOK_W windows back - a packet's
@@ -391,7 +414,8 @@ class WidebandReceiver:
         absolute output clock), ``margin`` (the least |matched filter output| among the symbols), ``f_re`` / ``f_im`` (the
         lag-1 correlation summed over the packet: ``acquire.burst_message_offset_hz`` turns it into a frequency),
         ``data`` (the on-air bytes, as ``Packet.data``: ``dsp.parse_packet`` takes them), ``ones`` and ``id``; ``pad`` is
-        zero unless ``set_burst_repair`` is on and the row was repaired (``flags`` bit 1).  A burst
+        zero unless ``set_burst_repair`` is on and the row was repaired (``flags`` bit 1) or ``set_burst_narrow`` is on
+        (``flags`` bit 2, ``pad[3]`` the filter's centre).  A burst
         the demodulator decodes as well is reported here and in ``parsed()``: dedupe by channel, chunk and data.
         A packet that ends within ``symbol_length`` outputs of a chunk boundary can be found by both chunks; the fetch
         drops the later chunk's look-back row when the fetch before it delivered the same ``channel`` and ``data`` less

@@ -12,7 +12,8 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its 
     python tools/wideband_stream.py [--chunks 2000] [--repeats 3] [--capture-chunks 6] [--warmup 20] [--parse]
                                     [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]]
                                     [--burst-decode [--burst-decode-out FILE]]
-                                    [--burst-repair N [--burst-repair-out FILE]] [--json OUT]
+                                    [--burst-repair N [--burst-repair-out FILE]]
+                                    [--burst-narrow [--burst-narrow-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -36,6 +37,11 @@ twin of a packet (synth.make_packet(..., flip_bit=...): one payload symbol wrong
 passes the sync word runs the whole search of the repair - the list, the 8 singles, the 28 pairs - and, the wrong symbol
 being a strong one, mostly finds nothing.  Both go into --burst-repair-out (default profiles/wideband_burst_repair.txt),
 with the spread of the windows beside the difference.  The kernel's own time is not measured here.
+--burst-narrow: as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts + decode +
+WidebandReceiver.set_burst_narrow(True) on (k_chan_burst_decode<false, true>: the narrow-band filter in front of the
+discriminator, in every chunk that holds a run); the capture is --burst-decode's, an undamaged burst on every channel.
+Both go into --burst-narrow-out (default profiles/wideband_burst_narrow.txt), with the spread of the windows beside the
+difference and whether the windows of the two settings overlap.  The kernel's own time is not measured here.
 """
 import argparse
 import json
@@ -73,6 +79,10 @@ def main():
                     help="time every window with bursts + decode on, and with repair of N flips on top, on damaged bursts; write --burst-repair-out")
     ap.add_argument("--burst-repair-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                "wideband_burst_repair.txt"))
+    ap.add_argument("--burst-narrow", action="store_true",
+                    help="time every window with bursts + decode on, and with the narrow-band filter on top; write --burst-narrow-out")
+    ap.add_argument("--burst-narrow-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                               "wideband_burst_narrow.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -82,7 +92,10 @@ def main():
     repair = args.burst_repair
     if repair and (args.bursts or args.burst_decode):
         raise SystemExit("--burst-repair alone: each run compares two windows")
-    decode = args.burst_decode or repair > 0
+    narrow = args.burst_narrow
+    if narrow and (args.bursts or args.burst_decode or repair):
+        raise SystemExit("--burst-narrow alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0 or narrow
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
@@ -116,6 +129,7 @@ def main():
     moved[[25] if args.retune == "one" else slice(None)] = 1
 
     bursts_on, decode_on, n_dmsgs, n_repaired, n_right, base_msgs = [False], [False], [0], [0], [0], [0]
+    n_narrow = [0]
 
     def meter():
         if ctl is not None:
@@ -130,6 +144,8 @@ def main():
             if decode_on[0]:
                 msgs = rx.burst_messages()
                 n_dmsgs[0] += len(msgs.records)
+                if narrow:
+                    n_narrow[0] += int(acquire.narrowband(msgs.records).sum())
                 if repair:
                     rep = msgs.records[acquire.repaired(msgs.records)]
                     n_repaired[0] += len(rep)
@@ -167,11 +183,13 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode((on and decode) or repair > 0)
+                rx.set_burst_decode((on and decode) or repair > 0 or narrow)
                 if repair:
                     rx.set_burst_repair(repair if on else 0)
-                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0
-                n_dmsgs[0] = n_repaired[0] = n_right[0] = 0
+                if narrow:
+                    rx.set_burst_narrow(on)
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow
+                n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = 0
                 acq.reset()
                 rx.set_burst_threshold(thr0)
                 n_bursts[0] = n_asked[0] = 0
@@ -251,7 +269,28 @@ def main():
                 f"{base_msgs[0]} burst messages - the difference includes the host's handling of the additional rows",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
-        with open(args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        if narrow:
+            res["burst_narrow"] = {"messages_last_window": n_dmsgs[0], "narrow_rows_last_window": n_narrow[0],
+                                   "messages_last_window_without": base_msgs[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            lines = [
+                "WidebandReceiver narrow-band burst filter (k_chan_burst_decode<false, true>), bursts + decode + narrow on against bursts + "
+                "decode on in the same run: tools/wideband_stream.py --burst-narrow" + (" --parse" if args.parse else ""),
+                lines[1] + "; a burst on every channel",
+                f"  bursts + decode on:           {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + narrow on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(burst_messages() read and handed to Acquisition.update per chunk)",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + narrow {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: narrow {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with narrow: {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages, all {n_narrow[0]} of them narrow rows, "
+                f"{n_asked[0]} retunes proposed; last window without: {base_msgs[0]} burst messages",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
+        with open(args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
