@@ -600,11 +600,11 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  * A rd_burst that k_chan_bursts never writes - windows = 0, first >= nW, first + windows > nW, or a place past the
  * channel's ceil(nW / 2) - is skipped (after step 1).
  * Records: channels ascending, a channel's runs ascending.  The same chunks and thresholds give the same bits on every run.
- * Not solved here: a packet of which only the last few outputs reach into a chunk whose window 0 stays OFF is missed; a run
- * of more than 32 windows is not decoded; a packet that ends a few outputs (5 .. 11 at SL 14) into a chunk whose run
- * holds nothing but the transmission's trailing symbols is missed too - that run's correlation sum lies a deviation off
- * the carrier, and the chunk before cannot reach the packet's end.  A burst the demodulator decodes too is reported by both paths (rd_wb_parsed and
- * here): the caller dedupes by channel, chunk and data.
+ * Not solved here, for a station never yet heard: a packet of which only the last few outputs reach into a chunk whose
+ * window 0 stays OFF, a run of more than 32 windows, and a packet that ends a few outputs into a chunk whose run holds
+ * nothing but the transmission's trailing symbols are missed.  For a station heard once, BURST EXPECT below decodes at
+ * the predicted place without a run and has none of the three gaps.  A burst the demodulator decodes too is reported by
+ * both paths (rd_wb_parsed and here): the caller dedupes by channel, chunk and data.
  * rd_wb_set_burst_decode: on / off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE otherwise),
  * like rd_wb_set_bursts, and bursts on (RD_ERR_STATE otherwise; rd_wb_set_bursts(w, 0) switches decode off too).
  * RD_ERR_ARG for a configuration other than preamble_symbols = 16, N a multiple of 8 in 40 .. 8 RD_BURST_MSG_BYTES,
@@ -633,10 +633,11 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
 #define RD_BD_NB_MAX_SL 51       /* ... and N SL + 1 <= 2048 with N >= 40 leaves no more: 2 SL + 5 <= 107 taps */
 typedef struct rd_burst_msg {
     int32_t  channel;
-    uint32_t first;          /* the run's first window (its rd_burst) */
+    uint32_t first;          /* the run's first window (its rd_burst); with bit 3: the expectation's index in its table */
     int32_t  tau;            /* the end of the first symbol, relative to the chunk's first output; may be negative */
     uint32_t flags;          /* bit 0: the region reached into the previous chunk; bit 1 (RD_BURST_MSG_REPAIRED): repaired;
-                                bit 2 (RD_BURST_MSG_NARROW): step 4n */
+                                bit 2 (RD_BURST_MSG_NARROW): step 4n; bit 3 (RD_BURST_MSG_EXPECTED): a record of BURST EXPECT,
+                                whose bit 0 says that the region began before the chunk */
     uint64_t time;           /* the chunk's absolute output clock + tau */
     uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped; in
                                 the units of step 4n when bit 2 is set: not comparable across the two kinds */
@@ -656,6 +657,68 @@ int rd_wb_burst_narrow(rd_wideband *w, int *on);
  * H[g][k] at [g][k + sl + 2] as (re, im); centres = int16 [64][2], C[g].  RD_ERR_ARG for sl outside 4 .. 51 or a null pointer. */
 int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres);
 int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels);
+/* BURST EXPECT (k_chan_burst_expect, rd_burst_expect.hip): decode where the HOST expects a packet, with no energy gate.
+ * BURST DECODE needs a clean run of ON windows first, and its slicing direction is the run's own noisy correlation sum.
+ * A station heard once is predictable: its next channel follows from its hop pattern, its next time is one dwell period
+ * later to within tens of outputs, and its carrier offset does not change from hop to hop.  An expectation says so
+ * (rtldavis_amd/track.py makes the tables), and the kernel decodes exactly there.  With a non-empty table in force, a
+ * chunk in which an expectation has candidates carries one more launch behind k_chan_burst_decode.  All quantities are
+ * exact integers; SL, N, sync, LOOK, z, p, have_prev are those of BURST DECODE.  Chunk k has clock K (the absolute output
+ * clock of its first output) and B = block_size outputs.  For expectation e the candidates of chunk k are the relative
+ * tau that meet all of
+ *     t_lo <= K + tau <= t_hi  (on the 64-bit clock: differences modulo 2^64);
+ *     0 <= tau + SL (N - 1) < B  - the packet ends in this chunk, as everywhere else;
+ *     tau - SL >= 0 when !have_prev.
+ * No tau qualifies: e is idle in this chunk - header candidates = 0, no record, the record place untouched.  Otherwise
+ * tau_a, tau_b = the least and greatest candidate, t0 = tau_a - SL, t1 = tau_b + SL (N - 1) + 1: t0 >= -N SL >= -LOOK, so
+ * only chunk k-1 is ever needed, t1 <= B, and t1 - t0 = (tau_b - tau_a) + N SL + 1 <= 4096.
+ *   4.  as step 4 of BURST DECODE with (corr_re, corr_im) of e in place of the run's: d[t] = im p[t] corr_re - re p[t]
+ *       corr_im for t0 < t < t1, s[t] = sum_{i < SL} d[t - i] for t0 + SL <= t < t1; |s| < 2^41.
+ *   4n. (narrow) ca = corr_re, cb = corr_im as they are (sh = 0); g chosen as in BURST DECODE.  z[t] is the chunk's (or,
+ *       for t < 0, chunk k-1's) for zf0 <= t < zf1, zf0 = max(t0 - M, have_prev ? -LOOK : 0), zf1 = min(t1 + M, B), and 0
+ *       outside: the filter sees the real samples beside the candidates' first and last symbols wherever the two chunks
+ *       hold them - a run's edge sits on the zero extension, an expectation's does not.  acc, y for t0 <= t < t1, p', d, s
+ *       as in BURST DECODE.
+ *   5, 5a, 5b, 6, 6' run unchanged over the candidates tau_a .. tau_b ONLY (a narrower range than the region's).  One
+ *       condition more: with e.id < 8, a candidate whose id (bit-swapped data[2] & 7 of the corrected symbols, after 5b)
+ *       differs is no candidate.
+ *   At most one record per expectation and chunk, a rd_burst_msg: flags = RD_BURST_MSG_EXPECTED | repaired | narrow |
+ *   (bit 0: t0 < 0, the region reached below t = 0); first = the expectation's index in the table; channel = e.channel;
+ *   every other field as for any record (pad[3] = g with narrow).
+ *   Header per expectation: { n_msgs (0 / 1), candidates = tau_b - tau_a + 1 (0: idle), chunk, pad = 0 }.
+ *   7'. on the host, at the fetch: an expectation whose window straddles the chunk in which the packet ends can be served
+ *       by chunks k and k+1, and a packet has about SL - 2 adjacent valid taus, so both may report it.  An expected record
+ *       is dropped when its channel and data equal those of an expected record that the previous fetch delivered (after
+ *       its own drop) and the times differ by less than SL.  Two expectations of one table that cover the same packet
+ *       each give their own record.
+ * A packet may now be reported by up to three paths: rd_wb_parsed, rd_wb_burst_messages and here.  The caller dedupes
+ * by channel, time and data.  The same chunks and table give the same bits on every run.
+ * rd_wb_set_burst_expect: the table (n entries, at most RD_BX_MAX; n = 0 clears it) in force from the next submitted
+ * chunk on, exactly at that boundary.  Host bookkeeping only, like rd_wb_set_burst_threshold: legal with two chunks in
+ * flight, calls before a submit collapse into the last, no device work (safe before fork).  RD_ERR_ARG, and nothing
+ * changes, for n outside 0 .. 64, a channel outside 0 .. n_channels-1, an id that is neither below 8 nor 0xFF,
+ * t_lo > t_hi, t_hi - t_lo > RD_BX_MAX_SPAN, a corr component outside -2^15 .. 2^15-1 or corr = (0, 0).  RD_ERR_STATE
+ * unless burst decode is on.  rd_wb_set_burst_decode(w, 0), rd_wb_set_bursts(w, 0) and rd_wideband_reset clear the table
+ * (reset restarts the clock the windows refer to).  Repair and narrow in force for a chunk apply to its expectations.
+ * rd_wb_burst_expect: the table the next submit will use (*n entries; RD_ERR_CAPACITY with cap < *n).
+ * rd_wb_expected_messages: the records of the chunk the last fetch returned, after step 7', kept by that fetch; capacity
+ * and state rules are those of rd_wb_burst_messages.  candidates: NULL, or room for n_cand = RD_BX_MAX counts - entry i
+ * is the header's count of expectation i of the table that chunk was submitted with, RD_BX_NO_ENTRY past its end.  A
+ * chunk submitted with an empty table gives *n = 0, not an error. */
+#define RD_BURST_MSG_EXPECTED 8u /* rd_burst_msg.flags: decoded at an expectation; `first` is its index in the table */
+#define RD_BX_MAX 64             /* expectations per table */
+#define RD_BX_MAX_SPAN 2048      /* t_hi - t_lo at most */
+#define RD_BX_ANY_ID 0xFFu       /* rd_expect.id: a message of any transmitter */
+#define RD_BX_NO_ENTRY 0xFFFFFFFFu
+typedef struct rd_expect {
+    int32_t  channel;            /* 0 .. n_channels-1 */
+    uint32_t id;                 /* 0 .. 7: only a message of this transmitter; RD_BX_ANY_ID: any */
+    uint64_t t_lo, t_hi;         /* absolute output clock of the end of the first symbol (rd_burst_msg.time), inclusive */
+    int32_t  corr_re, corr_im;   /* the direction to slice around: each in -2^15 .. 2^15-1, not both 0 */
+} rd_expect;
+int rd_wb_set_burst_expect(rd_wideband *w, const rd_expect *e, int n);
+int rd_wb_burst_expect(rd_wideband *w, rd_expect *out, int cap, int *n);
+int rd_wb_expected_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *candidates, int n_cand);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
  * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */
@@ -709,6 +772,14 @@ int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const
 int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                                  uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
                                  int narrow, rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs, uint32_t *chunk);
+/* rd_debug_burst_expect (tests/test_burst_track.py): k_chan_burst_expect alone, the same pattern - cur / prev as above, the
+ * table e[n_e] checked by the rule of rd_wb_set_burst_expect (RD_ERR_ARG before any device work; n_e >= 1), max_flips and
+ * narrow as above.  msgs_out: RD_BX_MAX record places, hdr_out: RD_BX_MAX headers of four uint32 { n_msgs, candidates,
+ * chunk, pad }; both slots are filled with 0xA5 and copied out whole, so places of idle expectations and everything past
+ * n_e come back as 0xA5 - and so does every header when no expectation has a candidate, for then nothing is launched. */
+int rd_debug_burst_expect(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                          uint64_t clock, uint64_t seq, const rd_expect *e, int n_e, int max_flips, int narrow,
+                          rd_burst_msg *msgs_out, uint32_t *hdr_out);
 
 #ifdef __cplusplus
 }

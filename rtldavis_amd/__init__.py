@@ -5,8 +5,9 @@
 ``rtldavis_amd.WidebandReceiver`` (``rtldavis_amd.wideband``) channelizes and demodulates a live wideband
 capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s front half in their kernels
 (``set_parse`` / ``parsed``); ``rtldavis_amd.parse_packet`` is the same CRC gate for one packet on the host.
+``rtldavis_amd.track.Tracker`` predicts where a station heard once transmits next (``WidebandReceiver.set_burst_expect``).
 """
-__all__ = ["dsp", "batch", "synth", "wideband", "WidebandReceiver", "parse_packet"]
+__all__ = ["dsp", "batch", "synth", "wideband", "track", "WidebandReceiver", "parse_packet"]
 
 import os as _os
 

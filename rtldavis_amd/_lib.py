@@ -212,6 +212,9 @@ SIGNATURES = {
     "rd_wb_set_burst_narrow": (C.c_int, [_P, C.c_int]),
     "rd_wb_burst_narrow": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "rd_bd_narrow_table": (C.c_int, [C.c_int, _P, _P]),
+    "rd_wb_set_burst_expect": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_burst_expect": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "rd_wb_expected_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
@@ -226,6 +229,8 @@ SIGNATURES = {
                                                C.c_int, _P, _P, _P, _P]),
     "rd_debug_burst_decode_narrow": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, _P,
                                                C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rd_debug_burst_expect": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int,
+                                        C.c_int, C.c_int, _P, _P]),
 }
 
 _lib = None

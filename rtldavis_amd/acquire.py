@@ -48,6 +48,7 @@ THRESHOLD_OFF = 2 ** 32 - 1  # wideband.BURST_THRESHOLD_OFF
 FLAG_FIRST, FLAG_LAST = 1, 2
 MSG_REPAIRED = 2             # wideband.BURST_MSG_REPAIRED: bit 1 of a burst message's flags
 MSG_NARROW = 4               # wideband.BURST_MSG_NARROW: bit 2
+MSG_EXPECTED = 8             # wideband.BURST_MSG_EXPECTED: bit 3
 
 
 def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
@@ -87,6 +88,14 @@ def narrowband(records) -> np.ndarray:
     False."""
     recs = np.asarray(getattr(records, "records", records))
     return (recs["flags"] & MSG_NARROW) != 0
+
+
+def expected(records) -> np.ndarray:
+    """Boolean mask over message rows (or a ``BurstMessages`` / ``ExpectedMessages``): the rows decoded at an expectation
+    (``flags`` bit 3; ``first`` is the expectation's index in its table) - all of ``expected_messages()``, none of
+    ``burst_messages()``."""
+    recs = np.asarray(getattr(records, "records", records))
+    return (recs["flags"] & MSG_EXPECTED) != 0
 
 
 def flipped_symbols(row) -> Tuple[int, ...]:

@@ -237,6 +237,68 @@ bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
     return false;
 }
 
+// BURST EXPECT (include/rtldavis_hip.h): the table's rules, one expectation's candidates in a chunk, step 7'
+int rd_bx_check_table(const rd_expect *e, int n, int n_channels, int *bad, const char **why) {
+    static const char *none = "";
+    const char *dummy_why;
+    int dummy_bad;
+    if (!why) why = &dummy_why;
+    if (!bad) bad = &dummy_bad;
+    *why = none;
+    *bad = -1;
+    if (n < 0 || n > RD_BX_MAX) { *why = "the number of expectations (0 .. 64)"; return RD_ERR_ARG; }
+    if (n > 0 && !e) { *why = "null table"; return RD_ERR_ARG; }
+    for (int i = 0; i < n; i++) {
+        const rd_expect &x = e[i];
+        *bad = i;
+        if (x.channel < 0 || x.channel >= n_channels) { *why = "channel"; return RD_ERR_ARG; }
+        if (x.id >= 8u && x.id != RD_BX_ANY_ID) { *why = "id (0 .. 7 or 0xFF)"; return RD_ERR_ARG; }
+        if (x.t_lo > x.t_hi) { *why = "t_lo > t_hi"; return RD_ERR_ARG; }
+        if (x.t_hi - x.t_lo > (uint64_t)RD_BX_MAX_SPAN) { *why = "t_hi - t_lo (at most 2048)"; return RD_ERR_ARG; }
+        if (x.corr_re < -32768 || x.corr_re > 32767 || x.corr_im < -32768 || x.corr_im > 32767) { *why = "corr (-32768 .. 32767)"; return RD_ERR_ARG; }
+        if (x.corr_re == 0 && x.corr_im == 0) { *why = "corr = (0, 0)"; return RD_ERR_ARG; }
+    }
+    *bad = -1;
+    return RD_OK;
+}
+
+bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t clock, uint64_t t_lo, uint64_t t_hi, int32_t *tau_a,
+                 int32_t *tau_b) {
+    if (sl < 1 || n_sym < 1 || block_size < 1 || t_lo > t_hi || !tau_a || !tau_b) return false;
+    const int64_t body = (int64_t)sl * (int64_t)(n_sym - 1);
+    const int64_t lo_b = have_prev ? -body : (int64_t)sl;      // 0 <= tau + SL (N - 1); tau - SL >= 0 with no chunk before
+    const int64_t hi_b = (int64_t)block_size - 1 - body;        // tau + SL (N - 1) < B
+    if (hi_b < lo_b) return false;
+    const uint64_t span = t_hi - t_lo;
+    const uint64_t start = clock + (uint64_t)lo_b;              // the clock of tau = lo_b, modulo 2^64
+    const uint64_t u = start - t_lo;                            // how far lo_b lies inside the window ...
+    int64_t a;
+    uint64_t room;                                              // ... and how much of the window is left from tau_a on
+    if (u <= span) {
+        a = lo_b;
+        room = span - u;
+    } else {
+        const uint64_t v = t_lo - start;                        // outputs from lo_b to the window's first
+        if (v > (uint64_t)(hi_b - lo_b)) return false;
+        a = lo_b + (int64_t)v;
+        room = span;
+    }
+    const int64_t b = room > (uint64_t)(hi_b - a) ? hi_b : a + (int64_t)room;
+    *tau_a = (int32_t)a;
+    *tau_b = (int32_t)b;
+    return true;
+}
+
+bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
+    if (sl <= 0) return false;
+    for (size_t i = 0; i < n_delivered; i++) {
+        const rd_burst_msg &q = delivered[i];
+        const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
+        if (q.channel == m.channel && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
+    }
+    return false;
+}
+
 // BURST DECODE step 4n (include/rtldavis_hip.h): designed in float64, every product and quotient in the order written
 // there - tests/burst_narrow_cases.py evaluates the same expressions in NumPy and must get the same integers.
 extern "C" int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres) {

@@ -50,6 +50,18 @@ int rd_check_block_count(int is_complex, size_t count, size_t B, size_t NS, size
 // outputs from m's on the 64-bit clock.  The fetch drops such a record (rd_wideband.hip).
 bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
 
+// BURST EXPECT (include/rtldavis_hip.h), the host's parts.
+// rd_bx_check_table: RD_OK, or RD_ERR_ARG with *bad = the first offending entry (-1: n itself) and *why naming the rule.
+// rd_bx_range: the candidates of one expectation in the chunk whose first output has clock `clock`: false when it is
+// idle there, else *tau_a <= *tau_b, the least and greatest tau with t_lo <= clock + tau <= t_hi on the 64-bit clock
+// (every difference is taken modulo 2^64, so a clock near the wrap is like any other), 0 <= tau + sl (n_sym - 1) <
+// block_size, and tau - sl >= 0 unless have_prev.  Needs t_hi - t_lo <= RD_BX_MAX_SPAN (rd_bx_check_table).
+// rd_bx_repeats: step 7' - one of `delivered` has m's channel and data and a time less than sl outputs from m's.
+int rd_bx_check_table(const rd_expect *e, int n, int n_channels, int *bad, const char **why);
+bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t clock, uint64_t t_lo, uint64_t t_hi, int32_t *tau_a,
+                 int32_t *tau_b);
+bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
+
 // Host waits poll (the runtime's blocking waits add 10-20 ms of wake-up latency on this platform).  A wait spins on
 // `pause` for the first ~50 us, then yields the core, then sleeps 50 us at a time; it gives up at its deadline.
 struct rd_waiter {

@@ -286,6 +286,33 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
                            size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const uint32_t *narrow_tab,
                            const void *burst_slot, void *slot, hipStream_t st);
 int rd_bd_narrow_upload(int sl, uint32_t **d_tab);
+// Burst expect of a channelized chunk (rd_burst_expect.hip: k_chan_burst_expect; the definition: include/rtldavis_hip.h,
+// BURST EXPECT), queued behind rd_burst_decode_launch on the same stream.  slot: mapped host memory of RD_BX_SLOT_BYTES,
+//   [RD_BX_MAX] rd_burst_msg | [RD_BX_MAX] rd_bx_header | [RD_BX_MAX] rd_bx_entry
+// rd_burst_expect_stage (host only): the candidate range of every expectation for `clock` into the slot's entries, as the
+// kernel reads them; returns how many are active - 0: the caller launches nothing.  cand (may be null): n counts.
+// rd_burst_expect_launch: one workgroup per entry; it writes every header below n and, for an expectation that found a
+// packet, its record place.  slot_host / slot_dev: the host and device address of the same slot.
+struct rd_bx_header {
+    uint32_t n_msgs, candidates;
+    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
+    uint32_t pad;
+};
+struct rd_bx_entry {
+    int32_t channel;
+    uint32_t id;
+    int32_t tau_a, tau_b;        // tau_a > tau_b: idle in this chunk
+    int32_t corr_re, corr_im;
+    uint32_t pad[2];
+};
+#define RD_BX_HEADER_OFFSET ((size_t)RD_BX_MAX * sizeof(rd_burst_msg))
+#define RD_BX_ENTRY_OFFSET (RD_BX_HEADER_OFFSET + (size_t)RD_BX_MAX * sizeof(rd_bx_header))
+#define RD_BX_SLOT_BYTES (RD_BX_ENTRY_OFFSET + (size_t)RD_BX_MAX * sizeof(rd_bx_entry))
+int rd_burst_expect_stage(const rd_config *cfg, int have_prev, uint64_t clock, const rd_expect *e, int n, void *slot_host,
+                          uint32_t *cand);
+int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                           size_t n_out, uint64_t clock, uint64_t seq, int n, int max_flips, const uint32_t *narrow_tab,
+                           void *slot_dev, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

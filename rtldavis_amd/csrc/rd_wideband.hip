@@ -52,6 +52,16 @@
 // filter (rd_wb_set_burst_narrow) is one flag kept the same way and one device table (rd_bd_narrow_upload: 64 x (2 SL + 5)
 // taps and the 64 centres, designed on the host) that the first submit with the flag set uploads, as the spectrum's tables
 // are; the launch gets the table when the flag is set and a null pointer otherwise, and picks the instantiation by it.
+// Burst expect (rd_wb_set_burst_expect / rd_wb_expected_messages; rd_burst_expect.hip): the table is host bookkeeping like
+// the thresholds - recorded by the call, in force from the next submit.  The submit works out from the clock alone which
+// expectations have candidates in the chunk (rd_burst_expect_stage) and writes them, as candidate ranges, into a mapped
+// pinned slot of the chunk's parity - free by the argument for the level slot; host writes made before the launch are
+// visible to it.  None active: nothing is launched, and the fetch reports zero records from the host's own note.
+// Otherwise k_chan_burst_expect is queued behind k_chan_burst_decode and in front of the chunk's demodulator launch.  It
+// reads d_out[s] and, below t = 0, the end of d_out[s ^ 1] under the same ordering as burst decode: chunk k-1's bytes are
+// next written by the channelizer of chunk k+1, later on the same stream, and d_out[s] by that of chunk k+2.  Its records
+// and headers go into the same slot, which the fetch copies out; step 7' runs there, against what the fetch of the chunk
+// before delivered.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -133,6 +143,17 @@ struct rd_wideband {
     // fetch before it delivered (bm_prev), against which a look-back record is a second report of the same packet
     std::vector<rd_burst_msg> bm_prev;
     long bm_chunk = -1;
+    // burst expect: the table the next submitted chunk will use (empty whenever decode is off), the mapped pinned slots per
+    // parity (rd_internal.h: RD_BX_SLOT_BYTES), what each parity's chunk was submitted with (its table's size, whether a
+    // launch was made, the host's candidate counts), and the records the last fetch kept - step 7' as step 7 above
+    std::vector<rd_expect> expect;
+    uint8_t *h_bx[2] = {nullptr, nullptr};
+    int bx_n[2] = {0, 0};
+    bool bx_launched[2] = {false, false};
+    uint32_t bx_cand[2][RD_BX_MAX] = {};
+    std::vector<rd_burst_msg> xm_last, xm_prev;
+    uint32_t xc_last[RD_BX_MAX] = {};
+    long xm_chunk = -1;
 };
 #define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
@@ -216,6 +237,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_sp[i]);
             hipHostFree(w->h_bu[i]);
             hipHostFree(w->h_bd[i]);
+            hipHostFree(w->h_bx[i]);
         }
         hipFree(w->d_lvacc);
         hipFree(w->d_nb);
@@ -305,6 +327,11 @@ static int wb_alloc_decode(rd_wideband *w) {
             WCHK(hipHostMalloc((void **)&w->h_bd[i], rd_bd_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
             memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));   // (a message count no chunk can have)
         }
+    for (int i = 0; i < 2; i++)
+        if (!w->h_bx[i]) {
+            WCHK(hipHostMalloc((void **)&w->h_bx[i], RD_BX_SLOT_BYTES, hipHostMallocMapped));
+            memset(w->h_bx[i], 0xFF, RD_BX_SLOT_BYTES);
+        }
     if (w->narrow && !w->d_nb) return rd_bd_narrow_upload(w->cfg.symbol_length, &w->d_nb);
     return RD_OK;
 }
@@ -336,6 +363,14 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->bm_prev.clear();
     for (int i = 0; i < 2; i++)
         if (w->h_bd[i]) memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));
+    w->expect.clear();            // (the windows refer to the clock that has just restarted)
+    w->xm_chunk = -1;
+    w->xm_prev.clear();
+    for (int i = 0; i < 2; i++) {
+        w->bx_n[i] = 0;
+        w->bx_launched[i] = false;
+        if (w->h_bx[i]) memset(w->h_bx[i], 0xFF, RD_BX_SLOT_BYTES);
+    }
     return RD_OK;
 }
 
@@ -408,6 +443,7 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         w->decode = false;
         w->repair = 0;
         w->narrow = false;
+        w->expect.clear();
     }
     return RD_OK;
 }
@@ -425,6 +461,7 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
     if (!w->decode) {
         w->repair = 0;
         w->narrow = false;
+        w->expect.clear();
     }
     return RD_OK;
 }
@@ -473,6 +510,40 @@ extern "C" int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, 
     if (long_runs) memcpy(long_runs, w->bl_last.data(), (size_t)w->n_ch * sizeof(uint32_t));
     if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d burst messages, room for %d", *n, cap);
     if (*n) memcpy(out, w->bm_last.data(), (size_t)*n * sizeof(rd_burst_msg));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_expect(rd_wideband *w, const rd_expect *e, int n) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    int bad = -1;
+    const char *why = "";
+    if (rd_bx_check_table(e, n, w->n_ch, &bad, &why)) {
+        if (bad < 0) return rd_fail_msg(RD_ERR_ARG, "burst expect: %s, got %d", why, n);
+        return rd_fail_msg(RD_ERR_ARG, "burst expect: entry %d: %s", bad, why);
+    }
+    if (!w->decode) return rd_fail_msg(RD_ERR_STATE, "burst expect needs burst decode on (rd_wb_set_burst_decode)");
+    w->expect.assign(e, e + n);
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_expect(rd_wideband *w, rd_expect *out, int cap, int *n) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *n = (int)w->expect.size();
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d expectations, room for %d", *n, cap);
+    if (*n) memcpy(out, w->expect.data(), (size_t)*n * sizeof(rd_expect));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_expected_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *candidates, int n_cand) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (candidates && n_cand != RD_BX_MAX)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d candidate counts of %d", n_cand, RD_BX_MAX);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_decode) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with burst decode off (rd_wb_set_burst_decode)");
+    *n = (int)w->xm_last.size();
+    if (candidates) memcpy(candidates, w->xc_last, sizeof w->xc_last);
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d expected messages, room for %d", *n, cap);
+    if (*n) memcpy(out, w->xm_last.data(), (size_t)*n * sizeof(rd_burst_msg));
     return RD_OK;
 }
 
@@ -592,6 +663,18 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
             rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
                                         w->clock, (uint64_t)w->n_sub, w->repair, w->narrow ? w->d_nb : nullptr, bu, bd, w->st);
             if (rc) return rc;
+            // expect slot s: free by the argument for the level slot; the candidate ranges travel in it (header comment)
+            const int nx = (int)w->expect.size();
+            w->bx_n[s] = nx;
+            w->bx_launched[s] = false;
+            if (nx && rd_burst_expect_stage(&w->cfg, w->n_sub >= 1 ? 1 : 0, w->clock, w->expect.data(), nx, w->h_bx[s], w->bx_cand[s]) > 0) {
+                void *bx = nullptr;
+                WCHK(hipHostGetDevicePointer(&bx, w->h_bx[s], 0));
+                rc = rd_burst_expect_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
+                                            w->clock, (uint64_t)w->n_sub, nx, w->repair, w->narrow ? w->d_nb : nullptr, bx, w->st);
+                if (rc) return rc;
+                w->bx_launched[s] = true;
+            }
         }
     }
     w->clock += w->B;
@@ -632,6 +715,27 @@ static int wb_fetched(rd_wideband *w, int rc) {
             }
         }
         w->bm_chunk = w->last;
+        // Burst expect: the slot's headers and records when the chunk's submit launched the kernel, else nothing.  Step 7'
+        // (include/rtldavis_hip.h, BURST EXPECT) against what the fetch of the chunk before delivered.
+        const int sx = (int)(w->last & 1), nx = w->bx_n[sx];
+        if (w->xm_chunk == w->last - 1) w->xm_prev.swap(w->xm_last);
+        else w->xm_prev.clear();
+        w->xm_chunk = -1;
+        w->xm_last.clear();
+        for (int i = 0; i < RD_BX_MAX; i++) w->xc_last[i] = i < nx ? 0u : RD_BX_NO_ENTRY;
+        if (nx && w->bx_launched[sx]) {
+            const rd_burst_msg *xr = (const rd_burst_msg *)w->h_bx[sx];
+            const rd_bx_header *xh = (const rd_bx_header *)(w->h_bx[sx] + RD_BX_HEADER_OFFSET);
+            for (int i = 0; i < nx; i++) {
+                const rd_bx_header h = xh[i];
+                if (h.chunk != (uint32_t)w->last || h.n_msgs > 1u || h.candidates != w->bx_cand[sx][i])
+                    return rd_fail_msg(RD_ERR_DEVICE, "expectation %d: header of chunk %u (%u messages, %u candidates), not of chunk %ld with %u candidates",
+                                       i, h.chunk, h.n_msgs, h.candidates, w->last, w->bx_cand[sx][i]);
+                w->xc_last[i] = h.candidates;
+                if (h.n_msgs && !rd_bx_repeats(xr[i], w->xm_prev.data(), w->xm_prev.size(), w->cfg.symbol_length)) w->xm_last.push_back(xr[i]);
+            }
+        }
+        w->xm_chunk = w->last;
         w->last_decode = true;
     }
     if (w->bursts) {

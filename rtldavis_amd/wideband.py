@@ -76,6 +76,13 @@ BURST_REPAIR_MAX_FLIPS = 2
 BURST_MSG_NARROW = 4                   # ``flags`` bit 2: decoded behind the narrow-band filter, ``pad[3]`` its centre g
 BURST_NARROW_GRID = 64                 # the filter's centre is g / 64 cycles per output
 BURST_NARROW_MIN_SL = 4
+BURST_MSG_EXPECTED = 8                 # ``flags`` bit 3: decoded at an expectation, ``first`` is its index in the table
+BURST_EXPECT_MAX = 64                  # expectations per table
+BURST_EXPECT_MAX_SPAN = 2048           # ``t_hi - t_lo`` at most
+BURST_EXPECT_ANY_ID = 0xFF
+# set_burst_expect(): one row per expectation - the layout of rd_expect
+EXPECT_DTYPE = np.dtype([("channel", np.int32), ("id", np.uint32), ("t_lo", np.uint64), ("t_hi", np.uint64),
+                         ("corr_re", np.int32), ("corr_im", np.int32)])
 
 
 class BurstMessages(NamedTuple):
@@ -84,6 +91,16 @@ class BurstMessages(NamedTuple):
     of more than 32 windows, which are not decoded) and ``chunk``, the chunk's number since construction / ``reset()``."""
     records: np.ndarray
     long_runs: np.ndarray
+    chunk: int
+
+
+class ExpectedMessages(NamedTuple):
+    """``WidebandReceiver.expected_messages()``: ``records`` (``BURST_MSG_DTYPE``, at most one row per expectation of the
+    table the chunk was submitted with, in table order; ``first`` is the expectation's index and ``flags`` has
+    ``BURST_MSG_EXPECTED`` set), ``candidates`` (uint32, one per expectation of that table: the number of candidate
+    positions it had in the chunk, 0 when it was idle there) and ``chunk``."""
+    records: np.ndarray
+    candidates: np.ndarray
     chunk: int
 
 
@@ -434,6 +451,45 @@ class WidebandReceiver:
         chunk = C.c_uint64(0)                            # the chunk whose headers the fetch checked
         _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
         return BurstMessages(recs[: n.value].copy(), long_runs, int(chunk.value))
+
+    def set_burst_expect(self, table) -> None:
+        """From the next submitted chunk on, exactly at that boundary, also decode at the places ``table`` names, with no
+        energy gate: rows of ``EXPECT_DTYPE`` (at most ``BURST_EXPECT_MAX``; an empty table clears it) - ``channel``,
+        ``id`` (0 .. 7: only that transmitter's message; ``BURST_EXPECT_ANY_ID``), ``t_lo .. t_hi`` (the window, inclusive,
+        on the receiver's absolute output clock, for the END of the packet's first symbol - ``time`` of a message row;
+        at most ``BURST_EXPECT_MAX_SPAN`` wide) and ``corr_re, corr_im`` (the direction to slice around, each in
+        ``-2**15 .. 2**15 - 1``: ``round(2**14 e^{j 2 pi f / out_rate})`` for a carrier at f Hz in the channel's bytes).
+        ``track.Tracker`` makes such tables from the messages already received.  Legal with chunks in flight; calls before
+        a submit collapse into the last.  ``set_burst_repair`` and ``set_burst_narrow`` apply to expectations too.
+        ValueError for a table that breaks a rule (nothing changes); RuntimeError unless ``set_burst_decode(True)``;
+        switching decode or bursts off and ``reset()`` clear the table."""
+        t = np.ascontiguousarray(np.asarray(table, EXPECT_DTYPE).reshape(-1))
+        _lib.check(_lib.lib().rd_wb_set_burst_expect(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def burst_expect(self) -> np.ndarray:
+        """The table the next submitted chunk will use (``EXPECT_DTYPE``)."""
+        t = np.empty(BURST_EXPECT_MAX, EXPECT_DTYPE)
+        n = C.c_int(0)
+        _lib.check(_lib.lib().rd_wb_burst_expect(self._h, t.ctypes.data, t.size, C.byref(n)))
+        return t[: n.value].copy()
+
+    def expected_messages(self) -> "ExpectedMessages":
+        """The messages found at the expectations in the chunk the last ``fetch()`` returned - rows like those of
+        ``burst_messages()`` with ``flags`` bit 3 (``BURST_MSG_EXPECTED``) set, ``first`` the expectation's index in the
+        table that chunk was submitted with and ``flags`` bit 0 meaning that the searched region began before the
+        chunk - and per expectation the number of candidate positions it had in the chunk.  A packet whose window
+        straddles a chunk boundary can be found from both sides; the fetch drops the later chunk's row when the fetch
+        before it delivered the same ``channel`` and ``data`` less than ``symbol_length`` outputs away.  The same packet
+        may also appear in ``parsed()`` and ``burst_messages()``: dedupe by channel, time and data.  A chunk submitted
+        with an empty table gives no rows.  RuntimeError before any fetch and when decode was off for that chunk."""
+        L = _lib.lib()
+        cand = np.empty(BURST_EXPECT_MAX, np.uint32)
+        recs = np.empty(BURST_EXPECT_MAX, BURST_MSG_DTYPE)
+        n = C.c_int(0)
+        _lib.check(L.rd_wb_expected_messages(self._h, recs.ctypes.data, recs.size, C.byref(n), cand.ctypes.data, cand.size))
+        chunk = C.c_uint64(0)
+        _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
+        return ExpectedMessages(recs[: n.value].copy(), cand[cand != 0xFFFFFFFF].copy(), int(chunk.value))
 
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel

@@ -13,7 +13,7 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its 
                                     [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]]
                                     [--burst-decode [--burst-decode-out FILE]]
                                     [--burst-repair N [--burst-repair-out FILE]]
-                                    [--burst-narrow [--burst-narrow-out FILE]] [--json OUT]
+                                    [--burst-narrow [--burst-narrow-out FILE]] [--track [--track-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -42,6 +42,11 @@ WidebandReceiver.set_burst_narrow(True) on (k_chan_burst_decode<false, true>: th
 discriminator, in every chunk that holds a run); the capture is --burst-decode's, an undamaged burst on every channel.
 Both go into --burst-narrow-out (default profiles/wideband_burst_narrow.txt), with the spread of the windows beside the
 difference and whether the windows of the two settings overlap.  The kernel's own time is not measured here.
+--track: as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts + decode on with a table
+of 8 expectations set before every submit (WidebandReceiver.set_burst_expect: k_chan_burst_expect behind
+k_chan_burst_decode, 8 workgroups, 201 candidates each, all inside the chunk) and expected_messages() read after every
+fetch.  Both go into --track-out (default profiles/wideband_burst_track.txt), with the spread of the windows beside the
+difference.  The kernel's own time is not measured here.
 """
 import argparse
 import json
@@ -83,6 +88,10 @@ def main():
                     help="time every window with bursts + decode on, and with the narrow-band filter on top; write --burst-narrow-out")
     ap.add_argument("--burst-narrow-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                "wideband_burst_narrow.txt"))
+    ap.add_argument("--track", action="store_true",
+                    help="time every window with bursts + decode on, and with 8 expectations active in every chunk on top; write --track-out")
+    ap.add_argument("--track-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                        "wideband_burst_track.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -95,7 +104,10 @@ def main():
     narrow = args.burst_narrow
     if narrow and (args.bursts or args.burst_decode or repair):
         raise SystemExit("--burst-narrow alone: each run compares two windows")
-    decode = args.burst_decode or repair > 0 or narrow
+    track = args.track
+    if track and (args.bursts or args.burst_decode or repair or narrow):
+        raise SystemExit("--track alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0 or narrow or track
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
@@ -130,6 +142,14 @@ def main():
 
     bursts_on, decode_on, n_dmsgs, n_repaired, n_right, base_msgs = [False], [False], [0], [0], [0], [0]
     n_narrow = [0]
+    track_on, n_xmsgs, n_xcand = [False], [0], [0]
+
+    def track_table(clock):
+        """8 expectations, every one with 201 candidates inside the chunk that begins at `clock`, spread over the channels."""
+        t = np.zeros(8, wideband.EXPECT_DTYPE)
+        for i in range(8):
+            t[i] = ((6 * i) % rx.n_channels, 0xFF, clock + 1000 + 100 * i, clock + 1200 + 100 * i, 0, -16384)
+        return t
 
     def meter():
         if ctl is not None:
@@ -146,6 +166,10 @@ def main():
                 n_dmsgs[0] += len(msgs.records)
                 if narrow:
                     n_narrow[0] += int(acquire.narrowband(msgs.records).sum())
+                if track_on[0]:
+                    x = rx.expected_messages()
+                    n_xmsgs[0] += len(x.records)
+                    n_xcand[0] += int(x.candidates.astype(np.int64).sum())
                 if repair:
                     rep = msgs.records[acquire.repaired(msgs.records)]
                     n_repaired[0] += len(rep)
@@ -167,6 +191,8 @@ def main():
             t_sub.append(time.perf_counter())
             if args.retune != "none":
                 rx.retune(moved * ((k + 1) & 1))
+            if track_on[0]:
+                rx.set_burst_expect(track_table(rx.submitted * B))
             rx.submit(chunks[k % nk])
         while rx.inflight:
             pk.append(rx.fetch())
@@ -183,13 +209,14 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode((on and decode) or repair > 0 or narrow)
+                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track)
                 if repair:
                     rx.set_burst_repair(repair if on else 0)
                 if narrow:
                     rx.set_burst_narrow(on)
-                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow
-                n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = 0
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track
+                track_on[0] = on and track
+                n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = n_xmsgs[0] = n_xcand[0] = 0
                 acq.reset()
                 rx.set_burst_threshold(thr0)
                 n_bursts[0] = n_asked[0] = 0
@@ -290,7 +317,27 @@ def main():
                 f"{n_asked[0]} retunes proposed; last window without: {base_msgs[0]} burst messages",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
-        with open(args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        if track:
+            res["burst_track"] = {"expectations_per_chunk": 8, "candidates_last_window": n_xcand[0], "expected_messages_last_window": n_xmsgs[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            lines = [
+                "WidebandReceiver burst expect (k_chan_burst_expect<false, false>), bursts + decode + 8 expectations active in every chunk "
+                "against bursts + decode on in the same run: tools/wideband_stream.py --track" + (" --parse" if args.parse else ""),
+                lines[1] + "; a burst on every channel; per chunk set_burst_expect with 8 windows of 201 candidates inside the chunk",
+                f"  bursts + decode on:                   {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + 8 expectations on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(set_burst_expect per submit, expected_messages() read per fetch)",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + expectations {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: expectations {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with expectations: {n_xcand[0]} candidates tested ({n_xcand[0] / max(args.chunks, 1):.0f} per chunk), {n_xmsgs[0]} expected messages, "
+                f"{n_dmsgs[0]} burst messages; last window without: {base_msgs[0]} burst messages",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
+        with open(args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
