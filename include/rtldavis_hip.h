@@ -719,6 +719,64 @@ typedef struct rd_expect {
 int rd_wb_set_burst_expect(rd_wideband *w, const rd_expect *e, int n);
 int rd_wb_burst_expect(rd_wideband *w, rd_expect *out, int cap, int *n);
 int rd_wb_expected_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *candidates, int n_cand);
+/* BURST QUALITY (k_chan_burst_quality, rd_burst_quality.hip): the power, the noise in front and the clipping of every
+ * record of BURST DECODE and BURST EXPECT - what the demodulator path reports as rd_packet.rssi / .snr, in integers, and
+ * the same behind the narrow-band filter of step 4n (an in-band figure: the one that corresponds to what the narrow
+ * decoder can do).  With quality on, a chunk carries one more launch behind k_chan_burst_decode and one behind
+ * k_chan_burst_expect when that was launched; the kernels in front are not changed.  All quantities are exact integers in
+ * the notation of BURST DECODE (b, a = 2 b - 255, z, SL, N, M = SL + 2, T = 2 SL + 5, H[g], C[g], have_prev); B = block_size.
+ * A record of channel c with first symbol end tau: the first output of its packet is P0 = tau - SL + 1.  Windows:
+ *     packet   P0 .. P0 + N SL - 1
+ *     sync     P0 .. P0 + 16 SL - 1                          (the reference's preamble_iq)
+ *     noise    P0 - gap - 16 SL .. P0 - gap - 1, intersected with t >= lo_lim;  lo_lim = -B with have_prev, else 0
+ * n_noise = the outputs the intersection leaves, 0 .. 16 SL.  With gap = 0 this is the reference's noise window.  gap
+ * (noise_gap, 0 .. RD_BQ_MAX_GAP outputs) is a parameter because what a real transmitter sends in front of its sync word
+ * has NOT been measured in this project: the synthetic bursts of the tests have a lead-in of alternating symbols there,
+ * and then the window holds signal, not noise (rtldavis_amd/acquire.py: snr_floor_db takes the noise from the channel's
+ * OFF windows instead).  A default, not a measurement - as Tracker's period and guard.
+ * Raw sums of |z[t]|^2 = aI^2 + aQ^2 (<= 130050): pkt, sig, noise over the three windows; each at most 2047 x 130050
+ * < 2^28.  peak = the maximum over the packet of max(|aI|, |aQ|) (1 .. 255); clipped = the bytes equal to 0 or 255 among
+ * the packet's 2 N SL bytes.
+ * In-band sums, valid only when flags bit 0 is set: g by the rule of step 4n applied to the record's own (f_re, f_im) -
+ * sh = max(0, bitlength(max(|f_re|, |f_im|)) - 15) on the 64-bit values, ca = f_re >> sh, cb = f_im >> sh (arithmetic),
+ * the smallest g that maximises ca C[g].re + cb C[g].im.  The same rule for records with and without flags bit 2: it is
+ * NOT pad[3], which followed from the run's correlation sum.  y[t] = (sum_{k = -M .. M} H[g][k] z[t - k] + 2^10) >> 11
+ * per component with z = 0 outside lo_lim <= t < B, exactly as in 4n.  pkt_nb, sig_nb, noise_nb = the sums of
+ * |y[t]|^2 over the same three windows: |y| <= 3192 per component, so |y|^2 <= 2 x 3192^2 = 20377728 < 2^25 and a sum
+ * over at most 2047 outputs is below 2^25 x 2^11 = 2^36.  Bit 0 is clear and the four in-band fields (and g) are 0 when
+ * SL < 4 or (f_re, f_im) = (0, 0).
+ * Before it indexes anything the kernel checks again that 0 <= c < n_channels, P0 >= lo_lim and P0 + N SL <= B (tau taken
+ * as a 64-bit value: no tau overflows the test); a record that fails gets flags = RD_BQ_UNMEASURABLE and zeros elsewhere
+ * (chunk excepted).  Quality record i of a slot belongs to message record i of the slot it was launched over.  The same
+ * bytes, records and gap give the same bits on every run.
+ * rd_wb_set_burst_quality: on / off and noise_gap for the chunks submitted from now on.  Off is the default: then nothing
+ * is launched and every other call returns what it returns without this section, byte for byte.  RD_ERR_ARG for noise_gap
+ * outside 0 .. 1024 (checked first); RD_ERR_STATE unless the receiver is quiet and burst decode is on;
+ * rd_wb_set_burst_decode(w, 0) and rd_wb_set_bursts(w, 0) switch it off, rd_wideband_reset keeps it.  A chunk's records
+ * come from the values in force when it was submitted.  No device work (safe before fork).  rd_wb_burst_quality: the
+ * values the next submitted chunk will use.
+ * rd_wb_burst_message_quality / rd_wb_expected_message_quality: row i belongs to row i of rd_wb_burst_messages /
+ * rd_wb_expected_messages of the same fetch, after steps 7 / 7' - the fetch drops a dropped record's quality with it.
+ * *n = the number of rows; with cap < *n: RD_ERR_CAPACITY, nothing is lost, call again (out may be NULL with cap = 0).
+ * RD_ERR_STATE before any fetch, and when the last fetched chunk was submitted with quality off. */
+#define RD_BQ_MAX_GAP 1024       /* noise_gap at most */
+#define RD_BQ_INBAND 1u          /* rd_burst_quality.flags: g, pkt_nb, sig_nb, noise_nb are valid */
+#define RD_BQ_UNMEASURABLE 128u  /* rd_burst_quality.flags: the record's channel or tau is out of range; every sum is 0 */
+typedef struct rd_burst_quality {
+    uint64_t pkt, sig, noise;              /* sums of |z|^2 over the packet, the sync word, the noise window */
+    uint64_t pkt_nb, sig_nb, noise_nb;     /* the same of |y|^2 (flags bit 0) */
+    uint32_t n_noise, clipped;
+    uint16_t peak; uint8_t g; uint8_t flags;   /* bit 0: in-band fields valid; bit 7: the record was not measurable */
+    uint32_t chunk;                        /* the chunk's sequence number since create / reset, its low 32 bits */
+} rd_burst_quality;
+int rd_wb_set_burst_quality(rd_wideband *w, int on, int noise_gap);
+int rd_wb_burst_quality(rd_wideband *w, int *on, int *noise_gap);
+int rd_wb_burst_message_quality(rd_wideband *w, rd_burst_quality *out, int cap, int *n);
+int rd_wb_expected_message_quality(rd_wideband *w, rd_burst_quality *out, int cap, int *n);
+/* The windows of one record, on the host (no device is touched): out = { p0, p1, s1, n0, n1 } - packet p0 .. p1 - 1, sync
+ * p0 .. s1 - 1, noise n0 .. n1 - 1 (n0 = n1 = p0 when nothing of it is left).  Returns 1, or 0 with out zeroed for a record
+ * that is not measurable (or a null out). */
+int rd_bq_window(int sl, int n_sym, int block_size, int have_prev, int64_t tau, int gap, int32_t *out);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
  * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */
@@ -780,6 +838,16 @@ int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t *cur, const
 int rd_debug_burst_expect(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                           uint64_t clock, uint64_t seq, const rd_expect *e, int n_e, int max_flips, int narrow,
                           rd_burst_msg *msgs_out, uint32_t *hdr_out);
+/* rd_debug_burst_quality (tests/test_burst_quality.py): k_chan_burst_quality alone, the same pattern - cur / prev as
+ * above; msgs[n_ch][cap] (cap = ceil(nW / 2)) and n_msgs_per_channel[n_ch] are written into a decode slot as they are,
+ * records no decoder would write included, with chunk = RD_BQ_DEBUG_CHUNK in every header.  out: n_ch x cap + RD_BX_MAX
+ * quality records, the receiver's slot [n_ch][cap] | [RD_BX_MAX]: filled with 0xA5, written by ONE launch over the decode
+ * part and copied out whole - the places past a channel's n_msgs and the whole expect part come back as 0xA5.
+ * RD_ERR_ARG before any device work for noise_gap outside 0 .. 1024, an n_msgs above cap, or a configuration
+ * rd_wb_set_burst_decode refuses. */
+#define RD_BQ_DEBUG_CHUNK 0x51A7u
+int rd_debug_burst_quality(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                           int noise_gap, const rd_burst_msg *msgs, const uint32_t *n_msgs_per_channel, rd_burst_quality *out);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,10 @@
 capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s front half in their kernels
 (``set_parse`` / ``parsed``); ``rtldavis_amd.parse_packet`` is the same CRC gate for one packet on the host.
 ``rtldavis_amd.track.Tracker`` predicts where a station heard once transmits next (``WidebandReceiver.set_burst_expect``).
+``WidebandReceiver.set_burst_quality`` measures every burst message's power and noise on the device, and
+``rtldavis_amd.burst_packets`` turns the rows into ``dsp.Packet``s with ``rssi`` and ``snr`` for ``protocol.Parser.parse``.
 """
-__all__ = ["dsp", "batch", "synth", "wideband", "track", "WidebandReceiver", "parse_packet"]
+__all__ = ["dsp", "batch", "synth", "wideband", "track", "WidebandReceiver", "parse_packet", "burst_packets"]
 
 import os as _os
 
@@ -40,6 +42,9 @@ def __getattr__(name):
     if name == "WidebandReceiver":
         from .wideband import WidebandReceiver
         return WidebandReceiver
+    if name == "burst_packets":
+        from .wideband import burst_packets
+        return burst_packets
     if name == "parse_packet":
         from .dsp import parse_packet
         return parse_packet

@@ -215,6 +215,11 @@ SIGNATURES = {
     "rd_wb_set_burst_expect": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_burst_expect": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "rd_wb_expected_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
+    "rd_wb_set_burst_quality": (C.c_int, [_P, C.c_int, C.c_int]),
+    "rd_wb_burst_quality": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rd_wb_burst_message_quality": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "rd_wb_expected_message_quality": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "rd_bq_window": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _P]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
@@ -231,6 +236,7 @@ SIGNATURES = {
                                                C.c_int, C.c_int, _P, _P, _P, _P]),
     "rd_debug_burst_expect": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int,
                                         C.c_int, C.c_int, _P, _P]),
+    "rd_debug_burst_quality": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -98,6 +98,55 @@ def expected(records) -> np.ndarray:
     return (recs["flags"] & MSG_EXPECTED) != 0
 
 
+# Signal quality of a message row (``WidebandReceiver.burst_message_quality()`` / ``expected_message_quality()``, rows of
+# ``wideband.QUALITY_DTYPE``), by the reference's formulas (rtldavis dsp.py: the mean power of the 16 sync symbols for
+# the signal, of the 16 symbols' worth of samples in front of the packet for the noise).  The sums are in the units of the
+# channelized bytes, a = 2 b - 255, so full scale is 255; behind the narrow-band filter the pass-band gain is 2^14 / 2^11.
+FULL_SCALE = 255.0
+INBAND_GAIN = 8.0            # 2^14 (the taps sum to it) / 2^11 (RD_BD_NB_SHIFT)
+QUALITY_INBAND = 1           # wideband.QUALITY_INBAND: bit 0 of a quality row's flags
+NO_NOISE_POWER = 1e-9        # the reference's noise power when there is no noise region, in full-scale^2
+NO_SIGNAL_DB = -120.0        # the reference's rssi at zero power
+ZERO_NOISE_SNR_DB = 50.0     # the reference's snr at zero noise power
+
+
+def _snr_db(sig: int, n_sig: int, noise: int, n_noise: int, full_scale: float) -> float:
+    if sig <= 0:
+        return float("nan")  # (no measurable row has it: every |z|^2 is at least 2)
+    signal_power = sig / (n_sig * full_scale * full_scale)
+    noise_power = noise / (n_noise * full_scale * full_scale) if n_noise > 0 else NO_NOISE_POWER
+    return 10.0 * math.log10(signal_power / noise_power) if noise_power > 0 else ZERO_NOISE_SNR_DB
+
+
+def rssi_db(q, symbol_length: int) -> float:
+    """``10 log10`` of the mean power of the packet's 16 sync symbols, 1.0 = a full-scale component (|a| = 255): the
+    reference's ``rssi`` on the channelized bytes.  -120 at zero power (a row with ``flags`` bit 7)."""
+    sig = int(q["sig"])
+    return 10.0 * math.log10(sig / (16 * int(symbol_length) * FULL_SCALE * FULL_SCALE)) if sig > 0 else NO_SIGNAL_DB
+
+
+def snr_db(q, symbol_length: int) -> float:
+    """The reference's ``snr``: sync power over the mean power of the ``n_noise`` outputs in front of the packet; with its
+    fallbacks - a noise power of 1e-9 full-scale^2 when ``n_noise`` = 0, and 50 when the noise sum is 0.  What lies in that
+    window is whatever the transmitter sends before its sync word: see ``snr_floor_db``.  NaN for a row without signal."""
+    return _snr_db(int(q["sig"]), 16 * int(symbol_length), int(q["noise"]), int(q["n_noise"]), FULL_SCALE)
+
+
+def snr_inband_db(q, symbol_length: int) -> float:
+    """The same on the sums behind the narrow-band filter (``sig_nb``, ``noise_nb``): the ratio in the +-0.9 symbol rates
+    the narrow decoder sees.  NaN without ``flags`` bit 0."""
+    if not int(q["flags"]) & QUALITY_INBAND:
+        return float("nan")
+    return _snr_db(int(q["sig_nb"]), 16 * int(symbol_length), int(q["noise_nb"]), int(q["n_noise"]), FULL_SCALE * INBAND_GAIN)
+
+
+def snr_floor_db(q, floor_row, symbol_length: int) -> float:
+    """Sync power over the channel's noise floor, ``power_off / (128 windows_off)`` of the chunk's ``bursts().floor`` row -
+    for the case where the window in front of the packet is not noise (a lead-in).  The reference's fallbacks apply to a
+    chunk without OFF windows and to a floor of 0."""
+    return _snr_db(int(q["sig"]), 16 * int(symbol_length), int(floor_row["power_off"]), WINDOW * int(floor_row["windows_off"]), FULL_SCALE)
+
+
 def flipped_symbols(row) -> Tuple[int, ...]:
     """The symbol indices (0 = the first sync symbol) a repaired row had flipped, ascending: a tuple of 0, 1 or 2."""
     if not int(row["flags"]) & MSG_REPAIRED:

@@ -328,3 +328,16 @@ extern "C" int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres) {
     }
     return RD_OK;
 }
+
+// BURST QUALITY (include/rtldavis_hip.h): the windows of one record, through the C ABI (rd_host.h: rd_bq_windows_of)
+extern "C" int rd_bq_window(int sl, int n_sym, int block_size, int have_prev, int64_t tau, int gap, int32_t *out) {
+    if (!out) return 0;
+    rd_bq_windows w;
+    const bool ok = rd_bq_windows_of(sl, n_sym, block_size, have_prev, tau, gap, &w);
+    out[0] = w.p0;
+    out[1] = w.p1;
+    out[2] = w.s1;
+    out[3] = w.n0;
+    out[4] = w.n1;
+    return ok ? 1 : 0;
+}

@@ -6,6 +6,7 @@
 //   rd_ord_bucket_cap     matches a stream's list in k_tail's LDS holds, from the stream's length
 //   rd_check_block_count  "Incompatible array sizes" (py:32-36, py:145-149)
 //   rd_waiter             the polling policy of every host wait: spin, then yield, then sleep, with a deadline
+//   rd_bq_windows_of      BURST QUALITY: a record's packet, sync and noise windows (inline: the kernel evaluates it too)
 // py = /root/reference/src/rtldavis/dsp.py
 #pragma once
 #include <stddef.h>
@@ -61,6 +62,40 @@ int rd_bx_check_table(const rd_expect *e, int n, int n_channels, int *bad, const
 bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t clock, uint64_t t_lo, uint64_t t_hi, int32_t *tau_a,
                  int32_t *tau_b);
 bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
+
+// BURST QUALITY (include/rtldavis_hip.h): the three windows of a record whose first symbol ends at tau, as half-open
+// ranges of outputs relative to the chunk's first - packet [p0, p1), sync [p0, s1), noise [n0, n1) with n1 - n0 = n_noise
+// (n0 = n1 = p0 when the intersection with t >= lo_lim is empty).  rd_bq_windows_of: false, and *w zeroed, for a record
+// that is not measurable - sl < 1, n_sym < 16, block_size < 1, gap < 0, p0 < lo_lim or p1 > block_size; tau is taken as a
+// 64-bit value so that no record overflows the test.  The one definition serves the host (rd_bq_window, the C form the
+// tests call) and k_chan_burst_quality, which checks every record again before it indexes anything.
+#if defined(__HIPCC__)
+#define RD_HOST_DEVICE __host__ __device__
+#else
+#define RD_HOST_DEVICE
+#endif
+struct rd_bq_windows {
+    int32_t p0, p1, s1, n0, n1;
+};
+RD_HOST_DEVICE static inline bool rd_bq_windows_of(int sl, int n_sym, int block_size, int have_prev, int64_t tau, int gap,
+                                                   rd_bq_windows *w) {
+    w->p0 = w->p1 = w->s1 = w->n0 = w->n1 = 0;
+    if (sl < 1 || n_sym < 16 || block_size < 1 || gap < 0) return false;
+    if (tau < -((int64_t)1 << 40) || tau > ((int64_t)1 << 40)) return false;   // (far outside any chunk; no sum below overflows)
+    const int64_t lo_lim = have_prev ? -(int64_t)block_size : 0;
+    const int64_t p0 = tau - (int64_t)sl + 1, p1 = p0 + (int64_t)n_sym * (int64_t)sl;
+    if (p0 < lo_lim || p1 > (int64_t)block_size) return false;
+    int64_t n1 = p0 - (int64_t)gap, n0 = n1 - 16 * (int64_t)sl;
+    if (n0 < lo_lim) n0 = lo_lim;
+    if (n1 <= n0) n0 = n1 = p0;                                  // nothing left of it
+    w->p0 = (int32_t)p0;
+    w->p1 = (int32_t)p1;
+    w->s1 = (int32_t)(p0 + 16 * (int64_t)sl);
+    w->n0 = (int32_t)n0;
+    w->n1 = (int32_t)n1;
+    return true;
+}
+// (rd_bq_window, include/rtldavis_hip.h, is the same through the C ABI)
 
 // Host waits poll (the runtime's blocking waits add 10-20 ms of wake-up latency on this platform).  A wait spins on
 // `pause` for the first ~50 us, then yields the core, then sleeps 50 us at a time; it gives up at its deadline.

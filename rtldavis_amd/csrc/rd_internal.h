@@ -313,6 +313,24 @@ int rd_burst_expect_stage(const rd_config *cfg, int have_prev, uint64_t clock, c
 int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                            size_t n_out, uint64_t clock, uint64_t seq, int n, int max_flips, const uint32_t *narrow_tab,
                            void *slot_dev, hipStream_t st);
+// Burst quality (rd_burst_quality.hip: k_chan_burst_quality; the definition: include/rtldavis_hip.h, BURST QUALITY),
+// queued behind rd_burst_decode_launch / rd_burst_expect_launch on the same stream.  One launch walks a slot of n_groups
+// groups of `cap` record places whose 16-byte headers begin with n_msgs and hold the chunk number in their third word -
+// rd_bd_header and rd_bx_header both do: the decode slot with n_ch groups of rd_bu_cap(n_win) places, the expect slot with
+// the table's size in groups of one.  recs, hdr: device addresses inside the slot the kernel in front filled; qual: a
+// device address (mapped host memory) with room for n_groups x cap records, record [group][place] beside its message.
+// The receiver's quality slot:  [n_ch][cap] rd_burst_quality | [RD_BX_MAX] rd_burst_quality.
+// narrow_tab: the device table of rd_bd_narrow_upload for cfg's symbol_length; may be null with symbol_length < 4 only.
+struct rd_bq_header {
+    uint32_t n_msgs, other;
+    uint32_t chunk;
+    uint32_t pad;
+};
+static inline size_t rd_bq_expect_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst_quality); }
+static inline size_t rd_bq_slot_bytes(int n_ch, size_t n_win) { return rd_bq_expect_offset(n_ch, n_win) + (size_t)RD_BX_MAX * sizeof(rd_burst_quality); }
+int rd_burst_quality_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                            size_t n_out, int noise_gap, const uint32_t *narrow_tab, const rd_burst_msg *recs, size_t cap,
+                            const rd_bq_header *hdr, int n_groups, rd_burst_quality *qual, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

@@ -62,6 +62,14 @@
 // next written by the channelizer of chunk k+1, later on the same stream, and d_out[s] by that of chunk k+2.  Its records
 // and headers go into the same slot, which the fetch copies out; step 7' runs there, against what the fetch of the chunk
 // before delivered.
+// Burst quality (rd_wb_set_burst_quality / rd_wb_burst_message_quality / rd_wb_expected_message_quality;
+// rd_burst_quality.hip): a flag and the noise gap, kept like repair.  With it on, k_chan_burst_quality is queued behind
+// k_chan_burst_decode over the decode slot and, when k_chan_burst_expect was launched, behind it over the expect slot; it
+// reads what the kernel in front wrote into the mapped slot, d_out[s] and d_out[s ^ 1] under the ordering above, and
+// writes into a mapped pinned slot of its own per parity ([n_ch][cap] | [RD_BX_MAX] records).  The fetch copies a quality
+// record out with its message and drops it with it (steps 7 / 7').  It needs the narrow-band tables whenever
+// symbol_length >= 4, whether or not the narrow decoder is on: the submit uploads them once.  Off: nothing is allocated,
+// nothing launched, nothing copied.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -154,6 +162,13 @@ struct rd_wideband {
     std::vector<rd_burst_msg> xm_last, xm_prev;
     uint32_t xc_last[RD_BX_MAX] = {};
     long xm_chunk = -1;
+    // burst quality: on / off and the noise gap of the chunks submitted from now on (off whenever decode is off), the
+    // mapped pinned slots per parity (rd_internal.h: rd_bq_slot_bytes), and the rows the last fetch kept beside bm_last
+    // and xm_last
+    bool quality = false, last_quality = false;
+    int q_gap = 0;
+    uint8_t *h_bq[2] = {nullptr, nullptr};
+    std::vector<rd_burst_quality> bq_last, xq_last;
 };
 #define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
@@ -238,6 +253,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_bu[i]);
             hipHostFree(w->h_bd[i]);
             hipHostFree(w->h_bx[i]);
+            hipHostFree(w->h_bq[i]);
         }
         hipFree(w->d_lvacc);
         hipFree(w->d_nb);
@@ -332,7 +348,14 @@ static int wb_alloc_decode(rd_wideband *w) {
             WCHK(hipHostMalloc((void **)&w->h_bx[i], RD_BX_SLOT_BYTES, hipHostMallocMapped));
             memset(w->h_bx[i], 0xFF, RD_BX_SLOT_BYTES);
         }
-    if (w->narrow && !w->d_nb) return rd_bd_narrow_upload(w->cfg.symbol_length, &w->d_nb);
+    if (w->quality)
+        for (int i = 0; i < 2; i++)
+            if (!w->h_bq[i]) {
+                WCHK(hipHostMalloc((void **)&w->h_bq[i], rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
+                memset(w->h_bq[i], 0xFF, rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)));
+            }
+    if ((w->narrow || (w->quality && w->cfg.symbol_length >= RD_BD_NB_MIN_SL)) && !w->d_nb)
+        return rd_bd_narrow_upload(w->cfg.symbol_length, &w->d_nb);
     return RD_OK;
 }
 
@@ -358,18 +381,20 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     w->last_bursts = false;
     for (int i = 0; i < 2; i++)
         if (w->h_bu[i]) memset(wb_bu_floor(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_burst_floor));
+    w->last_quality = false;      // (the setting stays)
     w->last_decode = false;       // (the setting stays; n_sub = 0: the first chunk has no look-back)
-    w->bm_chunk = -1;             // (... and no chunk before it whose records its own could repeat)
-    w->bm_prev.clear();
+    w->bm_chunk = -2;             // (... and no chunk before it whose records its own could repeat: -2, for the fetch of
+    w->bm_prev.clear();           //  chunk 0 looks for chunk -1 and must not take the run before for it)
     for (int i = 0; i < 2; i++)
         if (w->h_bd[i]) memset(wb_bd_header(w, i), 0xFF, (size_t)w->n_ch * sizeof(rd_bd_header));
     w->expect.clear();            // (the windows refer to the clock that has just restarted)
-    w->xm_chunk = -1;
+    w->xm_chunk = -2;             // (as bm_chunk: an expected record of chunk 0 repeats nothing of the run before)
     w->xm_prev.clear();
     for (int i = 0; i < 2; i++) {
         w->bx_n[i] = 0;
         w->bx_launched[i] = false;
         if (w->h_bx[i]) memset(w->h_bx[i], 0xFF, RD_BX_SLOT_BYTES);
+        if (w->h_bq[i]) memset(w->h_bq[i], 0xFF, rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)));
     }
     return RD_OK;
 }
@@ -443,6 +468,7 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         w->decode = false;
         w->repair = 0;
         w->narrow = false;
+        w->quality = false;
         w->expect.clear();
     }
     return RD_OK;
@@ -461,6 +487,7 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
     if (!w->decode) {
         w->repair = 0;
         w->narrow = false;
+        w->quality = false;
         w->expect.clear();
     }
     return RD_OK;
@@ -498,6 +525,45 @@ extern "C" int rd_wb_burst_narrow(rd_wideband *w, int *on) {
     if (!w || !on) return rd_fail_msg(RD_ERR_ARG, "null argument");
     *on = w->narrow ? 1 : 0;
     return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_quality(rd_wideband *w, int on, int noise_gap) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    if (noise_gap < 0 || noise_gap > RD_BQ_MAX_GAP)
+        return rd_fail_msg(RD_ERR_ARG, "burst quality: noise_gap %d, not 0 .. %d", noise_gap, RD_BQ_MAX_GAP);
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before burst quality is switched", rd_demod_inflight(w->dem));
+    if (!w->decode) return rd_fail_msg(RD_ERR_STATE, "burst quality needs burst decode on (rd_wb_set_burst_decode)");
+    w->quality = on != 0;
+    w->q_gap = noise_gap;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_quality(rd_wideband *w, int *on, int *noise_gap) {
+    if (!w || !on || !noise_gap) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *on = w->quality ? 1 : 0;
+    *noise_gap = w->q_gap;
+    return RD_OK;
+}
+
+static int wb_quality_rows(rd_wideband *w, const std::vector<rd_burst_quality> &rows, rd_burst_quality *out, int cap, int *n) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_quality) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with burst quality off (rd_wb_set_burst_quality)");
+    *n = (int)rows.size();
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d quality records, room for %d", *n, cap);
+    if (*n) memcpy(out, rows.data(), (size_t)*n * sizeof(rd_burst_quality));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_message_quality(rd_wideband *w, rd_burst_quality *out, int cap, int *n) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    return wb_quality_rows(w, w->bq_last, out, cap, n);
+}
+
+extern "C" int rd_wb_expected_message_quality(rd_wideband *w, rd_burst_quality *out, int cap, int *n) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    return wb_quality_rows(w, w->xq_last, out, cap, n);
 }
 
 extern "C" int rd_wb_burst_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *long_runs, int n_channels) {
@@ -663,6 +729,17 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
             rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
                                         w->clock, (uint64_t)w->n_sub, w->repair, w->narrow ? w->d_nb : nullptr, bu, bd, w->st);
             if (rc) return rc;
+            // quality slot s: free by the argument for the level slot; the decode slot is read on the device (header comment)
+            rd_burst_quality *bq = nullptr;
+            const size_t q_cap = rd_bu_cap(wb_bu_windows(w));
+            const uint8_t *q_prev = w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr;
+            if (w->quality) {
+                WCHK(hipHostGetDevicePointer((void **)&bq, w->h_bq[s], 0));
+                rc = rd_burst_quality_launch(&w->cfg, w->d_out[s], q_prev, 2 * w->B, w->n_ch, w->B, w->q_gap, w->d_nb, (const rd_burst_msg *)bd,
+                                             q_cap, (const rd_bq_header *)((uint8_t *)bd + rd_bd_header_offset(w->n_ch, wb_bu_windows(w))),
+                                             w->n_ch, bq, w->st);
+                if (rc) return rc;
+            }
             // expect slot s: free by the argument for the level slot; the candidate ranges travel in it (header comment)
             const int nx = (int)w->expect.size();
             w->bx_n[s] = nx;
@@ -674,6 +751,12 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                                             w->clock, (uint64_t)w->n_sub, nx, w->repair, w->narrow ? w->d_nb : nullptr, bx, w->st);
                 if (rc) return rc;
                 w->bx_launched[s] = true;
+                if (w->quality) {
+                    rc = rd_burst_quality_launch(&w->cfg, w->d_out[s], q_prev, 2 * w->B, w->n_ch, w->B, w->q_gap, w->d_nb, (const rd_burst_msg *)bx,
+                                                 1, (const rd_bq_header *)((uint8_t *)bx + RD_BX_HEADER_OFFSET), nx,
+                                                 bq + (size_t)w->n_ch * q_cap, w->st);
+                    if (rc) return rc;
+                }
             }
         }
     }
@@ -689,12 +772,17 @@ static int wb_fetched(rd_wideband *w, int rc) {
     w->last_spec = false;
     w->last_bursts = false;
     w->last_decode = false;
+    w->last_quality = false;
     if (w->decode) {
         // as the burst records below: k_chan_burst_decode ran before the demodulator launch that has reported.  Every
         // header carries the chunk's number; a channel's messages are the first n_msgs of its record places.
         const size_t cap_c = rd_bu_cap(wb_bu_windows(w));
         const rd_burst_msg *recs = (const rd_burst_msg *)w->h_bd[w->last & 1];
         const rd_bd_header *hd = wb_bd_header(w, (int)(w->last & 1));
+        // quality on: record i of the quality slot belongs to record i of the message slot, and goes where it goes
+        const rd_burst_quality *qrecs = w->quality ? (const rd_burst_quality *)w->h_bq[w->last & 1] : nullptr;
+        w->bq_last.clear();
+        w->xq_last.clear();
         // Step 7 (include/rtldavis_hip.h, BURST DECODE): a look-back record that repeats - same channel, same data, less
         // than SL outputs apart - a record the fetch of the chunk before DELIVERED is the second report of a packet that
         // ends at the boundary, and is dropped.  A chunk that was never fetched delivered nothing.
@@ -711,7 +799,14 @@ static int wb_fetched(rd_wideband *w, int rc) {
             w->bl_last[c] = h.long_runs;
             for (uint32_t i = 0; i < h.n_msgs; i++) {
                 const rd_burst_msg m = recs[(size_t)c * cap_c + i];
-                if (!rd_bd_repeats(m, w->bm_prev.data(), w->bm_prev.size(), w->cfg.symbol_length)) w->bm_last.push_back(m);
+                if (rd_bd_repeats(m, w->bm_prev.data(), w->bm_prev.size(), w->cfg.symbol_length)) continue;
+                w->bm_last.push_back(m);
+                if (qrecs) {
+                    const rd_burst_quality q = qrecs[(size_t)c * cap_c + i];
+                    if (q.chunk != (uint32_t)w->last)
+                        return rd_fail_msg(RD_ERR_DEVICE, "quality record %u of channel %d belongs to chunk %u, not %ld", i, c, q.chunk, w->last);
+                    w->bq_last.push_back(q);
+                }
             }
         }
         w->bm_chunk = w->last;
@@ -732,11 +827,19 @@ static int wb_fetched(rd_wideband *w, int rc) {
                     return rd_fail_msg(RD_ERR_DEVICE, "expectation %d: header of chunk %u (%u messages, %u candidates), not of chunk %ld with %u candidates",
                                        i, h.chunk, h.n_msgs, h.candidates, w->last, w->bx_cand[sx][i]);
                 w->xc_last[i] = h.candidates;
-                if (h.n_msgs && !rd_bx_repeats(xr[i], w->xm_prev.data(), w->xm_prev.size(), w->cfg.symbol_length)) w->xm_last.push_back(xr[i]);
+                if (!h.n_msgs || rd_bx_repeats(xr[i], w->xm_prev.data(), w->xm_prev.size(), w->cfg.symbol_length)) continue;
+                w->xm_last.push_back(xr[i]);
+                if (qrecs) {
+                    const rd_burst_quality q = qrecs[(size_t)w->n_ch * cap_c + (size_t)i];
+                    if (q.chunk != (uint32_t)w->last)
+                        return rd_fail_msg(RD_ERR_DEVICE, "quality record of expectation %d belongs to chunk %u, not %ld", i, q.chunk, w->last);
+                    w->xq_last.push_back(q);
+                }
             }
         }
         w->xm_chunk = w->last;
         w->last_decode = true;
+        w->last_quality = w->quality;
     }
     if (w->bursts) {
         // as the level records below: k_chan_bursts ran before the demodulator launch that has reported.  Every floor

@@ -85,6 +85,15 @@ EXPECT_DTYPE = np.dtype([("channel", np.int32), ("id", np.uint32), ("t_lo", np.u
                          ("corr_re", np.int32), ("corr_im", np.int32)])
 
 
+# burst_message_quality() / expected_message_quality(): one row per message row - the layout of rd_burst_quality
+QUALITY_DTYPE = np.dtype([("pkt", np.uint64), ("sig", np.uint64), ("noise", np.uint64), ("pkt_nb", np.uint64),
+                          ("sig_nb", np.uint64), ("noise_nb", np.uint64), ("n_noise", np.uint32), ("clipped", np.uint32),
+                          ("peak", np.uint16), ("g", np.uint8), ("flags", np.uint8), ("chunk", np.uint32)])
+QUALITY_INBAND = 1                     # ``flags`` bit 0: ``g`` and the ``_nb`` sums are valid
+QUALITY_UNMEASURABLE = 128             # ``flags`` bit 7: the message's channel or tau was out of range, every sum is 0
+QUALITY_MAX_GAP = 1024                 # ``noise_gap`` at most
+
+
 class BurstMessages(NamedTuple):
     """``WidebandReceiver.burst_messages()``: ``records`` (structured array of ``BURST_MSG_DTYPE``, one row per burst that
     carried a CRC-valid message, channels ascending, a channel's runs ascending), ``long_runs`` (uint32 per channel: runs
@@ -127,6 +136,28 @@ class Spectrum(NamedTuple):
 def spectrum_freqs(centre_hz: int, wide_rate: int, n_bins: int) -> np.ndarray:
     """The bin centres of an ``n_bins`` spectrum in Hz, ascending; entry ``n_bins // 2`` is ``centre_hz``."""
     return float(centre_hz) + (np.arange(n_bins, dtype=np.float64) - n_bins // 2) * (float(wide_rate) / n_bins)
+
+
+def burst_packets(records, quality, n_channels: int, symbol_length: int, inband: bool = False,
+                  use_repaired: bool = False, packet_symbols: int = 80) -> List[List[Packet]]:
+    """One ``List[Packet]`` per channel from message rows (``burst_messages().records`` or ``expected_messages().records``)
+    and their quality rows: ``Packet(index=-1, data, rssi, snr)`` with ``acquire.rssi_db`` and ``acquire.snr_db``
+    (``snr_inband_db`` with ``inband``).  ``index = -1`` selects the branch of the reference's ``Parser.parse`` for packets
+    demodulated in hardware (no frequency error from the discriminator), so the rows go through the unmodified parser.
+    Repaired rows (``flags`` bit 1) are left out unless ``use_repaired``; ``data`` is the row's first
+    ``packet_symbols / 8`` on-air bytes."""
+    from . import acquire
+    recs = np.asarray(getattr(records, "records", records))
+    quality = np.asarray(quality)
+    if recs.shape != quality.shape:
+        raise ValueError(f"Incompatible array sizes: {recs.size} message rows, {quality.size} quality rows")
+    out: List[List[Packet]] = [[] for _ in range(int(n_channels))]
+    for m, q in zip(recs.reshape(-1), quality.reshape(-1)):
+        if int(m["flags"]) & BURST_MSG_REPAIRED and not use_repaired:
+            continue
+        snr = acquire.snr_inband_db(q, symbol_length) if inband else acquire.snr_db(q, symbol_length)
+        out[int(m["channel"])].append(Packet(-1, np.array(m["data"][: int(packet_symbols) // 8], dtype=np.uint8), acquire.rssi_db(q, symbol_length), snr))
+    return out
 
 
 class WidebandReceiver:
@@ -490,6 +521,47 @@ class WidebandReceiver:
         chunk = C.c_uint64(0)
         _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
         return ExpectedMessages(recs[: n.value].copy(), cand[cand != 0xFFFFFFFF].copy(), int(chunk.value))
+
+    def set_burst_quality(self, on: bool = True, noise_gap: int = 0) -> None:
+        """From the next chunk on, every row of ``burst_messages()`` and ``expected_messages()`` gets a row of
+        ``QUALITY_DTYPE``, exact integers in the units of the channelized bytes (a = 2 b - 255): ``pkt`` / ``sig`` /
+        ``noise`` are the sums of |z|^2 over the packet, its 16 sync symbols and the ``n_noise`` outputs that end
+        ``noise_gap`` outputs in front of the packet (the reference's noise window at ``noise_gap = 0``; cut at the start
+        of the chunk before, possibly to nothing); ``peak`` and ``clipped`` are the largest component and the bytes at 0
+        or 255 inside the packet; ``pkt_nb`` / ``sig_nb`` / ``noise_nb`` (``flags`` bit 0) are the same sums behind the
+        narrow-band filter of ``set_burst_narrow`` centred at ``g`` / 64 cycles per output, chosen from the row's own
+        ``f_re, f_im`` - whether or not the row was decoded behind that filter.  ``acquire.rssi_db``, ``snr_db``,
+        ``snr_inband_db`` and ``snr_floor_db`` turn a row into decibels, ``burst_packets`` into ``Packet``s.  What a
+        transmitter sends in front of its sync word has not been measured in this project: ``noise_gap`` (0 .. 1024) moves
+        the window further out, and ``snr_floor_db`` does without it.  Off (the default) is the receiver without it, byte
+        for byte.  Needs a receiver with nothing in flight and ``set_burst_decode(True)`` (RuntimeError; switching decode
+        or bursts off switches it off, ``reset()`` keeps it); ValueError for a ``noise_gap`` out of range."""
+        _lib.check(_lib.lib().rd_wb_set_burst_quality(self._h, 1 if on else 0, int(noise_gap)))
+
+    def burst_quality(self):
+        """``(on, noise_gap)`` the next submitted chunk will use."""
+        on, gap = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().rd_wb_burst_quality(self._h, C.byref(on), C.byref(gap)))
+        return bool(on.value), int(gap.value)
+
+    def _quality_rows(self, fn) -> np.ndarray:
+        n = C.c_int(0)
+        rc = fn(self._h, None, 0, C.byref(n))
+        if rc != _lib.RD_ERR_CAPACITY:
+            _lib.check(rc)
+        out = np.empty(n.value, QUALITY_DTYPE)
+        if out.size:
+            _lib.check(fn(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out
+
+    def burst_message_quality(self) -> np.ndarray:
+        """``QUALITY_DTYPE`` rows parallel to ``burst_messages().records`` of the same fetch (a row the fetch dropped as a
+        repeat took its quality with it).  RuntimeError before any fetch and when quality was off for that chunk."""
+        return self._quality_rows(_lib.lib().rd_wb_burst_message_quality)
+
+    def expected_message_quality(self) -> np.ndarray:
+        """``QUALITY_DTYPE`` rows parallel to ``expected_messages().records`` of the same fetch."""
+        return self._quality_rows(_lib.lib().rd_wb_expected_message_quality)
 
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel

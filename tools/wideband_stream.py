@@ -13,7 +13,8 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its 
                                     [--retune {none,one,all}] [--levels] [--bursts [--bursts-out FILE]]
                                     [--burst-decode [--burst-decode-out FILE]]
                                     [--burst-repair N [--burst-repair-out FILE]]
-                                    [--burst-narrow [--burst-narrow-out FILE]] [--track [--track-out FILE]] [--json OUT]
+                                    [--burst-narrow [--burst-narrow-out FILE]] [--track [--track-out FILE]]
+                                    [--burst-quality [--burst-quality-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -37,6 +38,9 @@ twin of a packet (synth.make_packet(..., flip_bit=...): one payload symbol wrong
 passes the sync word runs the whole search of the repair - the list, the 8 singles, the 28 pairs - and, the wrong symbol
 being a strong one, mostly finds nothing.  Both go into --burst-repair-out (default profiles/wideband_burst_repair.txt),
 with the spread of the windows beside the difference.  The kernel's own time is not measured here.
+--burst-quality: as --burst-narrow, but the second window of every repeat has WidebandReceiver.set_burst_quality(True) on
+(k_chan_burst_quality behind k_chan_burst_decode) and reads burst_message_quality() per chunk; written to
+--burst-quality-out (default profiles/wideband_burst_quality.txt).
 --burst-narrow: as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts + decode +
 WidebandReceiver.set_burst_narrow(True) on (k_chan_burst_decode<false, true>: the narrow-band filter in front of the
 discriminator, in every chunk that holds a run); the capture is --burst-decode's, an undamaged burst on every channel.
@@ -88,6 +92,10 @@ def main():
                     help="time every window with bursts + decode on, and with the narrow-band filter on top; write --burst-narrow-out")
     ap.add_argument("--burst-narrow-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                "wideband_burst_narrow.txt"))
+    ap.add_argument("--burst-quality", action="store_true",
+                    help="time every window with bursts + decode on, and with burst quality on top; write --burst-quality-out")
+    ap.add_argument("--burst-quality-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                                "wideband_burst_quality.txt"))
     ap.add_argument("--track", action="store_true",
                     help="time every window with bursts + decode on, and with 8 expectations active in every chunk on top; write --track-out")
     ap.add_argument("--track-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
@@ -107,7 +115,10 @@ def main():
     track = args.track
     if track and (args.bursts or args.burst_decode or repair or narrow):
         raise SystemExit("--track alone: each run compares two windows")
-    decode = args.burst_decode or repair > 0 or narrow or track
+    quality = args.burst_quality
+    if quality and (args.bursts or args.burst_decode or repair or narrow or track):
+        raise SystemExit("--burst-quality alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0 or narrow or track or quality
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
@@ -143,6 +154,7 @@ def main():
     bursts_on, decode_on, n_dmsgs, n_repaired, n_right, base_msgs = [False], [False], [0], [0], [0], [0]
     n_narrow = [0]
     track_on, n_xmsgs, n_xcand = [False], [0], [0]
+    quality_on, n_qrows, q_snr = [False], [0], []
 
     def track_table(clock):
         """8 expectations, every one with 201 candidates inside the chunk that begins at `clock`, spread over the channels."""
@@ -166,6 +178,11 @@ def main():
                 n_dmsgs[0] += len(msgs.records)
                 if narrow:
                     n_narrow[0] += int(acquire.narrowband(msgs.records).sum())
+                if quality_on[0]:
+                    q = rx.burst_message_quality()
+                    n_qrows[0] += len(q)
+                    if len(q):
+                        q_snr[:] = [q]                       # (turned into decibels after the window, outside the timing)
                 if track_on[0]:
                     x = rx.expected_messages()
                     n_xmsgs[0] += len(x.records)
@@ -209,12 +226,17 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track)
+                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track or quality)
                 if repair:
                     rx.set_burst_repair(repair if on else 0)
                 if narrow:
                     rx.set_burst_narrow(on)
-                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track
+                if quality:
+                    rx.set_burst_quality(on)
+                quality_on[0] = on and quality
+                n_qrows[0] = 0
+                del q_snr[:]
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track or quality
                 track_on[0] = on and track
                 n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = n_xmsgs[0] = n_xcand[0] = 0
                 acq.reset()
@@ -337,7 +359,32 @@ def main():
                 f"{n_dmsgs[0]} burst messages; last window without: {base_msgs[0]} burst messages",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
-        with open(args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        if quality:
+            res["burst_quality"] = {"messages_last_window": n_dmsgs[0], "quality_rows_last_window": n_qrows[0],
+                                    "messages_last_window_without": base_msgs[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            snr_txt = "no rows"
+            if q_snr:
+                db = [(acquire.rssi_db(r, cfg.symbol_length), acquire.snr_db(r, cfg.symbol_length), acquire.snr_inband_db(r, cfg.symbol_length)) for r in q_snr[0]]
+                snr_txt = "the last chunk's rows: median rssi_db %.1f, snr_db %.1f, snr_inband_db %.1f" % tuple(np.median(np.array(db), axis=0))
+            lines = [
+                "WidebandReceiver burst quality (k_chan_burst_quality behind k_chan_burst_decode), bursts + decode + quality on against bursts + "
+                "decode on in the same run: tools/wideband_stream.py --burst-quality" + (" --parse" if args.parse else ""),
+                lines[1] + "; a burst on every channel",
+                f"  bursts + decode on:            {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + quality on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(burst_messages() and burst_message_quality() read per chunk, the messages handed to Acquisition.update)",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + quality {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: quality {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with quality: {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages, {n_qrows[0]} quality rows ({snr_txt}), "
+                f"{n_asked[0]} retunes proposed; last window without: {base_msgs[0]} burst messages",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
+        with open(args.burst_quality_out if quality else args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
