@@ -45,11 +45,18 @@ def next_phase(phase, shift, new_shift, t_b, fo):
     return [(int(p) + (int(s) - int(s2)) * int(t_b)) % int(fo) for p, s, s2 in zip(phase, shift, new_shift)]
 
 
-@functools.lru_cache(maxsize=None)
+EXTRA = {}      # cases another module brings along (full_stack_cases): name -> a namespace with the fields of case()
+
+
 def case(name):
     """Everything a test needs of one configuration: the receiver's arguments, the capture and its chunks, and the
     retune schedule {chunk index: offsets}: a subset of the channels before chunk 2, all of them before chunk 3
     (negative shifts and both band edges among them)."""
+    return EXTRA[name] if name in EXTRA else _case(name)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
     fmt, n_ch, decim, T, bs, sl, nk = CASES[name]
     seed = sum(map(ord, name))
     fo = 19200 * sl
