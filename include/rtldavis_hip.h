@@ -603,7 +603,8 @@ int rd_wb_bursts(rd_wideband *w, rd_burst *out, int cap, int *n, rd_burst_floor 
  * Not solved here, for a station never yet heard: a packet of which only the last few outputs reach into a chunk whose
  * window 0 stays OFF, a run of more than 32 windows, and a packet that ends a few outputs into a chunk whose run holds
  * nothing but the transmission's trailing symbols are missed.  For a station heard once, BURST EXPECT below decodes at
- * the predicted place without a run and has none of the three gaps.  A burst the demodulator decodes too is reported by
+ * the predicted place without a run and has none of the three gaps; BURST SEARCH, further below, tests every position
+ * of every channel and needs neither a run nor a station heard before.  A burst the demodulator decodes too is reported by
  * both paths (rd_wb_parsed and here): the caller dedupes by channel, chunk and data.
  * rd_wb_set_burst_decode: on / off (the default: nothing is launched).  Needs a quiet receiver (RD_ERR_STATE otherwise),
  * like rd_wb_set_bursts, and bursts on (RD_ERR_STATE otherwise; rd_wb_set_bursts(w, 0) switches decode off too).
@@ -637,7 +638,9 @@ typedef struct rd_burst_msg {
     int32_t  tau;            /* the end of the first symbol, relative to the chunk's first output; may be negative */
     uint32_t flags;          /* bit 0: the region reached into the previous chunk; bit 1 (RD_BURST_MSG_REPAIRED): repaired;
                                 bit 2 (RD_BURST_MSG_NARROW): step 4n; bit 3 (RD_BURST_MSG_EXPECTED): a record of BURST EXPECT,
-                                whose bit 0 says that the region began before the chunk */
+                                whose bit 0 says that the region began before the chunk; bit 4 (RD_BURST_MSG_SEARCHED): a
+                                record of BURST SEARCH, whose bit 0 says that the packet began before the chunk, `first` is
+                                the centre's index in the list and pad = (hits, 0, 0, g) */
     uint64_t time;           /* the chunk's absolute output clock + tau */
     uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped; in
                                 the units of step 4n when bit 2 is set: not comparable across the two kinds */
@@ -719,6 +722,74 @@ typedef struct rd_expect {
 int rd_wb_set_burst_expect(rd_wideband *w, const rd_expect *e, int n);
 int rd_wb_burst_expect(rd_wideband *w, rd_expect *out, int cap, int *n);
 int rd_wb_expected_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, uint32_t *candidates, int n_cand);
+/* BURST SEARCH (k_chan_burst_search, rd_burst_search.hip): find a station NEVER yet heard, with no energy gate and no
+ * prior knowledge of time.  BURST DECODE needs a clean run of ON windows and BURST EXPECT a station heard before; between
+ * the level at which a run is found and the level at which an expectation still decodes lie about 7 dB.  The sync word
+ * 0xCB89 has eight ones and eight zeros, so behind the narrow-band filter the sum of the 16 sync symbols' phase-difference
+ * sums points along the carrier, and each symbol can be sliced around that sum: sync equality plus CRC-16 then prove a
+ * message at every output position of every channel.  The host passes a short list of filter centres (one centre covers
+ * about +-2 grid steps at moderate noise, +-1 near the limit; rtldavis_amd/acquire.py: search_centres).  With a non-empty
+ * list in force a chunk carries one more launch, behind k_chan_burst_expect (or k_chan_burst_decode) and in front of the
+ * demodulator: a price, one filter pass over every channel per centre.  All quantities are exact integers.  SL, N, sync,
+ * LOOK, have_prev, z, the tables H[g] and C[g], M = SL + 2 and the shift RD_BD_NB_SHIFT are those of BURST DECODE step 4n.
+ * Chunk k has clock K and B = block_size outputs; lo = have_prev ? -LOOK : 0.  For every channel c and every centre g_i
+ * of the list (i ascending):
+ *   1s. z[t] is the chunk's own for lo <= t < B, chunk k-1's for t < 0, and 0 outside lo .. B-1 at both ends.
+ *       y[t] = (sum_k H[g][k] z[t-k] + 2^10) >> 11 for lo <= t < B.  p'[t] = y[t] conj(y[t-1]) for lo < t < B.
+ *       S[t] = sum_{i < SL} p'[t-i], complex with components below 2^31, for lo + SL <= t < B.
+ *   2s. candidates: tau with max(lo + SL, -SL (N-1)) <= tau <= B - 1 - SL (N-1).  The packet ends in this chunk, as
+ *       everywhere else; the candidates of consecutive chunks do not overlap.
+ *   3s. per tau: D = sum_{k < 16} S[tau + SL k], components below 2^35.  D = (0, 0): no candidate.
+ *       sh = max(0, bitlength(max(|D.re|, |D.im|)) - 15), ca = D.re >> sh, cb = D.im >> sh (arithmetic: floor, as in 4n);
+ *       ca = cb = 0: no candidate.  s_k = S[tau + SL k].im ca - S[tau + SL k].re cb for k < N, |s| < 2^47; bit_k = s_k > 0.
+ *       The first 16 bits equal sync - such a position counts in sync_hits -, and the N symbols pass the CRC gate of
+ *       BURST DECODE step 5.  margin = min_{k < N} |s_k|.  No repair, whatever max_flips is: a repaired candidate passes
+ *       a random syndrome up to 36 times as often, and the search tests every position.  A sync word with other than
+ *       eight ones is accepted as configured, and then D is biased towards the more frequent symbol's frequency by
+ *       (ones - 8) / 16 of the deviation's phase step: the slicing direction is off by that much.
+ *   4s. a passing tau is reported unless another passing tau' of the same (c, g_i) with |tau' - tau| < SL has a larger
+ *       margin, or the same margin and tau' < tau.  hits = the passing tau' with |tau' - tau| < SL, tau itself included
+ *       (at most 2 SL - 1 <= 101).
+ *   5s. per (i, c) at most RD_BS_PER = 4 records, the first four reported by tau, in fixed places of the slot.  Header per
+ *       (i, c): { n_msgs, sync_hits, chunk, dropped }, dropped = the reported taus beyond the fourth.  The record is a
+ *       rd_burst_msg: flags = RD_BURST_MSG_SEARCHED | RD_BURST_MSG_NARROW | (bit 0: tau - SL < 0); first = i;
+ *       pad = (hits, 0, 0, g); f_re, f_im = the sum of p' over the packet's N SL outputs (= sum_{k < N} S[tau + SL k]), so
+ *       a carrier estimate follows as for any narrow record; tau, time, margin, data, ones, id as for any record.
+ *   7s. on the host, at the fetch: a searched record is dropped when its channel, pad[3] and data equal those of a
+ *       searched record that the previous fetch delivered (after its own drop) and the times differ by less than SL.  Two
+ *       centres that both decode a packet each give their record; the caller dedupes by channel, time and data.
+ * Records: centres in list order, channels ascending, a (centre, channel)'s records by tau.  The same chunks and centres
+ * give the same bits on every run, and the result does not depend on how the kernel tiles a channel (RD_BS_TILE
+ * candidates per tile; every tile computes its halos again from the bytes).
+ * What a searched record proves: less per hour than any other record.  A random position passes the sync test with
+ * probability about 2^-16 and the CRC with 2^-16; a receiver of 51 channels and 8192 outputs per chunk tests 4 x 10^5
+ * positions per chunk and centre, which gives a false record every few minutes per centre (derived).  Bit 4 is there so
+ * that the caller can treat such a record as provisional (rtldavis_amd/track.py does).  hits and margin are reported and
+ * not gated on: a real packet has about SL - 2 adjacent passing positions, a false one has one.
+ * rd_wb_set_burst_search: the list (n centres, 0 .. RD_BS_MAX_CENTRES; n = 0, the default, clears it, and then nothing is
+ * launched and every other call returns what it returns without this section, byte for byte) in force from the next
+ * submitted chunk on.  Host bookkeeping like rd_wb_set_burst_expect: legal with two chunks in flight, no device work.
+ * RD_ERR_ARG, and nothing changes, for n outside 0 .. 8, a centre >= 64, a duplicate, symbol_length < 4, or a
+ * configuration that rd_wb_set_burst_decode refuses; RD_ERR_STATE unless burst decode is on.  rd_wb_set_burst_decode(w, 0)
+ * and rd_wb_set_bursts(w, 0) clear the list; rd_wideband_reset keeps it and forgets step 7s's memory.
+ * rd_wb_burst_search: the list the next submit will use (*n centres; RD_ERR_CAPACITY with cap < *n).
+ * rd_wb_searched_messages: the records of the chunk the last fetch returned, after step 7s, kept by that fetch; capacity
+ * and state rules are those of rd_wb_expected_messages.  hdr: NULL, or room for n_hdr = RD_BS_MAX_CENTRES x n_channels
+ * headers - [i][c] is the header of centre i of the list that chunk was submitted with and channel c, its n_msgs the
+ * device's count BEFORE step 7s; every field is RD_BX_NO_ENTRY past the list's end.  A chunk submitted with an empty list
+ * gives *n = 0, not an error. */
+#define RD_BURST_MSG_SEARCHED 16u /* rd_burst_msg.flags: found by BURST SEARCH; `first` is the centre's index in the list */
+#define RD_BS_MAX_CENTRES 8       /* centres per list */
+#define RD_BS_PER 4               /* records per (centre, channel) and chunk */
+#define RD_BS_TILE 1024           /* candidates per tile of k_chan_burst_search (tests place packets across its boundaries) */
+typedef struct rd_bs_header {
+    uint32_t n_msgs, sync_hits;
+    uint32_t chunk;               /* the chunk's sequence number since create / reset, its low 32 bits */
+    uint32_t dropped;
+} rd_bs_header;
+int rd_wb_set_burst_search(rd_wideband *w, const uint8_t *centres, int n);
+int rd_wb_burst_search(rd_wideband *w, uint8_t *out, int cap, int *n);
+int rd_wb_searched_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, rd_bs_header *hdr, int n_hdr);
 /* BURST QUALITY (k_chan_burst_quality, rd_burst_quality.hip): the power, the noise in front and the clipping of every
  * record of BURST DECODE and BURST EXPECT - what the demodulator path reports as rd_packet.rssi / .snr, in integers, and
  * the same behind the narrow-band filter of step 4n (an in-band figure: the one that corresponds to what the narrow
@@ -838,6 +909,14 @@ int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t *cur, const
 int rd_debug_burst_expect(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                           uint64_t clock, uint64_t seq, const rd_expect *e, int n_e, int max_flips, int narrow,
                           rd_burst_msg *msgs_out, uint32_t *hdr_out);
+/* rd_debug_burst_search (tests/test_burst_search.py): k_chan_burst_search alone, the same pattern - cur / prev as above,
+ * the centres checked by the rule of rd_wb_set_burst_search (RD_ERR_ARG before any device work; n >= 1; symbol_length >= 4;
+ * n_ch at most 4096).  msgs_out: RD_BS_MAX_CENTRES x n_ch x RD_BS_PER record places, hdr_out: RD_BS_MAX_CENTRES x n_ch
+ * headers, the receiver's slot: filled with 0xA5 and copied out whole, so the places past a header's n_msgs and
+ * everything of a centre index >= n come back as 0xA5. */
+int rd_debug_burst_search(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
+                          uint64_t clock, uint64_t seq, const uint8_t *centres, int n, rd_burst_msg *msgs_out,
+                          rd_bs_header *hdr_out);
 /* rd_debug_burst_quality (tests/test_burst_quality.py): k_chan_burst_quality alone, the same pattern - cur / prev as
  * above; msgs[n_ch][cap] (cap = ceil(nW / 2)) and n_msgs_per_channel[n_ch] are written into a decode slot as they are,
  * records no decoder would write included, with chunk = RD_BQ_DEBUG_CHUNK in every header.  out: n_ch x cap + RD_BX_MAX

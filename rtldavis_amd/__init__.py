@@ -6,6 +6,7 @@
 capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s front half in their kernels
 (``set_parse`` / ``parsed``); ``rtldavis_amd.parse_packet`` is the same CRC gate for one packet on the host.
 ``rtldavis_amd.track.Tracker`` predicts where a station heard once transmits next (``WidebandReceiver.set_burst_expect``).
+``WidebandReceiver.set_burst_search`` finds a station never yet heard, with no energy gate, at every output position.
 ``WidebandReceiver.set_burst_quality`` measures every burst message's power and noise on the device, and
 ``rtldavis_amd.burst_packets`` turns the rows into ``dsp.Packet``s with ``rssi`` and ``snr`` for ``protocol.Parser.parse``.
 """

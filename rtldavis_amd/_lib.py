@@ -215,6 +215,9 @@ SIGNATURES = {
     "rd_wb_set_burst_expect": (C.c_int, [_P, _P, C.c_int]),
     "rd_wb_burst_expect": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "rd_wb_expected_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
+    "rd_wb_set_burst_search": (C.c_int, [_P, _P, C.c_int]),
+    "rd_wb_burst_search": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "rd_wb_searched_messages": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_int]),
     "rd_wb_set_burst_quality": (C.c_int, [_P, C.c_int, C.c_int]),
     "rd_wb_burst_quality": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rd_wb_burst_message_quality": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
@@ -236,6 +239,8 @@ SIGNATURES = {
                                                C.c_int, C.c_int, _P, _P, _P, _P]),
     "rd_debug_burst_expect": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int,
                                         C.c_int, C.c_int, _P, _P]),
+    "rd_debug_burst_search": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int,
+                                        _P, _P]),
     "rd_debug_burst_quality": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, _P]),
 }
 

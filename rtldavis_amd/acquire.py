@@ -49,6 +49,8 @@ FLAG_FIRST, FLAG_LAST = 1, 2
 MSG_REPAIRED = 2             # wideband.BURST_MSG_REPAIRED: bit 1 of a burst message's flags
 MSG_NARROW = 4               # wideband.BURST_MSG_NARROW: bit 2
 MSG_EXPECTED = 8             # wideband.BURST_MSG_EXPECTED: bit 3
+MSG_SEARCHED = 16            # wideband.BURST_MSG_SEARCHED: bit 4
+SEARCH_GRID = 64             # wideband.BURST_NARROW_GRID: a centre is g / 64 cycles per output
 
 
 def burst_offset_hz(rec, floor_row, out_rate: int, if_hz: int) -> float:
@@ -96,6 +98,38 @@ def expected(records) -> np.ndarray:
     ``burst_messages()``."""
     recs = np.asarray(getattr(records, "records", records))
     return (recs["flags"] & MSG_EXPECTED) != 0
+
+
+def searched(records) -> np.ndarray:
+    """Boolean mask over message rows (or a ``SearchedMessages`` / ``BurstMessages`` / ``ExpectedMessages``): the rows the
+    blind search found (``flags`` bit 4; ``first`` is the centre's index in its list) - all of ``searched_messages()``,
+    none of the others.  Such a row proves less than any other (``WidebandReceiver.searched_messages``)."""
+    recs = np.asarray(getattr(records, "records", records))
+    return (recs["flags"] & MSG_SEARCHED) != 0
+
+
+def search_hits(records) -> np.ndarray:
+    """uint8 per searched row: the adjacent positions (less than ``symbol_length`` away, the row's own included) that
+    passed sync word and CRC - ``pad[0]``.  About ``symbol_length - 2`` for a real packet and 1 for a chance hit; the
+    library gates on neither this nor ``margin``, the policy is the caller's.  0 for a row that is not a searched one."""
+    recs = np.asarray(getattr(records, "records", records))
+    return np.where((recs["flags"] & MSG_SEARCHED) != 0, recs["pad"][..., 0], 0).astype(np.uint8)
+
+
+def search_centres(offsets_hz, out_rate: int, if_hz: Optional[int] = None, spread: int = 0) -> np.ndarray:
+    """The list for ``WidebandReceiver.set_burst_search``: sorted unique grid points
+    ``g = round(64 (if_hz + off) / out_rate) mod 64`` for every carrier offset ``off`` (Hz from the channel centre, as
+    ``burst_message_offset_hz`` gives it) and the ``spread`` grid steps to either side of each.  ``if_hz`` None is the
+    receiver's default, ``-out_rate // 4``.  One centre covers about +-2 steps at moderate noise and +-1 near the limit
+    (profiles/burst_search_gain.txt); the library takes at most eight."""
+    if int(spread) < 0:
+        raise ValueError("spread: a non-negative number of grid steps")
+    i_f = -int(out_rate) // 4 if if_hz is None else int(if_hz)
+    out = set()
+    for off in np.asarray(offsets_hz, np.float64).reshape(-1):
+        g = int(round(SEARCH_GRID * (i_f + float(off)) / float(out_rate)))
+        out.update((g + d) % SEARCH_GRID for d in range(-int(spread), int(spread) + 1))
+    return np.asarray(sorted(out), np.uint8)
 
 
 # Signal quality of a message row (``WidebandReceiver.burst_message_quality()`` / ``expected_message_quality()``, rows of

@@ -299,6 +299,37 @@ bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
     return false;
 }
 
+// BURST SEARCH (include/rtldavis_hip.h): the list's rules and step 7s (a chunk's candidates, step 2s: rd_host.h, inline)
+int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why) {
+    static const char *none = "";
+    const char *dummy_why;
+    int dummy_bad;
+    if (!why) why = &dummy_why;
+    if (!bad) bad = &dummy_bad;
+    *why = none;
+    *bad = -1;
+    if (n < 0 || n > RD_BS_MAX_CENTRES) { *why = "the number of centres (0 .. 8)"; return RD_ERR_ARG; }
+    if (n > 0 && !centres) { *why = "null list"; return RD_ERR_ARG; }
+    for (int i = 0; i < n; i++) {
+        *bad = i;
+        if (centres[i] >= RD_BD_NB_GRID) { *why = "centre (0 .. 63)"; return RD_ERR_ARG; }
+        for (int j = 0; j < i; j++)
+            if (centres[j] == centres[i]) { *why = "duplicate"; return RD_ERR_ARG; }
+    }
+    *bad = -1;
+    return RD_OK;
+}
+
+bool rd_bs_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
+    if (sl <= 0) return false;
+    for (size_t i = 0; i < n_delivered; i++) {
+        const rd_burst_msg &q = delivered[i];
+        const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
+        if (q.channel == m.channel && q.pad[3] == m.pad[3] && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
+    }
+    return false;
+}
+
 // BURST DECODE step 4n (include/rtldavis_hip.h): designed in float64, every product and quotient in the order written
 // there - tests/burst_narrow_cases.py evaluates the same expressions in NumPy and must get the same integers.
 extern "C" int rd_bd_narrow_table(int sl, int16_t *taps, int16_t *centres) {

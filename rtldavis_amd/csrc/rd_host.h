@@ -7,6 +7,7 @@
 //   rd_check_block_count  "Incompatible array sizes" (py:32-36, py:145-149)
 //   rd_waiter             the polling policy of every host wait: spin, then yield, then sleep, with a deadline
 //   rd_bq_windows_of      BURST QUALITY: a record's packet, sync and noise windows (inline: the kernel evaluates it too)
+//   rd_bs_range           BURST SEARCH: a chunk's candidate positions (inline: the kernel evaluates it too)
 // py = /root/reference/src/rtldavis/dsp.py
 #pragma once
 #include <stddef.h>
@@ -63,6 +64,15 @@ bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t cloc
                  int32_t *tau_b);
 bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
 
+// BURST SEARCH (include/rtldavis_hip.h), the parts that need no device.
+// rd_bs_check_centres: RD_OK, or RD_ERR_ARG with *why naming the rule and *bad the offending centre's index (-1: the
+// count n outside 0 .. RD_BS_MAX_CENTRES or a null list) - a centre >= RD_BD_NB_GRID, or one that repeats an earlier one.
+// rd_bs_range: step 2s - false when the chunk has no candidate, else *tau_a .. *tau_b = max(lo + sl, -sl (n_sym - 1)) ..
+// block_size - 1 - sl (n_sym - 1), lo = have_prev ? -look : 0 (defined below, inline).
+// rd_bs_repeats: step 7s - one of `delivered` has m's channel, pad[3] and data and a time less than sl outputs from m's.
+int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why);
+bool rd_bs_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
+
 // BURST QUALITY (include/rtldavis_hip.h): the three windows of a record whose first symbol ends at tau, as half-open
 // ranges of outputs relative to the chunk's first - packet [p0, p1), sync [p0, s1), noise [n0, n1) with n1 - n0 = n_noise
 // (n0 = n1 = p0 when the intersection with t >= lo_lim is empty).  rd_bq_windows_of: false, and *w zeroed, for a record
@@ -74,6 +84,17 @@ bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
 #else
 #define RD_HOST_DEVICE
 #endif
+// (rd_bs_range: the one definition serves the host's tests and k_chan_burst_search, which walks exactly this range)
+RD_HOST_DEVICE static inline bool rd_bs_range(int sl, int n_sym, int block_size, int look, int have_prev, int32_t *tau_a, int32_t *tau_b) {
+    if (sl < 1 || n_sym < 1 || block_size < 1 || look < 0 || !tau_a || !tau_b) return false;
+    const int64_t body = (int64_t)sl * (int64_t)(n_sym - 1);
+    const int64_t lo = have_prev ? -(int64_t)look : 0;
+    const int64_t a = lo + sl > -body ? lo + sl : -body, b = (int64_t)block_size - 1 - body;
+    if (b < a || a < INT32_MIN || b > INT32_MAX) return false;
+    *tau_a = (int32_t)a;
+    *tau_b = (int32_t)b;
+    return true;
+}
 struct rd_bq_windows {
     int32_t p0, p1, s1, n0, n1;
 };

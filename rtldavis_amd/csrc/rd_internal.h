@@ -313,6 +313,20 @@ int rd_burst_expect_stage(const rd_config *cfg, int have_prev, uint64_t clock, c
 int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                            size_t n_out, uint64_t clock, uint64_t seq, int n, int max_flips, const uint32_t *narrow_tab,
                            void *slot_dev, hipStream_t st);
+// Burst search of a channelized chunk (rd_burst_search.hip: k_chan_burst_search; the definition: include/rtldavis_hip.h,
+// BURST SEARCH), queued behind rd_burst_expect_launch (or rd_burst_decode_launch) on the same stream.  slot: a device
+// address (mapped host memory) of rd_bs_slot_bytes(n_ch) laid out as
+//   [RD_BS_MAX_CENTRES][n_ch][RD_BS_PER] rd_burst_msg | [RD_BS_MAX_CENTRES][n_ch] rd_bs_header
+// One workgroup per (channel, centre i < n): it writes its header and the first header.n_msgs of its RD_BS_PER record
+// places; nothing of a centre index >= n is touched.  centres: host memory, n of them, checked by rd_bs_check_centres
+// (rd_host.h); they travel in the kernel's arguments.  narrow_tab: the device table of rd_bd_narrow_upload for cfg's
+// symbol_length (never null: the search is always a narrow-band one).
+#define RD_BS_MAX_CHANNELS 4096
+static inline size_t rd_bs_header_offset(int n_ch) { return (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * RD_BS_PER * sizeof(rd_burst_msg); }
+static inline size_t rd_bs_slot_bytes(int n_ch) { return rd_bs_header_offset(n_ch) + (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * sizeof(rd_bs_header); }
+int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                           size_t n_out, uint64_t clock, uint64_t seq, const uint8_t *centres, int n, const uint32_t *narrow_tab,
+                           void *slot_dev, hipStream_t st);
 // Burst quality (rd_burst_quality.hip: k_chan_burst_quality; the definition: include/rtldavis_hip.h, BURST QUALITY),
 // queued behind rd_burst_decode_launch / rd_burst_expect_launch on the same stream.  One launch walks a slot of n_groups
 // groups of `cap` record places whose 16-byte headers begin with n_msgs and hold the chunk number in their third word -

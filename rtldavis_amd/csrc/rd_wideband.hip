@@ -70,6 +70,13 @@
 // record out with its message and drops it with it (steps 7 / 7').  It needs the narrow-band tables whenever
 // symbol_length >= 4, whether or not the narrow decoder is on: the submit uploads them once.  Off: nothing is allocated,
 // nothing launched, nothing copied.
+// Burst search (rd_wb_set_burst_search / rd_wb_searched_messages; rd_burst_search.hip): the list of centres is host
+// bookkeeping like the expect table - recorded by the call, in force from the next submit, which notes the list's size
+// with the chunk's parity and hands the centres to the launch in the kernel's arguments.  k_chan_burst_search is queued
+// behind k_chan_burst_expect (behind k_chan_burst_decode when that was not launched) and in front of the chunk's
+// demodulator launch; it reads d_out[s] and the end of d_out[s ^ 1] under the ordering above and needs the narrow-band
+// tables.  Its slot per parity ([8][n_ch][4] records | [8][n_ch] headers) is allocated by the first submit with a list in
+// force; the fetch checks every header's chunk and runs step 7s.  An empty list: nothing allocated, launched or copied.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -162,6 +169,15 @@ struct rd_wideband {
     std::vector<rd_burst_msg> xm_last, xm_prev;
     uint32_t xc_last[RD_BX_MAX] = {};
     long xm_chunk = -1;
+    // burst search: the centres the next submitted chunk will use (empty whenever decode is off), the mapped pinned slots
+    // per parity (rd_internal.h: rd_bs_slot_bytes; allocated when a list is first in force), the list each parity's chunk
+    // was submitted with, and the records and headers the last fetch kept - step 7s as step 7 above
+    std::vector<uint8_t> search;
+    uint8_t *h_bs[2] = {nullptr, nullptr};
+    int bs_n[2] = {0, 0};
+    std::vector<rd_burst_msg> sm_last, sm_prev;
+    std::vector<rd_bs_header> sh_last;
+    long sm_chunk = -1;
     // burst quality: on / off and the noise gap of the chunks submitted from now on (off whenever decode is off), the
     // mapped pinned slots per parity (rd_internal.h: rd_bq_slot_bytes), and the rows the last fetch kept beside bm_last
     // and xm_last
@@ -253,6 +269,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_bu[i]);
             hipHostFree(w->h_bd[i]);
             hipHostFree(w->h_bx[i]);
+            hipHostFree(w->h_bs[i]);
             hipHostFree(w->h_bq[i]);
         }
         hipFree(w->d_lvacc);
@@ -354,7 +371,13 @@ static int wb_alloc_decode(rd_wideband *w) {
                 WCHK(hipHostMalloc((void **)&w->h_bq[i], rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)), hipHostMallocMapped));
                 memset(w->h_bq[i], 0xFF, rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)));
             }
-    if ((w->narrow || (w->quality && w->cfg.symbol_length >= RD_BD_NB_MIN_SL)) && !w->d_nb)
+    if (!w->search.empty())
+        for (int i = 0; i < 2; i++)
+            if (!w->h_bs[i]) {
+                WCHK(hipHostMalloc((void **)&w->h_bs[i], rd_bs_slot_bytes(w->n_ch), hipHostMallocMapped));
+                memset(w->h_bs[i], 0xFF, rd_bs_slot_bytes(w->n_ch));
+            }
+    if ((w->narrow || !w->search.empty() || (w->quality && w->cfg.symbol_length >= RD_BD_NB_MIN_SL)) && !w->d_nb)
         return rd_bd_narrow_upload(w->cfg.symbol_length, &w->d_nb);
     return RD_OK;
 }
@@ -395,7 +418,11 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
         w->bx_launched[i] = false;
         if (w->h_bx[i]) memset(w->h_bx[i], 0xFF, RD_BX_SLOT_BYTES);
         if (w->h_bq[i]) memset(w->h_bq[i], 0xFF, rd_bq_slot_bytes(w->n_ch, wb_bu_windows(w)));
+        w->bs_n[i] = 0;               // (the search list stays; what step 7s remembers goes)
+        if (w->h_bs[i]) memset(w->h_bs[i], 0xFF, rd_bs_slot_bytes(w->n_ch));
     }
+    w->sm_chunk = -2;
+    w->sm_prev.clear();
     return RD_OK;
 }
 
@@ -470,6 +497,7 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         w->narrow = false;
         w->quality = false;
         w->expect.clear();
+        w->search.clear();
     }
     return RD_OK;
 }
@@ -489,6 +517,7 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
         w->narrow = false;
         w->quality = false;
         w->expect.clear();
+        w->search.clear();
     }
     return RD_OK;
 }
@@ -610,6 +639,50 @@ extern "C" int rd_wb_expected_messages(rd_wideband *w, rd_burst_msg *out, int ca
     if (candidates) memcpy(candidates, w->xc_last, sizeof w->xc_last);
     if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d expected messages, room for %d", *n, cap);
     if (*n) memcpy(out, w->xm_last.data(), (size_t)*n * sizeof(rd_burst_msg));
+    return RD_OK;
+}
+
+extern "C" int rd_wb_set_burst_search(rd_wideband *w, const uint8_t *centres, int n) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    int bad = -1;
+    const char *why = "";
+    if (rd_bs_check_centres(centres, n, &bad, &why)) {
+        if (bad < 0) return rd_fail_msg(RD_ERR_ARG, "burst search: %s, got %d", why, n);
+        return rd_fail_msg(RD_ERR_ARG, "burst search: centre %d: %s", bad, why);
+    }
+    if (!w->decode) return rd_fail_msg(RD_ERR_STATE, "burst search needs burst decode on (rd_wb_set_burst_decode)");
+    if (n > 0) {
+        int rc = rd_burst_decode_check(&w->cfg);
+        if (rc) return rc;
+        if (w->cfg.symbol_length < RD_BD_NB_MIN_SL)
+            return rd_fail_msg(RD_ERR_ARG, "burst search: symbol_length %d, at least %d", w->cfg.symbol_length, RD_BD_NB_MIN_SL);
+        if (w->n_ch > RD_BS_MAX_CHANNELS) return rd_fail_msg(RD_ERR_ARG, "burst search: %d channels, at most %d", w->n_ch, RD_BS_MAX_CHANNELS);
+    }
+    w->search.assign(centres, centres + n);
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_search(rd_wideband *w, uint8_t *out, int cap, int *n) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *n = (int)w->search.size();
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d centres, room for %d", *n, cap);
+    if (*n) memcpy(out, w->search.data(), (size_t)*n);
+    return RD_OK;
+}
+
+extern "C" int rd_wb_searched_messages(rd_wideband *w, rd_burst_msg *out, int cap, int *n, rd_bs_header *hdr, int n_hdr) {
+    if (!w || !n || cap < 0 || (!out && cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (hdr && n_hdr != RD_BS_MAX_CENTRES * w->n_ch)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d headers of %d", n_hdr, RD_BS_MAX_CENTRES * w->n_ch);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_decode) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with burst decode off (rd_wb_set_burst_decode)");
+    *n = (int)w->sm_last.size();
+    if (hdr) {
+        memset(hdr, 0xFF, (size_t)n_hdr * sizeof(rd_bs_header));
+        if (!w->sh_last.empty()) memcpy(hdr, w->sh_last.data(), w->sh_last.size() * sizeof(rd_bs_header));
+    }
+    if (cap < *n) return rd_fail_msg(RD_ERR_CAPACITY, "%d searched messages, room for %d", *n, cap);
+    if (*n) memcpy(out, w->sm_last.data(), (size_t)*n * sizeof(rd_burst_msg));
     return RD_OK;
 }
 
@@ -758,6 +831,16 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                     if (rc) return rc;
                 }
             }
+            // search slot s: free by the argument for the level slot; the centres travel in the kernel's arguments
+            const int ns = (int)w->search.size();
+            w->bs_n[s] = ns;
+            if (ns) {
+                void *bs = nullptr;
+                WCHK(hipHostGetDevicePointer(&bs, w->h_bs[s], 0));
+                rc = rd_burst_search_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
+                                            w->clock, (uint64_t)w->n_sub, w->search.data(), ns, w->d_nb, bs, w->st);
+                if (rc) return rc;
+            }
         }
     }
     w->clock += w->B;
@@ -838,6 +921,31 @@ static int wb_fetched(rd_wideband *w, int rc) {
             }
         }
         w->xm_chunk = w->last;
+        // Burst search: the headers and records of the list the chunk was submitted with.  Step 7s (include/rtldavis_hip.h,
+        // BURST SEARCH) against what the fetch of the chunk before delivered.
+        const int nsr = w->bs_n[sx];
+        if (w->sm_chunk == w->last - 1) w->sm_prev.swap(w->sm_last);
+        else w->sm_prev.clear();
+        w->sm_chunk = -1;
+        w->sm_last.clear();
+        w->sh_last.clear();
+        if (nsr) {
+            const rd_burst_msg *sr = (const rd_burst_msg *)w->h_bs[sx];
+            const rd_bs_header *sh = (const rd_bs_header *)(w->h_bs[sx] + rd_bs_header_offset(w->n_ch));
+            w->sh_last.assign(sh, sh + (size_t)nsr * (size_t)w->n_ch);
+            for (int i = 0; i < nsr; i++)
+                for (int c = 0; c < w->n_ch; c++) {
+                    const rd_bs_header h = w->sh_last[(size_t)i * (size_t)w->n_ch + (size_t)c];
+                    if (h.chunk != (uint32_t)w->last || h.n_msgs > (uint32_t)RD_BS_PER)
+                        return rd_fail_msg(RD_ERR_DEVICE, "search header of centre %d, channel %d belongs to chunk %u (%u messages), not %ld",
+                                           i, c, h.chunk, h.n_msgs, w->last);
+                    for (uint32_t r = 0; r < h.n_msgs; r++) {
+                        const rd_burst_msg m = sr[((size_t)i * (size_t)w->n_ch + (size_t)c) * RD_BS_PER + r];
+                        if (!rd_bs_repeats(m, w->sm_prev.data(), w->sm_prev.size(), w->cfg.symbol_length)) w->sm_last.push_back(m);
+                    }
+                }
+        }
+        w->sm_chunk = w->last;
         w->last_decode = true;
         w->last_quality = w->quality;
     }

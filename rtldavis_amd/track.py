@@ -16,6 +16,13 @@ energy gate (include/rtldavis_hip.h, BURST EXPECT), and to say which packets of 
         trk.observe(rx.burst_messages().records)
         trk.observe(rx.expected_messages().records)
 
+A station never yet heard and too weak for a run is found by the blind search (``set_burst_search``, BURST SEARCH), whose
+rows prove less than any other: with every position of every channel tested, sync word and CRC pass by chance every few
+minutes per centre.  The acquisition loop is therefore ``search -> provisional -> expectation -> promoted``: feed
+``rx.searched_messages()`` to ``observe`` as well; a searched row of an unknown id seeds a PROVISIONAL station, which gets
+expectations like any other, is promoted by the first row of another path that ``observe`` accepts for it, and is dropped
+quietly after ``provisional_missed`` misses in a row.
+
 ``hop_pattern`` is the caller's: this package holds no station's table.  Rows of ``parsed()`` carry no clock, so a
 tracker cannot be fed from them alone; that is out of scope here.
 
@@ -58,11 +65,14 @@ class Tracker:
     ``max_missed``: a station that misses this many expectations in a row is dropped (``lost``).
     ``if_hz``: where the channel's centre lies in its channelized bytes; default ``-out_rate // 4``, the channelizer's.
     ``use_repaired``: also learn from repaired rows (``acquire.repaired``), which are not CRC-proven.
+    ``provisional_missed``: a provisional station (seeded by a searched row, ``acquire.searched``) that misses this many
+    expectations in a row is dropped; it appears in ``provisional()``, not in ``stations()`` or ``stats()``, until a
+    row of another path promotes it.
     """
 
     def __init__(self, cfg, hop_pattern: Sequence[int], *, period_outputs: Optional[int] = None,
                  guard_outputs: Optional[int] = None, drift_ppm: float = 100, max_missed: int = MAX_MISSED,
-                 if_hz: Optional[int] = None, use_repaired: bool = False) -> None:
+                 if_hz: Optional[int] = None, use_repaired: bool = False, provisional_missed: int = 2) -> None:
         self.hop_pattern = [int(c) for c in hop_pattern]
         if not self.hop_pattern or min(self.hop_pattern) < 0:
             raise ValueError("hop_pattern: a non-empty sequence of channel indices")
@@ -72,6 +82,8 @@ class Tracker:
             raise ValueError("guard_outputs must not be negative")
         if int(max_missed) < 1 or float(drift_ppm) < 0:
             raise ValueError("max_missed must be positive and drift_ppm not negative")
+        if int(provisional_missed) < 1:
+            raise ValueError("provisional_missed must be positive")
         self.symbol_length = int(cfg.symbol_length)
         self.packet_symbols = int(cfg.packet_symbols)
         self.out_rate = int(cfg.bit_rate) * self.symbol_length
@@ -84,6 +96,9 @@ class Tracker:
         self.use_repaired = bool(use_repaired)
         self._stations: Dict[int, _Station] = {}
         self._stats: Dict[int, Dict[str, int]] = {}
+        self.provisional_missed = int(provisional_missed)
+        self._provisional: Dict[int, _Station] = {}
+        self._search_stats = {"seeded": 0, "promoted": 0, "expired": 0, "ignored": 0}
 
     # ------------------------------------------------------------------------------------ the policy's numbers
     def period(self, ident: int) -> int:
@@ -111,6 +126,8 @@ class Tracker:
         if channel not in self.hop_pattern:
             return
         hop = self.hop_pattern.index(channel)
+        if self._provisional.pop(ident, None) is not None:    # confirmed: from here on a station like any other
+            self._search_stats["promoted"] += 1
         st = self._stations.get(ident)
         stats = self._stats.setdefault(ident, {"received": 0, "missed": 0, "lost": 0})
         if st is not None and abs(time - st.last) < self.period(ident) // 2:
@@ -120,18 +137,31 @@ class Tracker:
         stats["received"] += 1
 
     def observe(self, rows) -> None:
-        """Rows of ``burst_messages()`` / ``expected_messages()`` (the records, or the named tuple), in order."""
+        """Rows of ``burst_messages()`` / ``expected_messages()`` / ``searched_messages()`` (the records, or the named
+        tuple), in order.  A searched row (``acquire.searched``) never re-anchors anything: of an id already known,
+        provisional or not, or on a channel outside the hop pattern, it is ignored; of an unknown id it seeds a
+        provisional station."""
         recs = np.asarray(getattr(rows, "records", rows))
         if recs.size and not self.use_repaired:
             recs = recs[~acquire.repaired(recs)]
         for r in recs:
             hz = acquire.burst_message_offset_hz(r, self.out_rate, self.if_hz, self.deviation_hz, self.packet_symbols)
-            self.observe_at(int(r["channel"]), int(r["id"]), int(r["time"]), hz)
+            if int(r["flags"]) & acquire.MSG_SEARCHED:
+                self._observe_searched(int(r["channel"]), int(r["id"]), int(r["time"]), hz)
+            else:
+                self.observe_at(int(r["channel"]), int(r["id"]), int(r["time"]), hz)
+
+    def _observe_searched(self, channel: int, ident: int, time: int, offset_hz: float) -> None:
+        if ident in self._stations or ident in self._provisional or channel not in self.hop_pattern:
+            self._search_stats["ignored"] += 1
+            return
+        self._provisional[ident] = _Station(self.hop_pattern.index(channel), time, float(offset_hz))
+        self._search_stats["seeded"] += 1
 
     def retuned(self, delta_hz: float) -> None:
         """Every channel's centre has moved by ``delta_hz`` (a ``retune`` to ``old + delta_hz``): the stored carriers,
         which are relative to the centres, move the other way."""
-        for st in self._stations.values():
+        for st in list(self._stations.values()) + list(self._provisional.values()):
             st.offset_hz -= float(delta_hz)
 
     # ------------------------------------------------------------------------------------ what to expect
@@ -145,29 +175,37 @@ class Tracker:
         chunk before ``clock`` having been observed.  Per station: the next channel by the hop pattern, ``t_lo .. t_hi``
         around ``last + (missed + 1) * period``, the stored carrier as ``corr``.  An expectation all of whose packets
         would have ended before ``clock`` with nothing observed counts one miss and moves one hop on; after
-        ``max_missed`` in a row the station is dropped."""
+        ``max_missed`` in a row the station is dropped.  A provisional station gets its rows in the same way, counts its
+        misses apart from ``stats()`` and is dropped after ``provisional_missed`` of them."""
         clock, horizon = int(clock), int(horizon_outputs)
         body = self.symbol_length * (self.packet_symbols - 1)
         rows = []
-        for ident in sorted(self._stations):
-            st = self._stations[ident]
+        for ident in sorted(set(self._stations) | set(self._provisional)):   # (an id is in one of the two)
+            prov = ident in self._provisional
+            st = self._provisional[ident] if prov else self._stations[ident]
+            limit = self.provisional_missed if prov else self.max_missed
             while True:
                 _, t_hi = self._window(ident, st, st.missed)
                 if t_hi + body >= clock:
                     break
                 st.missed += 1
-                self._stats[ident]["missed"] += 1
-                if st.missed >= self.max_missed:
+                if not prov:
+                    self._stats[ident]["missed"] += 1
+                if st.missed >= limit:
                     break
-            if st.missed >= self.max_missed:
-                del self._stations[ident]
-                self._stats[ident]["lost"] += 1
+            if st.missed >= limit:
+                if prov:
+                    del self._provisional[ident]
+                    self._search_stats["expired"] += 1
+                else:
+                    del self._stations[ident]
+                    self._stats[ident]["lost"] += 1
                 continue
             cre, cim = self.corr(st.offset_hz)
             m = st.missed
             while True:                                   # every window that begins inside the horizon
                 t_lo, t_hi = self._window(ident, st, m)
-                if t_lo - self.symbol_length >= clock + horizon or m - st.missed >= self.max_missed:
+                if t_lo - self.symbol_length >= clock + horizon or m - st.missed >= limit:
                     break
                 ch = self.hop_pattern[(st.hop + m + 1) % len(self.hop_pattern)]
                 rows.append((ch, ident, t_lo, t_hi, cre, cim))
@@ -183,3 +221,13 @@ class Tracker:
         """{id: {"received": messages counted, "missed": expectations that passed with nothing observed, "lost": times
         the station was dropped after ``max_missed`` misses in a row}}."""
         return {i: dict(v) for i, v in sorted(self._stats.items())}
+
+    def provisional(self):
+        """The ids of the provisional stations (seeded by a searched row, not yet confirmed), ascending."""
+        return sorted(self._provisional)
+
+    def search_stats(self):
+        """{"seeded": searched rows that made a provisional station, "promoted": provisional stations confirmed by a row of
+        another path, "expired": provisional stations dropped after ``provisional_missed`` misses, "ignored": searched rows
+        of an id already known or of a channel outside the hop pattern}."""
+        return dict(self._search_stats)

@@ -83,6 +83,12 @@ BURST_EXPECT_ANY_ID = 0xFF
 # set_burst_expect(): one row per expectation - the layout of rd_expect
 EXPECT_DTYPE = np.dtype([("channel", np.int32), ("id", np.uint32), ("t_lo", np.uint64), ("t_hi", np.uint64),
                          ("corr_re", np.int32), ("corr_im", np.int32)])
+BURST_MSG_SEARCHED = 16                # ``flags`` bit 4: found by the blind search, ``first`` is the centre's index in the list
+BURST_SEARCH_MAX_CENTRES = 8           # centres per list
+BURST_SEARCH_PER = 4                   # rows per (centre, channel) and chunk
+BURST_SEARCH_TILE = 1024               # candidates per tile of the search kernel
+# searched_messages(): the layout of rd_bs_header, one per (centre, channel)
+SEARCH_HDR_DTYPE = np.dtype([("n_msgs", np.uint32), ("sync_hits", np.uint32), ("chunk", np.uint32), ("dropped", np.uint32)])
 
 
 # burst_message_quality() / expected_message_quality(): one row per message row - the layout of rd_burst_quality
@@ -110,6 +116,18 @@ class ExpectedMessages(NamedTuple):
     positions it had in the chunk, 0 when it was idle there) and ``chunk``."""
     records: np.ndarray
     candidates: np.ndarray
+    chunk: int
+
+
+class SearchedMessages(NamedTuple):
+    """``WidebandReceiver.searched_messages()``: ``records`` (``BURST_MSG_DTYPE``, centres in list order, channels
+    ascending, at most ``BURST_SEARCH_PER`` rows per centre and channel by ``tau``; ``flags`` has ``BURST_MSG_SEARCHED`` and
+    ``BURST_MSG_NARROW`` set, ``first`` is the centre's index in the list the chunk was submitted with, ``pad`` is
+    ``(hits, 0, 0, g)``), ``sync_hits`` and ``dropped`` (uint32 [centres, channels]: the positions whose first 16 symbols
+    equalled the sync word, and the reported positions beyond the fourth) and ``chunk``."""
+    records: np.ndarray
+    sync_hits: np.ndarray
+    dropped: np.ndarray
     chunk: int
 
 
@@ -521,6 +539,50 @@ class WidebandReceiver:
         chunk = C.c_uint64(0)
         _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
         return ExpectedMessages(recs[: n.value].copy(), cand[cand != 0xFFFFFFFF].copy(), int(chunk.value))
+
+    def set_burst_search(self, centres) -> None:
+        """From the next submitted chunk on, also search EVERY output position of every channel for the sync word and a
+        valid CRC behind the narrow-band filter, once per centre of ``centres`` (at most ``BURST_SEARCH_MAX_CENTRES``
+        distinct grid points 0 .. 63, g / 64 cycles per output; ``acquire.search_centres`` makes the list; an empty list,
+        the default, switches the search off and nothing is launched).  No energy threshold and no earlier message is
+        needed: this is how a station never yet heard is found when it is too weak for ``burst_messages()``.  It costs one
+        filter pass over every channel per centre and chunk.  Legal with chunks in flight.  ValueError for a centre above
+        63, a duplicate, more than eight, or ``symbol_length < 4`` (nothing changes); RuntimeError unless
+        ``set_burst_decode(True)``; switching decode or bursts off clears the list, ``reset()`` keeps it."""
+        t = np.asarray(centres).reshape(-1)
+        if t.size and (np.any(t < 0) or np.any(t > 255) or np.any(t != np.floor(t))):
+            raise ValueError("burst search: centres are grid points 0 .. 63")
+        t = np.ascontiguousarray(t.astype(np.uint8))
+        _lib.check(_lib.lib().rd_wb_set_burst_search(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def burst_search(self) -> np.ndarray:
+        """The centres the next submitted chunk will use (uint8)."""
+        t = np.empty(BURST_SEARCH_MAX_CENTRES, np.uint8)
+        n = C.c_int(0)
+        _lib.check(_lib.lib().rd_wb_burst_search(self._h, t.ctypes.data, t.size, C.byref(n)))
+        return t[: n.value].copy()
+
+    def searched_messages(self) -> "SearchedMessages":
+        """The messages the blind search found in the chunk the last ``fetch()`` returned - rows like those of
+        ``burst_messages()`` with ``flags`` bit 4 (``BURST_MSG_SEARCHED``) and bit 2 set, ``first`` the centre's index in
+        the list that chunk was submitted with, ``pad[0]`` the number of adjacent positions that passed (about
+        ``symbol_length - 2`` for a real packet, 1 for a chance hit) and ``pad[3]`` the centre.  A searched row proves less
+        than any other: with every position tested, sync word and CRC pass by chance every few minutes per centre -
+        ``track.Tracker`` holds a station seeded by one as provisional until an expectation confirms it.  A packet found
+        from both sides of a chunk boundary is dropped from the later chunk; two centres that both decode a packet each
+        give their row: dedupe by channel, time and data.  A chunk submitted with an empty list gives no rows.
+        RuntimeError before any fetch and when decode was off for that chunk."""
+        L = _lib.lib()
+        n_ch = self.n_channels
+        hdr = np.empty(BURST_SEARCH_MAX_CENTRES * n_ch, SEARCH_HDR_DTYPE)
+        recs = np.empty(BURST_SEARCH_MAX_CENTRES * n_ch * BURST_SEARCH_PER, BURST_MSG_DTYPE)
+        n = C.c_int(0)
+        _lib.check(L.rd_wb_searched_messages(self._h, recs.ctypes.data, recs.size, C.byref(n), hdr.ctypes.data, hdr.size))
+        chunk = C.c_uint64(0)
+        _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
+        hdr = hdr.reshape(BURST_SEARCH_MAX_CENTRES, n_ch)
+        hdr = hdr[hdr["n_msgs"][:, 0] != 0xFFFFFFFF]
+        return SearchedMessages(recs[: n.value].copy(), hdr["sync_hits"].copy(), hdr["dropped"].copy(), int(chunk.value))
 
     def set_burst_quality(self, on: bool = True, noise_gap: int = 0) -> None:
         """From the next chunk on, every row of ``burst_messages()`` and ``expected_messages()`` gets a row of

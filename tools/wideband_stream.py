@@ -51,6 +51,12 @@ of 8 expectations set before every submit (WidebandReceiver.set_burst_expect: k_
 k_chan_burst_decode, 8 workgroups, 201 candidates each, all inside the chunk) and expected_messages() read after every
 fetch.  Both go into --track-out (default profiles/wideband_burst_track.txt), with the spread of the windows beside the
 difference.  The kernel's own time is not measured here.
+--burst-search N (1 .. 8): as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts +
+decode on with the blind search at N centres (WidebandReceiver.set_burst_search: k_chan_burst_search behind
+k_chan_burst_decode, one workgroup per channel and centre, every output position tested) and searched_messages() read
+after every fetch.  The centres are the grid point of the channels' centre and its neighbours; the capture's bursts lie
+there.  Both go into --burst-search-out (default profiles/wideband_burst_search.txt), with the rate against that of the
+air.  The kernel's own time is not measured here.
 """
 import argparse
 import json
@@ -100,6 +106,10 @@ def main():
                     help="time every window with bursts + decode on, and with 8 expectations active in every chunk on top; write --track-out")
     ap.add_argument("--track-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                         "wideband_burst_track.txt"))
+    ap.add_argument("--burst-search", type=int, default=0, choices=range(0, 9), metavar="N",
+                    help="time every window with bursts + decode on, and with the blind search at N centres on top; write --burst-search-out")
+    ap.add_argument("--burst-search-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                               "wideband_burst_search.txt"))
     ap.add_argument("--json", default=None, help="also write the result as JSON here")
     args = ap.parse_args()
     if args.chunks < 1 or args.repeats < 1 or args.capture_chunks < 3:
@@ -118,7 +128,10 @@ def main():
     quality = args.burst_quality
     if quality and (args.bursts or args.burst_decode or repair or narrow or track):
         raise SystemExit("--burst-quality alone: each run compares two windows")
-    decode = args.burst_decode or repair > 0 or narrow or track or quality
+    search = args.burst_search
+    if search and (args.bursts or args.burst_decode or repair or narrow or track or quality):
+        raise SystemExit("--burst-search alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0 or narrow or track or quality or search > 0
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
@@ -155,6 +168,9 @@ def main():
     n_narrow = [0]
     track_on, n_xmsgs, n_xcand = [False], [0], [0]
     quality_on, n_qrows, q_snr = [False], [0], []
+    # the capture's bursts lie on their channels' centres: the nearest grid point first, then its neighbours
+    search_on, n_smsgs, n_shits = [False], [0], [0]
+    centres = [(48 + d) % 64 for d in (0, -1, 1, -2, 2, -3, 3, -4)][:search]
 
     def track_table(clock):
         """8 expectations, every one with 201 candidates inside the chunk that begins at `clock`, spread over the channels."""
@@ -183,6 +199,10 @@ def main():
                     n_qrows[0] += len(q)
                     if len(q):
                         q_snr[:] = [q]                       # (turned into decibels after the window, outside the timing)
+                if search_on[0]:
+                    sm = rx.searched_messages()
+                    n_smsgs[0] += len(sm.records)
+                    n_shits[0] += int(sm.sync_hits.astype(np.int64).sum())
                 if track_on[0]:
                     x = rx.expected_messages()
                     n_xmsgs[0] += len(x.records)
@@ -226,7 +246,11 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track or quality)
+                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track or quality or search > 0)
+                if search:
+                    rx.set_burst_search(centres if on else [])
+                search_on[0] = on and search > 0
+                n_smsgs[0] = n_shits[0] = 0
                 if repair:
                     rx.set_burst_repair(repair if on else 0)
                 if narrow:
@@ -236,7 +260,7 @@ def main():
                 quality_on[0] = on and quality
                 n_qrows[0] = 0
                 del q_snr[:]
-                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track or quality
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track or quality or search > 0
                 track_on[0] = on and track
                 n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = n_xmsgs[0] = n_xcand[0] = 0
                 acq.reset()
@@ -384,7 +408,29 @@ def main():
                 f"{n_asked[0]} retunes proposed; last window without: {base_msgs[0]} burst messages",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
-        with open(args.burst_quality_out if quality else args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        if search:
+            res["burst_search"] = {"centres": centres, "searched_messages_last_window": n_smsgs[0], "sync_hits_last_window": n_shits[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            air_rate = out_rate / B
+            lines = [
+                f"WidebandReceiver burst search (k_chan_burst_search, {search} centre{'s' if search > 1 else ''} {centres}), bursts + decode + search on "
+                f"against bursts + decode on in the same run: tools/wideband_stream.py --burst-search {search}" + (" --parse" if args.parse else ""),
+                lines[1] + "; a burst on every channel, on its centre",
+                f"  bursts + decode on:           {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + search on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(searched_messages() read per fetch)",
+                f"  the air delivers {air_rate:.1f} chunks/s: search on runs at {res['chunks_per_s'] / air_rate:.1f} x real time",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + search {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: search {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with search: {n_smsgs[0]} searched messages, {n_shits[0]} sync hits over {search * rx.n_channels} (centre, channel) pairs, "
+                f"{n_dmsgs[0]} burst messages; last window without: {base_msgs[0]} burst messages",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
+        with open(args.burst_search_out if search else args.burst_quality_out if quality else args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
