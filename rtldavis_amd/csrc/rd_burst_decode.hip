@@ -21,66 +21,37 @@
 //   one record per run at most: the candidate with the largest margin = min_i |s[tau + SL i]|, ties to the smallest tau.
 //
 // Kernel.  One workgroup of 256 threads per channel, the channel's runs one after the other (the loop is bounded by the
-// record places, every inner loop by the region).  Per run: the region's bytes go to LDS as they lie (16-byte vectors;
-// t0 and the chunk boundary are multiples of 128); s is linear in p, so with SI, SR the sums of im p, re p over the SL
-// samples (< 2^24: int32; a lane takes a stretch of consecutive outputs and slides both sums along it, one p in and one
-// out per output) s[t] = corr_re SI[t] - corr_im SR[t] - two 32 x 32 -> 64-bit multiplies per sample, exact -
-// goes to LDS as int64 (48 KiB for the longest region, 32 + 16 windows; the bytes 12 KiB); then one lane per tau: the
-// sync word first - all but a few lanes leave there -, the rest of the symbols with byte packing, CRC and margin.  The
-// candidates are reduced by a max over (margin, -tau): a total order, so the fixed tree of shuffles and the four waves'
-// results in LDS give the same record whatever the order - no atomics.  The winner's record is completed by the whole
-// workgroup (sum of p over the packet's N SL samples) and written by thread 0.
+// record places, every inner loop by the region); thread 0 fetches a run's record with system-scope loads from the burst
+// slot where k_chan_bursts, earlier on the same stream, wrote it.  Per run the phases of rd_burst_common.h in order: the
+// region's bytes (t0 and the chunk boundary are multiples of 128), the sliding sums into s (int64, 48 KiB for the longest
+// region, 32 + 16 windows; the bytes 12 KiB), one lane per tau - all but a few leave at the sync word -, the reduction,
+// and the winner's record, completed by the whole workgroup and written by thread 0.
 // Output: channel c owns cap = rd_bu_cap(nW) record places, as in the burst slot, and one header (n_msgs, long_runs,
 // chunk): a run gives at most one record, so there is no overflow and no ticket; the channel's records are its first
-// n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  The
-// burst records and the floor row are read from the burst slot where k_chan_bursts, earlier on the same stream, wrote
-// them (system-scope loads).  With the default thresholds there are no runs: the header is written and that is all.
+// n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  With
+// the default thresholds there are no runs: the header is written and that is all.
 //
-// Repair (steps 5a, 5b, 6' of the header; rd_wb_set_burst_repair).  The kernel is a template on it: k_chan_burst_decode<false>
-// is the code above and is what max_flips = 0 launches; k_chan_burst_decode<true> adds, behind the sync test and the CRC
-// of a tau - where all but a few lanes have left -, for a candidate with syndrome S != 0: the L = 8 smallest (|s|, k) of
-// the payload symbols, kept sorted in registers by an unrolled insertion (64-bit magnitudes, ties to the smaller k); the
-// singles, then the pairs in (a, b) order against S through E[k], the CRC of the packet whose only set symbol is k - the
-// CRC has init 0 and is linear -, which the workgroup builds once into LDS (N x 16 bits); and the margin again without
-// the flipped symbols.  The reduction carries (flips, k1, k2) in one word beside (margin, tau) and orders by
-// (flips ascending, margin descending, tau ascending): still a total order, the same tree, the same four slots.  Thread 0
-// writes the corrected symbols.
-//
-// Narrow-band filter (step 4n of the header; rd_wb_set_burst_narrow).  The second template argument: the two <*, false>
-// forms are the code above, the two <*, true> forms put, between the region's bytes and the sliding sums: the grid choice
-// - every wave scores the 64 centres, lane g its own, against (ca, cb) and reduces over (score, -g) by the fixed tree of
-// shuffles: a max over a total order, the same g in all four waves, no LDS, no atomics -; the T = 2 SL + 5 taps of H[g]
-// from the device table into LDS, as the two int16 pairs (re, -im) and (im, re) a complex product wants; the region as
-// int16 pairs (zi, zq) with SL + 2 zeros on both sides (the zero extension: no bounds test per tap) in the place of s,
-// which is not yet live; then y: a lane takes outputs tid + 256 j, four at a time in registers, per tap two LDS
-// broadcasts of the tap and, per output, one LDS word and two packed 16-bit dot products (v_dot2_i32_i16) - 4 T integer
-// multiply-adds per output, |acc| < 2^23 -; y = (acc + 2^10) >> 11 goes to LDS as a packed int16 pair, 24 KiB of its own
-// for the longest region, because p' reads y while s is written and the record's f sum reads it again.  That takes the
-// <*, true> forms to 85 KiB of static LDS (87024 and 87200 bytes) - one workgroup per CU where the others fit two; the grid is one workgroup per
-// channel, far fewer than the chip has CUs, so nothing waits for the second.  The sliding sums, the candidates and the
-// reduction then run as they are on p' = y conj(y[-1]) (components < 2^25, SL-sums < 2^31: int32) with (ca, cb) for the
-// correlation sum, |s| < 2^47; the record's f sum is widened to 64 bits before the lanes are added (< 2^36).
-#include <cstring>
+// The kernel is a template on the repair (steps 5a, 5b, 6'; rd_wb_set_burst_repair: max_flips > 0 launches <true, *>, whose
+// candidate test goes on behind a failed CRC - rd_burst_candidate.h - and whose reduction carries the flips) and on the
+// narrow-band filter (step 4n; rd_wb_set_burst_narrow: a table launches <*, true>).  The <*, true> forms put, between the
+// bytes and the sliding sums: the grid choice from (ca, cb), the taps, the region as int16 pairs with SL + 2 zeros on
+// both sides in the place of s, which is not yet live, and y, 24 KiB of its own for the longest region, because p' reads
+// y while s is written and the record's f sum reads it again.  That takes them to 85 KiB of static LDS (87024 and 87200
+// bytes) - one workgroup per CU where the others fit two; the grid is one workgroup per channel, far fewer than the chip
+// has CUs, so nothing waits for the second.  The rest then runs on p' = y conj(y[-1]) with (ca, cb) for the correlation
+// sum, |s| < 2^47.
 #include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime.h>
 
 #include "rd_burst_common.h"
-#include "rd_internal.h"
-#include "rd_parse.h"
 
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
-#define RD_BD_THREADS 256
 #define RD_BD_MAX_REGION ((RD_BD_MAX_W + RD_BD_MAX_LOOK_W) * RD_BU_WINDOW)   // outputs of the longest region
 
 static_assert(sizeof(rd_burst_msg) == 64 && sizeof(rd_bd_header) == 16, "the slot layout of rd_bd_* (rd_internal.h)");
 static_assert(RD_BD_MAX_REGION * 10 + 2 * 8 * RD_BD_DATA_BYTES + 256 <= 64 * 1024,
               "s (int64) and the bytes of the longest region, 60 KiB; the E table of the repair; 256 bytes of per-wave slots: under 64 KiB of LDS");
-static_assert(RD_BD_REPAIR_L == 8, "the pair loop and the record's pad[] are written for a list of 8");
-#define RD_BD_NB_MAX_T (2 * RD_BD_NB_MAX_SL + 5)
-static_assert(RD_BD_NB_GRID == 64, "one lane of a wave per centre");
 static_assert((RD_BD_MAX_REGION + RD_BD_NB_MAX_T - 1) * 4 <= RD_BD_MAX_REGION * 8, "the padded int16 region lies in s's place");
 static_assert(RD_BD_MAX_REGION * 14 + 2 * 8 * RD_BD_DATA_BYTES + 2 * 4 * RD_BD_NB_MAX_T + 512 <= 160 * 1024,
               "narrow: y (4 bytes per output) and the taps beside the rest, under gfx950's 160 KiB of LDS");
@@ -91,28 +62,28 @@ struct rd_bd_params {
     int look;                  // LOOK
     int have_prev;
     unsigned n_win, cap;
-    int max_flips;             // R (k_chan_burst_decode<true> alone reads it)
+    int max_flips;             // R (k_chan_burst_decode<true, *> alone reads it)
     uint64_t clock, seq;
 };
 
 template <bool REPAIR, bool NARROW>
-__global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
-                                                                     size_t ch_stride, size_t n_out, rd_bd_params P,
-                                                                     const rd_burst *runs, const rd_burst_floor *floor,
-                                                                     rd_burst_msg *recs, rd_bd_header *hdr,
-                                                                     const uint32_t *__restrict__ nb_tab) {
+__global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_decode(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
+                                                                        size_t ch_stride, size_t n_out, rd_bd_params P,
+                                                                        const rd_burst *runs, const rd_burst_floor *floor,
+                                                                        rd_burst_msg *recs, rd_bd_header *hdr,
+                                                                        const uint32_t *__restrict__ nb_tab) {
+    using f_t = std::conditional_t<NARROW, int64_t, int>;
     __shared__ int64_t s_s[RD_BD_MAX_REGION];            // s[t0 + i] at i (i >= SL)
     __shared__ uint4 s_z[RD_BD_MAX_REGION / 8];          // the region's bytes: output t0 + i at bytes 2 i, 2 i + 1
-    __shared__ uint64_t s_m[RD_BD_THREADS / 64];
-    __shared__ int s_t[RD_BD_THREADS / 64];
-    __shared__ int s_fr[RD_BD_THREADS / 64], s_fi[RD_BD_THREADS / 64];
+    __shared__ uint64_t s_m[RD_BURST_THREADS / 64];
+    __shared__ int s_t[RD_BURST_THREADS / 64];
+    __shared__ f_t s_fr[RD_BURST_THREADS / 64], s_fi[RD_BURST_THREADS / 64];
     __shared__ uint32_t s_run[4];                        // n_bursts; first, windows, flags of the run in hand
     __shared__ int64_t s_corr[2];
     __shared__ uint16_t s_E[8 * RD_BD_DATA_BYTES];       // (REPAIR) E[k], 16 <= k < N
-    __shared__ uint32_t s_f[RD_BD_THREADS / 64];         // (REPAIR) the waves' flips
+    __shared__ uint32_t s_f[RD_BURST_THREADS / 64];      // (REPAIR) the waves' flips
     __shared__ uint32_t s_y[RD_BD_MAX_REGION];           // (NARROW) y[t0 + i] at i: re in the low half, im in the high one
     __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // (NARROW) H[g][kk - M] as (re, -im) and (im, re)
-    __shared__ int64_t s_fr64[RD_BD_THREADS / 64], s_fi64[RD_BD_THREADS / 64];   // (NARROW) in the place of s_fr, s_fi
     const int c = (int)blockIdx.x;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint8_t *src = cur + (size_t)c * ch_stride;
@@ -121,14 +92,7 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
     rd_burst_msg *out = recs + (size_t)c * P.cap;
     const uint16_t *zw = (const uint16_t *)s_z;           // output t0 + i: I in the low byte, Q in the high one
     if (tid == 0u) s_run[0] = rd_bd_sys_load(&floor[c].n_bursts);
-    if constexpr (REPAIR) {
-        // E[k]: symbol k is bit 7 - (k & 7) of on-air byte k >> 3, bit k & 7 of the bit-swapped byte
-        if ((int)tid >= 16 && (int)tid < P.n_sym) {
-            uint32_t crc = 0u;
-            for (int b = 2; b < P.n_sym >> 3; b++) crc = rd_crc16_step(crc, b == (int)(tid >> 3) ? 1u << (tid & 7u) : 0u);
-            s_E[tid] = (uint16_t)crc;
-        }
-    }
+    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.n_sym, tid);
     __syncthreads();
     uint32_t n_runs = s_run[0];
     if (n_runs > P.cap) n_runs = P.cap;                   // (k_chan_bursts never writes more)
@@ -165,297 +129,38 @@ __global__ __launch_bounds__(RD_BD_THREADS) void k_chan_burst_decode(const uint8
         }
         // |corr| <= 32 x 254 x 65025 < 2^30; NARROW: (ca, cb), in -2^15 .. 2^15 - 1
         const int32_t cr = NARROW ? (int32_t)(cr64 >> nb_sh) : (int32_t)cr64, ci = NARROW ? (int32_t)(ci64 >> nb_sh) : (int32_t)ci64;
-        // ---- the region's bytes
-        for (int v = (int)tid; v < len / 8; v += RD_BD_THREADS) {
-            const int t = t0 + 8 * v;                     // (t0 and 0 are multiples of 8: a vector lies in one chunk)
-            const uint8_t *g = t < 0 ? src_prev + 2 * ((long)t + (long)n_out) : src + 2 * (long)t;
-            s_z[v] = *(const uint4 *)g;
-        }
+        rd_bd_load_bytes(s_z, src, src_prev, t0, t1, (long)n_out, tid);
         __syncthreads();
         if constexpr (NARROW) {
             const int T = 2 * SL + 5, M = SL + 2;
-            // ---- g: the smallest centre with the largest ca C.re + cb C.im (|score| < 2^30), the same in every wave
-            {
-                const uint32_t cw = nb_tab[RD_BD_NB_GRID * T + (int)lane];
-                int sc = cr * (int)(int16_t)(cw & 0xFFFFu) + ci * ((int)cw >> 16);
-                nb_g = (int)lane;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const int os = __shfl_xor(sc, off), og = __shfl_xor(nb_g, off);
-                    if (os > sc || (os == sc && og < nb_g)) {
-                        sc = os;
-                        nb_g = og;
-                    }
-                }
-            }
-            if ((int)tid < T) {
-                const uint32_t hw = nb_tab[nb_g * T + (int)tid];
-                const int hr = (int)(int16_t)(hw & 0xFFFFu), hi = (int)hw >> 16;
-                s_hA[tid] = rd_bd_pack16(hr, -hi);
-                s_hB[tid] = rd_bd_pack16(hi, hr);
-            }
-            // ---- z as int16 pairs, output t0 + i at word i + M, zeros in front of the region and behind it
-            uint32_t *z16 = (uint32_t *)s_s;
-            for (int i = (int)tid; i < len + 2 * M; i += RD_BD_THREADS) {
-                const int j = i - M;
-                uint32_t zv = 0u;
-                if (j >= 0 && j < len) {
-                    const uint32_t a = zw[j];
-                    zv = rd_bd_pack16(2 * (int)(a & 0xFFu) - 255, 2 * (int)(a >> 8) - 255);
-                }
-                z16[i] = zv;
-            }
+            uint32_t *z16 = (uint32_t *)s_s;              // output t0 - M + i at word i: zeros in front of the region and behind it
+            nb_g = rd_bd_grid_choice(nb_tab, T, cr, ci, lane);
+            rd_bd_load_taps(nb_tab, nb_g, T, s_hA, s_hB, tid);
+            rd_bd_fill_z16(z16, zw, t0, t0 - M, len + 2 * M, t0, t1, tid);
             __syncthreads();
-            // ---- y[t0 + i] = (sum_kk H[g][kk - M] z[t0 + i - (kk - M)] + 2^10) >> 11: z[..] lies at word i + T - 1 - kk
-            for (int base = (int)tid; base < len; base += 4 * RD_BD_THREADS) {
-                int at[4], ar[4], ai[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int i = base + q * RD_BD_THREADS;
-                    at[q] = (i < len ? i : base) + T - 1;    // (an output past the region repeats the lane's first and is not stored)
-                    ar[q] = 0;
-                    ai[q] = 0;
-                }
-                for (int kk = 0; kk < T; kk++) {
-                    const uint32_t hA = s_hA[kk], hB = s_hB[kk];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const uint32_t zv = z16[at[q] - kk];
-                        ar[q] = rd_bd_dot2(hA, zv, ar[q]);
-                        ai[q] = rd_bd_dot2(hB, zv, ai[q]);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int i = base + q * RD_BD_THREADS;
-                    if (i < len)
-                        s_y[i] = rd_bd_pack16((ar[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT,
-                                              (ai[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT);
-                }
-            }
+            rd_bd_filter(z16, len, T, s_hA, s_hB, s_y, tid);
             __syncthreads();                              // y is whole, and z16 has been read: s may be written
         }
-        // ---- s[t0 + i], SL <= i < len: a lane takes a stretch of outputs and slides the two window sums along it
-        const int per = (len - SL + RD_BD_THREADS - 1) / RD_BD_THREADS;
-        const int ia = SL + (int)tid * per, ib = min(ia + per, len);
-        if (ia < ib) {
-            int sr = 0, si = 0, re, im;
-            for (int j = ia - SL + 1; j <= ia; j++) {
-                rd_bd_pp<NARROW>(zw, s_y, j, re, im);
-                sr += re;
-                si += im;
-            }
-            s_s[ia] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
-            for (int i = ia + 1; i < ib; i++) {
-                rd_bd_pp<NARROW>(zw, s_y, i, re, im);
-                sr += re;
-                si += im;
-                rd_bd_pp<NARROW>(zw, s_y, i - SL, re, im);          // (i - SL >= 1: its pair lies in the region)
-                sr -= re;
-                si -= im;
-                s_s[i] = (int64_t)cr * (int64_t)si - (int64_t)ci * (int64_t)sr;
-            }
-        }
+        rd_bd_symbol_sums<NARROW>(zw, s_y, s_s, SL, len, cr, ci, tid);
         __syncthreads();
         // ---- one lane per tau = t0 + i
         uint64_t best_m = 0ull;
         int best_t = INT32_MAX;
         uint32_t best_f = 0u;
         const int i_hi = len - SL * (N - 1);              // i + SL (N - 1) < len
-        for (int i = SL + (int)tid; i < i_hi; i += RD_BD_THREADS) {
+        for (int i = SL + (int)tid; i < i_hi; i += RD_BURST_THREADS) {
             const int tau = t0 + i;
             if (tau + SL * (N - 1) < 0) continue;         // the packet ended in the chunk before: reported there
-            uint64_t margin = ~0ull;
-            uint32_t word = 0u, crc = 0u;
-            bool ok = true;
-            for (int k = 0; k < N; k++) {
-                const int64_t v = s_s[i + SL * k];
-                const uint32_t bit = v > 0 ? 1u : 0u;
-                if (k < 16 && bit != ((P.sync >> (15 - k)) & 1u)) {
-                    ok = false;
-                    break;
-                }
-                const uint64_t mag = (uint64_t)(v > 0 ? v : -v);
-                margin = mag < margin ? mag : margin;
-                word = ((word << 1) | bit) & 0xFFu;
-                if ((k & 7) == 7 && k >= 16) crc = rd_crc16_step(crc, rd_swap_bits8(word));
-            }
-            if constexpr (!REPAIR) {
-                if (ok && crc == 0u && rd_bd_better(margin, tau, best_m, best_t)) {
-                    best_m = margin;
-                    best_t = tau;
-                }
-            } else {
-                if (!ok) continue;
-                uint32_t fl = 0u;
-                if (crc != 0u) {                          // steps 5a, 5b: the syndrome S = crc
-                    uint64_t lm[RD_BD_REPAIR_L];          // the list, ascending in (|s|, k)
-                    int lk[RD_BD_REPAIR_L];
-#pragma unroll
-                    for (int a = 0; a < RD_BD_REPAIR_L; a++) {
-                        lm[a] = ~0ull;
-                        lk[a] = INT32_MAX;
-                    }
-                    for (int k = 16; k < N; k++) {
-                        const int64_t v = s_s[i + SL * k];
-                        uint64_t cm = (uint64_t)(v > 0 ? v : -v);
-                        int ck = k;
-#pragma unroll
-                        for (int a = 0; a < RD_BD_REPAIR_L; a++)
-                            if (cm < lm[a] || (cm == lm[a] && ck < lk[a])) {   // the entry moves in, the one it displaces goes on
-                                const uint64_t tm = lm[a];
-                                const int tk = lk[a];
-                                lm[a] = cm;
-                                lk[a] = ck;
-                                cm = tm;
-                                ck = tk;
-                            }
-                    }
-                    uint32_t e[RD_BD_REPAIR_L];
-#pragma unroll
-                    for (int a = 0; a < RD_BD_REPAIR_L; a++) e[a] = s_E[lk[a]];   // (N >= 40: 24 payload symbols, the list is full)
-#pragma unroll
-                    for (int a = 0; a < RD_BD_REPAIR_L; a++)
-                        if (fl == 0u && e[a] == crc) fl = 1u | ((uint32_t)lk[a] << 8);
-                    if (P.max_flips >= 2) {
-#pragma unroll
-                        for (int a = 0; a < RD_BD_REPAIR_L; a++)
-#pragma unroll
-                            for (int b = a + 1; b < RD_BD_REPAIR_L; b++)
-                                if (fl == 0u && (e[a] ^ e[b]) == crc) {
-                                    const uint32_t ka = (uint32_t)lk[a], kb = (uint32_t)lk[b];
-                                    fl = 2u | ((ka < kb ? ka : kb) << 8) | ((ka < kb ? kb : ka) << 16);
-                                }
-                    }
-                    if (fl == 0u) continue;
-                    const int k1 = (int)((fl >> 8) & 0xFFu), k2 = (fl & 0xFFu) == 2u ? (int)(fl >> 16) : -1;
-                    margin = ~0ull;                       // step 6': over the symbols that were not flipped
-                    for (int k = 0; k < N; k++) {
-                        if (k == k1 || k == k2) continue;
-                        const int64_t v = s_s[i + SL * k];
-                        const uint64_t mag = (uint64_t)(v > 0 ? v : -v);
-                        margin = mag < margin ? mag : margin;
-                    }
-                }
-                if (rd_bd_better_r(fl, margin, tau, best_f, best_m, best_t)) {
-                    best_f = fl;
-                    best_m = margin;
-                    best_t = tau;
-                }
-            }
+            rd_bd_consider<REPAIR>(s_s + i, SL, N, P.sync, P.max_flips, s_E, 8u, tau, best_f, best_m, best_t);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t om = (uint64_t)__shfl_xor((unsigned long long)best_m, off);
-            const int ot = __shfl_xor(best_t, off);
-            if constexpr (!REPAIR) {
-                if (rd_bd_better(om, ot, best_m, best_t)) {
-                    best_m = om;
-                    best_t = ot;
-                }
-            } else {
-                const uint32_t of = (uint32_t)__shfl_xor((int)best_f, off);
-                if (rd_bd_better_r(of, om, ot, best_f, best_m, best_t)) {
-                    best_f = of;
-                    best_m = om;
-                    best_t = ot;
-                }
-            }
-        }
-        if (lane == 0u) {
-            s_m[wave] = best_m;
-            s_t[wave] = best_t;
-            if constexpr (REPAIR) s_f[wave] = best_f;
-        }
-        __syncthreads();
-        best_m = s_m[0];
-        best_t = s_t[0];
-        if constexpr (REPAIR) best_f = s_f[0];
-#pragma unroll
-        for (int wv = 1; wv < RD_BD_THREADS / 64; wv++) {
-            if constexpr (!REPAIR) {
-                if (rd_bd_better(s_m[wv], s_t[wv], best_m, best_t)) {
-                    best_m = s_m[wv];
-                    best_t = s_t[wv];
-                }
-            } else {
-                if (rd_bd_better_r(s_f[wv], s_m[wv], s_t[wv], best_f, best_m, best_t)) {
-                    best_f = s_f[wv];
-                    best_m = s_m[wv];
-                    best_t = s_t[wv];
-                }
-            }
-        }
+        rd_bd_reduce_best<REPAIR>(best_f, best_m, best_t, s_f, s_m, s_t, lane, wave);
         if (best_t == INT32_MAX) continue;                // (uniform: every thread read the same four)
         // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
         const int i0 = best_t - t0;
-        // |.| <= 2048 x 2 x 255^2 < 2^29; NARROW: a lane's 8 terms of p' < 2^28, the packet's 2047 < 2^36
-        std::conditional_t<NARROW, long long, int> fr = 0, fi = 0;
-        for (int j = i0 - SL + 1 + (int)tid; j <= i0 + SL * (N - 1); j += RD_BD_THREADS) {
-            int re, im;
-            rd_bd_pp<NARROW>(zw, s_y, j, re, im);
-            fr += re;
-            fi += im;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            fr += __shfl_xor(fr, off);
-            fi += __shfl_xor(fi, off);
-        }
-        if (lane == 0u) {
-            if constexpr (NARROW) {
-                s_fr64[wave] = fr;
-                s_fi64[wave] = fi;
-            } else {
-                s_fr[wave] = fr;
-                s_fi[wave] = fi;
-            }
-        }
-        __syncthreads();
-        if (tid == 0u) {                                  // field by field into the slot: no private copy of the record
-            rd_burst_msg *m = &out[n_msgs];
-            m->channel = c;
-            m->first = first;
-            m->tau = best_t;
-            uint32_t n_flip = 0u;
-            int k1 = -1, k2 = -1;                         // the flipped symbols (REPAIR; none: -1)
-            if constexpr (REPAIR) {
-                n_flip = best_f & 0xFFu;
-                if (n_flip >= 1u) k1 = (int)((best_f >> 8) & 0xFFu);
-                if (n_flip == 2u) k2 = (int)((best_f >> 16) & 0xFFu);
-            }
-            m->flags = (back ? 1u : 0u) | (n_flip ? RD_BURST_MSG_REPAIRED : 0u) | (NARROW ? RD_BURST_MSG_NARROW : 0u);
-            m->time = P.clock + (uint64_t)(int64_t)best_t;
-            m->margin = best_m;
-            int64_t sfr = 0, sfi = 0;
-            for (int wv = 0; wv < RD_BD_THREADS / 64; wv++) {
-                if constexpr (NARROW) {
-                    sfr += s_fr64[wv];
-                    sfi += s_fi64[wv];
-                } else {
-                    sfr += s_fr[wv];
-                    sfi += s_fi[wv];
-                }
-            }
-            m->f_re = sfr;
-            m->f_im = sfi;
-            uint32_t word = 0u, ones = 0u, id = 0u;
-            for (int k = 0; k < N; k++) {
-                uint32_t bit = s_s[i0 + SL * k] > 0 ? 1u : 0u;
-                if constexpr (REPAIR) bit ^= (k == k1 || k == k2) ? 1u : 0u;
-                ones += bit;
-                word = ((word << 1) | bit) & 0xFFu;
-                if ((k & 7) == 7) m->data[k >> 3] = (uint8_t)word;
-                if (k == 23) id = rd_swap_bits8(word) & 7u;
-            }
-            for (int k = N >> 3; k < RD_BD_DATA_BYTES; k++) m->data[k] = 0;
-            m->ones = (uint8_t)ones;
-            m->id = (uint8_t)id;
-            m->pad[0] = (uint8_t)n_flip;
-            m->pad[1] = (uint8_t)(n_flip >= 1u ? k1 : 0);
-            m->pad[2] = (uint8_t)(n_flip == 2u ? k2 : 0);
-            m->pad[3] = (uint8_t)nb_g;                     // (0 without NARROW)
-        }
+        rd_bd_packet_f<NARROW>(zw, s_y, i0 - SL + 1, i0 + SL * (N - 1), s_fr, s_fi, tid);
+        if (tid == 0u)
+            rd_bd_write_record<REPAIR, NARROW>(&out[n_msgs], c, first, back ? 1u : 0u, best_t, P.clock, best_m, best_f, s_fr, s_fi,
+                                               s_s + i0, SL, N, nb_g);
         n_msgs++;
     }
     if (tid == 0u) {
@@ -512,22 +217,15 @@ int rd_bd_narrow_upload(int sl, uint32_t **d_tab) {
 int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                            size_t n_out, uint64_t clock, uint64_t seq, int max_flips, const uint32_t *narrow_tab,
                            const void *burst_slot, void *slot, hipStream_t st) {
-    if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
-        return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
-    if (!chan_out || !burst_slot || !slot || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    int rc = rd_burst_decode_check(cfg);
+    // (a missing burst slot is refused where a missing message slot is)
+    int rc = rd_burst_launch_check(cfg, chan_out, chan_prev, out_stride, n_ch, n_out, burst_slot ? slot : nullptr, max_flips, narrow_tab,
+                                   "burst decode");
     if (rc) return rc;
-    if (narrow_tab && cfg->symbol_length < RD_BD_NB_MIN_SL)   // (at most RD_BD_NB_MAX_SL by the check above)
-        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
-    if (n_out != (size_t)cfg->block_size || out_stride < 2 * n_out || (out_stride & 15) || ((uintptr_t)chan_out & 15) ||
-        ((uintptr_t)chan_prev & 15) || ((uintptr_t)slot & 15))
-        return rd_fail_msg(RD_ERR_ARG, "burst decode: stride %zu for %zu outputs, or a misaligned buffer", out_stride, n_out);
     const size_t n_win = n_out / RD_BU_WINDOW;
     rd_bd_params P;
     P.sl = cfg->symbol_length;
     P.n_sym = cfg->packet_symbols;
-    P.sync = 0u;
-    for (int i = 0; i < 16; i++) P.sync = (P.sync << 1) | (cfg->preamble[i] ? 1u : 0u);
+    P.sync = rd_bd_sync_word(cfg);
     P.look = RD_BU_WINDOW * rd_bd_look_windows(cfg);
     P.have_prev = chan_prev ? 1 : 0;
     P.n_win = (unsigned)n_win;
@@ -542,10 +240,10 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     rd_burst_msg *recs = (rd_burst_msg *)base;
     rd_bd_header *hdr = (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win));
 #define RD_BD_LAUNCH(REPAIR, NARROW)                                                                                          \
-    hipLaunchKernelGGL((k_chan_burst_decode<REPAIR, NARROW>), dim3((unsigned)n_ch), dim3(RD_BD_THREADS), 0, st, chan_out, chan_prev, \
+    hipLaunchKernelGGL((k_chan_burst_decode<REPAIR, NARROW>), dim3((unsigned)n_ch), dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, \
                        out_stride, n_out, P, runs, floor, recs, hdr, narrow_tab)
     if (!narrow_tab) {
-        if (max_flips == 0) RD_BD_LAUNCH(false, false);   // the kernels from before step 4n, instruction for instruction
+        if (max_flips == 0) RD_BD_LAUNCH(false, false);
         else RD_BD_LAUNCH(true, false);
     } else {
         if (max_flips == 0) RD_BD_LAUNCH(false, true);
@@ -568,34 +266,17 @@ extern "C" int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t 
                                             uint64_t clock, uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, int max_flips,
                                             int narrow, rd_burst_msg *msgs_out, uint32_t *n_msgs, uint32_t *long_runs,
                                             uint32_t *chunk) {
-    if (max_flips < 0 || max_flips > RD_BD_MAX_FLIPS)
-        return rd_fail_msg(RD_ERR_ARG, "burst repair: max_flips %d, not 0 .. %d", max_flips, RD_BD_MAX_FLIPS);
-    if (narrow != 0 && narrow != 1) return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: narrow %d, not 0 or 1", narrow);
-    if (narrow && cfg && cfg->symbol_length < RD_BD_NB_MIN_SL)
-        return rd_fail_msg(RD_ERR_ARG, "narrow-band filter: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
+    int rc = rd_burst_hook_modes(cfg, max_flips, narrow);
+    if (rc) return rc;
     if (!cfg || !cur || !runs || !n_runs || !msgs_out || !n_msgs || !long_runs || !chunk || n_ch < 1)
         return rd_fail_msg(RD_ERR_ARG, "null argument");
-    int rc = rd_burst_decode_check(cfg);
-    if (rc) return rc;                               // (nothing allocated, nothing launched)
-    const size_t n_out = (size_t)cfg->block_size;
-    if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "burst decode: stride %zu for %zu outputs", stride, n_out);
-    rc = rd_ensure_device_public();
-    if (rc) return rc;
-    const size_t n_win = n_out / RD_BU_WINDOW, bu_bytes = rd_bu_slot_bytes(n_ch, n_win), bd_bytes = rd_bd_slot_bytes(n_ch, n_win);
-    uint8_t *d_cur = nullptr, *d_prev = nullptr, *bu = nullptr, *bd = nullptr;
-    uint32_t *d_nb = nullptr;
-    void *d_bu = nullptr, *d_bd = nullptr;
-#define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
-    RD_DBG_CHK(hipMalloc(&d_cur, (size_t)n_ch * stride));
-    RD_DBG_CHK(hipMemcpy(d_cur, cur, (size_t)n_ch * stride, hipMemcpyHostToDevice));
-    if (prev) {
-        RD_DBG_CHK(hipMalloc(&d_prev, (size_t)n_ch * stride));
-        RD_DBG_CHK(hipMemcpy(d_prev, prev, (size_t)n_ch * stride, hipMemcpyHostToDevice));
-    }
-    RD_DBG_CHK(hipHostMalloc((void **)&bu, bu_bytes, hipHostMallocMapped));
-    RD_DBG_CHK(hipHostMalloc((void **)&bd, bd_bytes, hipHostMallocMapped));
-    memset(bu, 0xA5, bu_bytes);
-    memset(bd, 0xA5, bd_bytes);
+    if ((rc = rd_burst_dbg::check(cfg, stride, "burst decode"))) return rc;   // (nothing allocated, nothing launched)
+    const size_t n_out = (size_t)cfg->block_size, n_win = n_out / RD_BU_WINDOW;
+    rd_burst_dbg D;                                     // slot 0: the burst slot, slot 1: the message slot
+    if ((rc = D.upload(cur, prev, (size_t)n_ch * stride)) || (rc = D.map(0, rd_bu_slot_bytes(n_ch, n_win))) ||
+        (rc = D.map(1, rd_bd_slot_bytes(n_ch, n_win))) || (narrow && (rc = D.narrow(cfg->symbol_length))))
+        return rc;
+    uint8_t *bu = D.slot[0], *bd = D.slot[1];
     memcpy(bu, runs, rd_bu_floor_offset(n_ch, n_win));
     for (int c = 0; c < n_ch; c++) {
         rd_burst_floor f = {};
@@ -603,12 +284,10 @@ extern "C" int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t 
         f.chunk = (uint32_t)seq;
         memcpy(bu + rd_bu_floor_offset(n_ch, n_win) + (size_t)c * sizeof f, &f, sizeof f);
     }
-    RD_DBG_CHK(hipHostGetDevicePointer(&d_bu, bu, 0));
-    RD_DBG_CHK(hipHostGetDevicePointer(&d_bd, bd, 0));
-    if (narrow && (rc = rd_bd_narrow_upload(cfg->symbol_length, &d_nb))) goto out;
-    rc = rd_burst_decode_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, max_flips, d_nb, d_bu, d_bd, nullptr);
-    if (rc) goto out;
-    RD_DBG_CHK(hipDeviceSynchronize());
+    if ((rc = rd_burst_decode_launch(cfg, D.d_cur, D.d_prev, stride, n_ch, n_out, clock, seq, max_flips, D.d_nb, D.d_slot[0], D.d_slot[1],
+                                     nullptr)) ||
+        (rc = D.sync()))
+        return rc;
     memcpy(msgs_out, bd, rd_bd_header_offset(n_ch, n_win));
     for (int c = 0; c < n_ch; c++) {
         rd_bd_header h;
@@ -617,14 +296,7 @@ extern "C" int rd_debug_burst_decode_narrow(const rd_config *cfg, const uint8_t 
         long_runs[c] = h.long_runs;
         chunk[c] = h.chunk;
     }
-out:
-#undef RD_DBG_CHK
-    if (bu) hipHostFree(bu);
-    if (bd) hipHostFree(bd);
-    if (d_cur) hipFree(d_cur);
-    if (d_prev) hipFree(d_prev);
-    if (d_nb) hipFree(d_nb);
-    return rc;
+    return RD_OK;
 }
 
 extern "C" int rd_debug_burst_decode_repair(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,

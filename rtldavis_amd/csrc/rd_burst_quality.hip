@@ -16,31 +16,26 @@
 // 2047 = 3887 <= RD_BQ_LEN = 4096 outputs.  The filter needs M = SL + 2 outputs more on either side where the two
 // chunks hold them (zf0 .. zf1); the bytes are loaded as 16-byte vectors from L0 = zf0 rounded DOWN to 8 up to zf1
 // rounded up - lo_lim and block_size are multiples of 8, so a vector lies in one chunk and inside it.  z goes to LDS as
-// int16 pairs, output R0 - M + i at word i, zeros outside zf0 .. zf1.  A lane takes the outputs R0 + tid + 256 j; one in
+// int16 pairs, output R0 - M + i at word i, zeros outside zf0 .. zf1.  Bytes, grid choice, taps and z are the phases of
+// rd_burst_common.h; the sums are this kernel's own: a lane takes the outputs R0 + tid + 256 j; one in
 // the gap between noise and packet is skipped; y is 2 T packed 16-bit dot products (rd_bd_dot2); the eight sums are
 // per-lane partials, a fixed tree of shuffles, then LDS across the four waves - integer sums, the same bits on every run.
 // Thread 0 writes the record field by field with plain vector stores; no atomics.
 // LDS: the bytes (RD_BQ_LOAD x 2 = 8.25 KiB), z16 ((RD_BQ_LEN + 2 x 53) x 4 = 16.4 KiB), the taps (2 x 107 x 4), the
 // waves' partials: under 27 KiB.
 #include <cstddef>
-#include <cstring>
 
 #include <hip/hip_runtime.h>
 
 #include "rd_burst_common.h"
-#include "rd_internal.h"
 
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
-#define RD_BQ_THREADS 256
 #define RD_BQ_LEN 4096                                    // outputs of a region at most
-#define RD_BQ_NB_MAX_T (2 * RD_BD_NB_MAX_SL + 5)
 #define RD_BQ_NB_MAX_M (RD_BD_NB_MAX_SL + 2)
 #define RD_BQ_LOAD (RD_BQ_LEN + 128)                      // outputs loaded at most
 #define RD_BQ_SUMS 8                                      // pkt, sig, noise, pkt_nb, sig_nb, noise_nb, clipped, peak
 static_assert(RD_BQ_MAX_GAP + 16 * RD_BD_NB_MAX_SL + RD_BD_MAX_LOOK_W * RD_BU_WINDOW <= RD_BQ_LEN, "gap + noise + packet fit the region");
 static_assert(RD_BQ_LEN + 2 * RD_BQ_NB_MAX_M + 14 <= RD_BQ_LOAD && RD_BQ_LOAD % 8 == 0, "the filter's margins and the rounding to 8");
-static_assert(RD_BQ_LOAD * 2 + (RD_BQ_LEN + 2 * RD_BQ_NB_MAX_M) * 4 + 2 * RD_BQ_NB_MAX_T * 4 + (RD_BQ_THREADS / 64) * RD_BQ_SUMS * 8 + 64 <= 32768,
+static_assert(RD_BQ_LOAD * 2 + (RD_BQ_LEN + 2 * RD_BQ_NB_MAX_M) * 4 + 2 * RD_BD_NB_MAX_T * 4 + (RD_BURST_THREADS / 64) * RD_BQ_SUMS * 8 + 64 <= 32768,
               "the LDS budget of the file header");
 static_assert(sizeof(rd_burst_quality) == 64 && sizeof(rd_bq_header) == 16 && sizeof(rd_bd_header) == 16 && sizeof(rd_bx_header) == 16,
               "one header shape for both slots, one record layout");
@@ -57,14 +52,14 @@ struct rd_bq_params {
     int inband;                // SL >= 4 and the tables are there
 };
 
-__global__ __launch_bounds__(RD_BQ_THREADS) void k_chan_burst_quality(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
+__global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_quality(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
                                                                       size_t ch_stride, rd_bq_params P, const rd_burst_msg *recs,
                                                                       uint32_t cap, const rd_bq_header *hdr, rd_burst_quality *qual,
                                                                       const uint32_t *__restrict__ nb_tab) {
     __shared__ uint4 s_z[RD_BQ_LOAD / 8];                 // the loaded bytes: output L0 + i at bytes 2 i, 2 i + 1
     __shared__ uint32_t s_z16[RD_BQ_LEN + 2 * RD_BQ_NB_MAX_M];   // z as int16 pairs: output R0 - M + i at word i
-    __shared__ uint32_t s_hA[RD_BQ_NB_MAX_T], s_hB[RD_BQ_NB_MAX_T];   // H[g][kk - M] as (re, -im) and (im, re)
-    __shared__ unsigned long long s_red[RD_BQ_THREADS / 64][RD_BQ_SUMS];
+    __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // H[g][kk - M] as (re, -im) and (im, re)
+    __shared__ unsigned long long s_red[RD_BURST_THREADS / 64][RD_BQ_SUMS];
     __shared__ int64_t s_rec[4];                          // the record: channel, tau, f_re, f_im
     __shared__ uint32_t s_hd[2];                          // the header: n_msgs, chunk
     const unsigned grp = blockIdx.x;
@@ -112,12 +107,7 @@ __global__ __launch_bounds__(RD_BQ_THREADS) void k_chan_burst_quality(const uint
         }
         const uint8_t *src = cur + (size_t)c64 * ch_stride;
         const uint8_t *src_prev = prev ? prev + (size_t)c64 * ch_stride : nullptr;
-        // ---- the bytes of L0 .. L1 (L0 < 0 only with lo_lim < 0: there is a chunk before)
-        for (int v = (int)tid; v < (L1 - L0) / 8; v += RD_BQ_THREADS) {
-            const int t = L0 + 8 * v;                     // (L0 and 0 are multiples of 8: a vector lies in one chunk)
-            const uint8_t *gp = t < 0 ? src_prev + 2 * ((long)t + (long)P.block) : src + 2 * (long)t;
-            s_z[v] = *(const uint4 *)gp;
-        }
+        rd_bd_load_bytes(s_z, src, src_prev, L0, L1, (long)P.block, tid);   // (L0 < 0 only with lo_lim < 0: there is a chunk before)
         int nb_g = 0;
         if (inband) {
             // ---- sh, ca, cb and g of step 4n from the record's own f: the same in every wave
@@ -125,40 +115,16 @@ __global__ __launch_bounds__(RD_BQ_THREADS) void k_chan_burst_quality(const uint
             const int bl = 64 - __clzll((long long)(mr > mi ? mr : mi));   // (not both 0: at least 1)
             const int sh = bl > 15 ? bl - 15 : 0;
             const int ca = (int)(fr >> sh), cb = (int)(fi >> sh);          // each in -2^15 .. 2^15 - 1
-            const uint32_t cw = nb_tab[RD_BD_NB_GRID * T + (int)lane];
-            int sc = ca * (int)(int16_t)(cw & 0xFFFFu) + cb * ((int)cw >> 16);
-            nb_g = (int)lane;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const int os = __shfl_xor(sc, off), og = __shfl_xor(nb_g, off);
-                if (os > sc || (os == sc && og < nb_g)) {
-                    sc = os;
-                    nb_g = og;
-                }
-            }
-            if ((int)tid < T) {
-                const uint32_t hw = nb_tab[nb_g * T + (int)tid];
-                const int hr = (int)(int16_t)(hw & 0xFFFFu), hi = (int)hw >> 16;
-                s_hA[tid] = rd_bd_pack16(hr, -hi);
-                s_hB[tid] = rd_bd_pack16(hi, hr);
-            }
+            nb_g = rd_bd_grid_choice(nb_tab, T, ca, cb, lane);
+            rd_bd_load_taps(nb_tab, nb_g, T, s_hA, s_hB, tid);
         }
         __syncthreads();
-        // ---- z as int16 pairs, output R0 - M + i at word i: the samples of zf0 .. zf1, zeros outside
-        for (int i = (int)tid; i < len + 2 * M; i += RD_BQ_THREADS) {
-            const int t = R0 - M + i;
-            uint32_t zv = 0u;
-            if (t >= zf0 && t < zf1) {
-                const uint32_t a = zl[t - L0];
-                zv = rd_bd_pack16(2 * (int)(a & 0xFFu) - 255, 2 * (int)(a >> 8) - 255);
-            }
-            s_z16[i] = zv;
-        }
+        rd_bd_fill_z16(s_z16, zl, L0, R0 - M, len + 2 * M, zf0, zf1, tid);
         __syncthreads();
         // ---- the sums: output R0 + i, i = tid + 256 j
         unsigned long long a_pkt = 0ull, a_sig = 0ull, a_noise = 0ull, a_pkt_nb = 0ull, a_sig_nb = 0ull, a_noise_nb = 0ull;
         uint32_t a_clip = 0u, a_peak = 0u;
-        for (int i = (int)tid; i < len; i += RD_BQ_THREADS) {
+        for (int i = (int)tid; i < len; i += RD_BURST_THREADS) {
             const int t = R0 + i;
             const bool in_pkt = t >= w.p0, in_sig = in_pkt && t < w.s1, in_noise = n_noise > 0 && t < w.n1;
             if (!in_pkt && !in_noise) continue;           // the gap
@@ -175,7 +141,7 @@ __global__ __launch_bounds__(RD_BQ_THREADS) void k_chan_burst_quality(const uint
                     ar = rd_bd_dot2(s_hA[kk], x, ar);
                     ai = rd_bd_dot2(s_hB[kk], x, ai);
                 }
-                const int yr = (ar + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT, yi = (ai + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT;
+                const int yr = rd_bd_round(ar), yi = rd_bd_round(ai);
                 e_nb = (uint32_t)(yr * yr + yi * yi);     // < 2^25
             }
             if (in_noise) {
@@ -221,7 +187,7 @@ __global__ __launch_bounds__(RD_BQ_THREADS) void k_chan_burst_quality(const uint
 #pragma unroll
             for (int k = 0; k < RD_BQ_SUMS; k++) t[k] = s_red[0][k];
 #pragma unroll
-            for (int wv = 1; wv < RD_BQ_THREADS / 64; wv++) {
+            for (int wv = 1; wv < RD_BURST_THREADS / 64; wv++) {
 #pragma unroll
                 for (int k = 0; k < RD_BQ_SUMS - 1; k++) t[k] += s_red[wv][k];
                 t[7] = s_red[wv][7] > t[7] ? s_red[wv][7] : t[7];
@@ -267,7 +233,7 @@ int rd_burst_quality_launch(const rd_config *cfg, const uint8_t *chan_out, const
     P.n_ch = n_ch;
     P.gap = noise_gap;
     P.inband = cfg->symbol_length >= RD_BD_NB_MIN_SL ? 1 : 0;   // (at most RD_BD_NB_MAX_SL by the check above)
-    hipLaunchKernelGGL(k_chan_burst_quality, dim3((unsigned)n_groups), dim3(RD_BQ_THREADS), 0, st, chan_out, chan_prev, out_stride, P,
+    hipLaunchKernelGGL(k_chan_burst_quality, dim3((unsigned)n_groups), dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, out_stride, P,
                        recs, (uint32_t)cap, hdr, qual, narrow_tab);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_quality: %s", hipGetErrorString(e));
@@ -285,53 +251,28 @@ extern "C" int rd_debug_burst_quality(const rd_config *cfg, const uint8_t *cur, 
     if (!cfg || !cur || !msgs || !n_msgs_per_channel || !out || n_ch < 1) return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = rd_burst_decode_check(cfg);
     if (rc) return rc;                               // (nothing allocated, nothing launched)
-    const size_t n_out = (size_t)cfg->block_size;
-    if ((rc = rd_bursts_check(n_out))) return rc;
-    if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "burst quality: stride %zu for %zu outputs", stride, n_out);
-    const size_t n_win = n_out / RD_BU_WINDOW, cap = rd_bu_cap(n_win);
+    const size_t n_out = (size_t)cfg->block_size, n_win = n_out / RD_BU_WINDOW, cap = rd_bu_cap(n_win);
     for (int c = 0; c < n_ch; c++)
         if (n_msgs_per_channel[c] > cap) return rd_fail_msg(RD_ERR_ARG, "burst quality: %u records in channel %d, room for %zu", n_msgs_per_channel[c], c, cap);
-    rc = rd_ensure_device_public();
-    if (rc) return rc;
-    const size_t bd_bytes = rd_bd_slot_bytes(n_ch, n_win), bq_bytes = rd_bq_slot_bytes(n_ch, n_win);
-    uint8_t *d_cur = nullptr, *d_prev = nullptr, *bd = nullptr, *bq = nullptr;
-    uint32_t *d_nb = nullptr;
-    void *d_bd = nullptr, *d_bq = nullptr;
-#define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
-    RD_DBG_CHK(hipMalloc(&d_cur, (size_t)n_ch * stride));
-    RD_DBG_CHK(hipMemcpy(d_cur, cur, (size_t)n_ch * stride, hipMemcpyHostToDevice));
-    if (prev) {
-        RD_DBG_CHK(hipMalloc(&d_prev, (size_t)n_ch * stride));
-        RD_DBG_CHK(hipMemcpy(d_prev, prev, (size_t)n_ch * stride, hipMemcpyHostToDevice));
+    if ((rc = rd_burst_dbg::check(cfg, stride, "burst quality"))) return rc;   // (the stride, then the device: no device work for a wrong argument)
+    const size_t bq_bytes = rd_bq_slot_bytes(n_ch, n_win);
+    rd_burst_dbg D;                                     // slot 0: the decode slot, slot 1: the quality slot
+    if ((rc = D.upload(cur, prev, (size_t)n_ch * stride)) || (rc = D.map(0, rd_bd_slot_bytes(n_ch, n_win))) || (rc = D.map(1, bq_bytes)) ||
+        (cfg->symbol_length >= RD_BD_NB_MIN_SL && (rc = D.narrow(cfg->symbol_length))))
+        return rc;
+    memcpy(D.slot[0], msgs, (size_t)n_ch * cap * sizeof(rd_burst_msg));
+    rd_bd_header *h = (rd_bd_header *)(D.slot[0] + rd_bd_header_offset(n_ch, n_win));
+    for (int c = 0; c < n_ch; c++) {
+        h[c].n_msgs = n_msgs_per_channel[c];
+        h[c].long_runs = 0u;
+        h[c].chunk = RD_BQ_DEBUG_CHUNK;
+        h[c].pad = 0u;
     }
-    RD_DBG_CHK(hipHostMalloc((void **)&bd, bd_bytes, hipHostMallocMapped));
-    RD_DBG_CHK(hipHostMalloc((void **)&bq, bq_bytes, hipHostMallocMapped));
-    memcpy(bd, msgs, (size_t)n_ch * cap * sizeof(rd_burst_msg));
-    {
-        rd_bd_header *h = (rd_bd_header *)(bd + rd_bd_header_offset(n_ch, n_win));
-        for (int c = 0; c < n_ch; c++) {
-            h[c].n_msgs = n_msgs_per_channel[c];
-            h[c].long_runs = 0u;
-            h[c].chunk = RD_BQ_DEBUG_CHUNK;
-            h[c].pad = 0u;
-        }
-    }
-    memset(bq, 0xA5, bq_bytes);
-    RD_DBG_CHK(hipHostGetDevicePointer(&d_bd, bd, 0));
-    RD_DBG_CHK(hipHostGetDevicePointer(&d_bq, bq, 0));
-    if (cfg->symbol_length >= RD_BD_NB_MIN_SL && (rc = rd_bd_narrow_upload(cfg->symbol_length, &d_nb))) goto out;
-    rc = rd_burst_quality_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, noise_gap, d_nb, (const rd_burst_msg *)d_bd, cap,
-                                 (const rd_bq_header *)((uint8_t *)d_bd + rd_bd_header_offset(n_ch, n_win)), n_ch,
-                                 (rd_burst_quality *)d_bq, nullptr);
-    if (rc) goto out;
-    RD_DBG_CHK(hipDeviceSynchronize());
-    memcpy(out, bq, bq_bytes);
-out:
-#undef RD_DBG_CHK
-    if (bd) hipHostFree(bd);
-    if (bq) hipHostFree(bq);
-    if (d_cur) hipFree(d_cur);
-    if (d_prev) hipFree(d_prev);
-    if (d_nb) hipFree(d_nb);
-    return rc;
+    if ((rc = rd_burst_quality_launch(cfg, D.d_cur, D.d_prev, stride, n_ch, n_out, noise_gap, D.d_nb, (const rd_burst_msg *)D.d_slot[0], cap,
+                                      (const rd_bq_header *)((uint8_t *)D.d_slot[0] + rd_bd_header_offset(n_ch, n_win)), n_ch,
+                                      (rd_burst_quality *)D.d_slot[1], nullptr)) ||
+        (rc = D.sync()))
+        return rc;
+    memcpy(out, D.slot[1], bq_bytes);
+    return RD_OK;
 }

@@ -13,30 +13,23 @@
 //     z[t], M further to either side           (the filter)
 // all inside lo .. B - 1 by the candidate range, except z, which is 0 outside it.  Every tile computes its halos again
 // from the bytes: what a position gives is a function of the bytes alone, so the result does not depend on the tile size.
+// The taps and the filter are the phases of rd_burst_common.h; the z16 load straight from global memory, the int32-pair
+// sums, the per-position slicing and the ranking are this kernel's own.
 // LDS: S (int32 pair per output, 24.8 KiB; the int16 z of the filter lies in its place before S exists), y (12.6 KiB),
 // the candidates' margins (8.8 KiB), the taps: 47.0 KiB, three workgroups per CU.  One lane works per tau; most leave after the sync
 // test.  The records of a (centre, channel) are written in tau order by its one workgroup: the reported positions of a
 // pass over 256 taus are ranked by ballot and prefix count, no atomics; plain vector stores into the mapped slot.
-#include <cstring>
-#include <vector>
-
 #include <hip/hip_runtime.h>
 
 #include "rd_burst_common.h"
 #include "rd_host.h"
-#include "rd_internal.h"
-#include "rd_parse.h"
 
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
-#define RD_BS_THREADS 256
 #define RD_BS_MAX_BODY 2048                                           // SL (N - 1) < N SL + 1 <= 2048
 #define RD_BS_E_LEN (RD_BS_TILE + 2 * (RD_BD_NB_MAX_SL - 1))          // positions a tile evaluates at most
 #define RD_BS_S_LEN (RD_BS_E_LEN + RD_BS_MAX_BODY)
 #define RD_BS_Y_LEN (RD_BS_S_LEN + RD_BD_NB_MAX_SL + 1)
-#define RD_BS_NB_MAX_T (2 * RD_BD_NB_MAX_SL + 5)
 static_assert(RD_BS_Y_LEN + 2 * (RD_BD_NB_MAX_SL + 2) <= 2 * RD_BS_S_LEN, "the int16 z of the filter lies in S's place");
-static_assert(RD_BS_TILE % RD_BS_THREADS == 0, "a tile is a whole number of passes");
+static_assert(RD_BS_TILE % RD_BURST_THREADS == 0, "a tile is a whole number of passes");
 static_assert(sizeof(rd_bs_header) == 16 && sizeof(rd_burst_msg) == 64, "the slot layout of rd_bs_* (rd_internal.h)");
 static_assert(2 * RD_BD_NB_MAX_SL - 1 <= 255, "hits fits a byte");
 
@@ -49,14 +42,14 @@ struct rd_bs_params {
     uint64_t clock, seq;
 };
 
-__global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
+__global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_search(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ prev,
                                                                      size_t ch_stride, size_t n_out, rd_bs_params P, rd_burst_msg *recs,
                                                                      rd_bs_header *hdr, const uint32_t *__restrict__ nb_tab) {
     __shared__ int2 s_S[RD_BS_S_LEN];                    // S[e0 + i] at i: (re, im)
     __shared__ uint32_t s_y[RD_BS_Y_LEN];                // y[e0 - SL + j] at j: re in the low half, im in the high one
     __shared__ uint64_t s_m[RD_BS_E_LEN];                // margin + 1 of a passing position e0 + i, 0 of any other
-    __shared__ uint32_t s_hA[RD_BS_NB_MAX_T], s_hB[RD_BS_NB_MAX_T];   // H[g][kk - M] as (re, -im) and (im, re)
-    __shared__ uint32_t s_cnt[RD_BS_THREADS / 64];
+    __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // H[g][kk - M] as (re, -im) and (im, re)
+    __shared__ uint32_t s_cnt[RD_BURST_THREADS / 64];
     const int c = (int)blockIdx.x, ci = (int)blockIdx.y;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const int SL = P.sl, N = P.n_sym, body = SL * (N - 1), M = SL + 2, T = 2 * SL + 5;
@@ -84,12 +77,7 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
     }
     const uint8_t *src = cur + (size_t)c * ch_stride;
     const uint8_t *src_prev = prev ? prev + (size_t)c * ch_stride : nullptr;
-    if ((int)tid < T) {
-        const uint32_t hw = nb_tab[g * T + (int)tid];
-        const int hr = (int)(int16_t)(hw & 0xFFFFu), hi = (int)hw >> 16;
-        s_hA[tid] = rd_bd_pack16(hr, -hi);
-        s_hB[tid] = rd_bd_pack16(hi, hr);
-    }
+    rd_bd_load_taps(nb_tab, g, T, s_hA, s_hB, tid);
     uint32_t my_sync = 0u;                               // this thread's positions whose first 16 symbols equal sync
     uint32_t n_rep = 0u;                                 // reported positions so far (uniform)
     for (int a = tau_min; a <= tau_max; a += RD_BS_TILE) {
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
         uint32_t *z16 = (uint32_t *)s_S;
         {
             const int g0 = zt0 & ~7, g1 = (zt0 + nZ + 7) & ~7;
-            for (int t = g0 + 8 * (int)tid; t < g1; t += 8 * RD_BS_THREADS) {
+            for (int t = g0 + 8 * (int)tid; t < g1; t += 8 * RD_BURST_THREADS) {
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
                 const bool in = t >= lo && t < B;
                 if (in) v = *(const uint4 *)(t < 0 ? src_prev + 2 * ((long)t + (long)n_out) : src + 2 * (long)t);
@@ -117,37 +105,11 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
             }
         }
         __syncthreads();
-        // ---- y[e0 - SL + j] = (sum_kk H[g][kk - M] z[.. - (kk - M)] + 2^10) >> 11: that z lies at word j + T - 1 - kk
-        for (int base = (int)tid; base < nY; base += 4 * RD_BS_THREADS) {
-            int at[4], ar[4], ai[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int j = base + q * RD_BS_THREADS;
-                at[q] = (j < nY ? j : base) + T - 1;     // (an output past the region repeats the lane's first and is not stored)
-                ar[q] = 0;
-                ai[q] = 0;
-            }
-            for (int kk = 0; kk < T; kk++) {
-                const uint32_t hA = s_hA[kk], hB = s_hB[kk];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t zv = z16[at[q] - kk];
-                    ar[q] = rd_bd_dot2(hA, zv, ar[q]);
-                    ai[q] = rd_bd_dot2(hB, zv, ai[q]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int j = base + q * RD_BS_THREADS;
-                if (j < nY)
-                    s_y[j] = rd_bd_pack16((ar[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT,
-                                          (ai[q] + (1 << (RD_BD_NB_SHIFT - 1))) >> RD_BD_NB_SHIFT);
-            }
-        }
+        rd_bd_filter(z16, nY, T, s_hA, s_hB, s_y, tid);   // y[e0 - SL + j] at word j
         __syncthreads();                                 // y is whole, and z16 has been read: S may be written
         // ---- S[e0 + i] = sum of p' at y words i + 1 .. i + SL: a lane takes a stretch and slides the window along it
         {
-            const int per = (nS + RD_BS_THREADS - 1) / RD_BS_THREADS;
+            const int per = (nS + RD_BURST_THREADS - 1) / RD_BURST_THREADS;
             const int ia = (int)tid * per, ib = min(ia + per, nS);
             if (ia < ib) {
                 int sr = 0, si = 0, re, im;
@@ -170,7 +132,7 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
         }
         __syncthreads();
         // ---- one lane per position e0 + i: step 3s
-        for (int i = (int)tid; i < nE; i += RD_BS_THREADS) {
+        for (int i = (int)tid; i < nE; i += RD_BURST_THREADS) {
             int sr[16], si[16];
             long long dr = 0, di = 0;
 #pragma unroll
@@ -218,7 +180,7 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
         }
         __syncthreads();
         // ---- step 4s over the tile's own positions a .. b, in passes of 256 ascending taus; step 5s
-        for (int p0 = a; p0 <= b; p0 += RD_BS_THREADS) {  // (uniform: every thread makes every pass)
+        for (int p0 = a; p0 <= b; p0 += RD_BURST_THREADS) {  // (uniform: every thread makes every pass)
             const int tau = p0 + (int)tid, i = tau - e0;
             bool rep = false;
             uint32_t hits = 0u;
@@ -238,7 +200,7 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
             __syncthreads();
             uint32_t rank = n_rep, total = 0u;
 #pragma unroll
-            for (unsigned wv = 0; wv < RD_BS_THREADS / 64; wv++) {
+            for (unsigned wv = 0; wv < RD_BURST_THREADS / 64; wv++) {
                 const uint32_t n = s_cnt[wv];
                 if (wv < wave) rank += n;
                 total += n;
@@ -307,10 +269,9 @@ __global__ __launch_bounds__(RD_BS_THREADS) void k_chan_burst_search(const uint8
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
-                           size_t n_out, uint64_t clock, uint64_t seq, const uint8_t *centres, int n, const uint32_t *narrow_tab,
-                           void *slot_dev, hipStream_t st) {
-    if (!cfg || !chan_out || !slot_dev || !narrow_tab || !centres || n_ch < 1 || n_ch > RD_BS_MAX_CHANNELS)
+// what the launch and the hook test first: the configuration pointer, the channels, the centres
+static int rd_bs_check_args(const rd_config *cfg, int n_ch, const uint8_t *centres, int n) {
+    if (!cfg || !centres || n_ch < 1 || n_ch > RD_BS_MAX_CHANNELS)
         return rd_fail_msg(RD_ERR_ARG, "burst search: null argument or %d channels", n_ch);
     int bad = -1;
     const char *why = "";
@@ -318,18 +279,20 @@ int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const 
         if (bad < 0) return rd_fail_msg(RD_ERR_ARG, "burst search: %d centres, not 1 .. %d", n, RD_BS_MAX_CENTRES);
         return rd_fail_msg(RD_ERR_ARG, "burst search: centre %d: %s", bad, why);
     }
-    int rc = rd_burst_decode_check(cfg);
+    return RD_OK;
+}
+
+int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                           size_t n_out, uint64_t clock, uint64_t seq, const uint8_t *centres, int n, const uint32_t *narrow_tab,
+                           void *slot_dev, hipStream_t st) {
+    int rc = rd_bs_check_args(cfg, n_ch, centres, n);
     if (rc) return rc;
-    if (cfg->symbol_length < RD_BD_NB_MIN_SL)             // (at most RD_BD_NB_MAX_SL by the check above)
-        return rd_fail_msg(RD_ERR_ARG, "burst search: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
-    if (n_out != (size_t)cfg->block_size || out_stride < 2 * n_out || (out_stride & 15) || ((uintptr_t)chan_out & 15) ||
-        ((uintptr_t)chan_prev & 15) || ((uintptr_t)slot_dev & 15))
-        return rd_fail_msg(RD_ERR_ARG, "burst search: stride %zu for %zu outputs, or a misaligned buffer", out_stride, n_out);
+    if (!narrow_tab) return rd_fail_msg(RD_ERR_ARG, "burst search: null argument");
+    if ((rc = rd_burst_launch_check(cfg, chan_out, chan_prev, out_stride, n_ch, n_out, slot_dev, 0, narrow_tab, "burst search"))) return rc;
     rd_bs_params P;
     P.sl = cfg->symbol_length;
     P.n_sym = cfg->packet_symbols;
-    P.sync = 0u;
-    for (int i = 0; i < 16; i++) P.sync = (P.sync << 1) | (cfg->preamble[i] ? 1u : 0u);
+    P.sync = rd_bd_sync_word(cfg);
     P.look = RD_BU_WINDOW * rd_bd_look_windows(cfg);
     P.n_ch = n_ch;
     P.n_centres = n;
@@ -337,7 +300,7 @@ int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     P.clock = clock;
     P.seq = seq;
     uint8_t *base = (uint8_t *)slot_dev;
-    hipLaunchKernelGGL(k_chan_burst_search, dim3((unsigned)n_ch, (unsigned)n), dim3(RD_BS_THREADS), 0, st, chan_out, chan_prev, out_stride,
+    hipLaunchKernelGGL(k_chan_burst_search, dim3((unsigned)n_ch, (unsigned)n), dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, out_stride,
                        n_out, P, (rd_burst_msg *)base, (rd_bs_header *)(base + rd_bs_header_offset(n_ch)), narrow_tab);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_search: %s", hipGetErrorString(e));
@@ -349,47 +312,16 @@ int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const 
 extern "C" int rd_debug_burst_search(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                                      uint64_t clock, uint64_t seq, const uint8_t *centres, int n, rd_burst_msg *msgs_out,
                                      rd_bs_header *hdr_out) {
-    if (!cfg || !cur || !centres || !msgs_out || !hdr_out || n_ch < 1 || n_ch > RD_BS_MAX_CHANNELS)
-        return rd_fail_msg(RD_ERR_ARG, "burst search: null argument or %d channels", n_ch);
-    int bad = -1;
-    const char *why = "";
-    if (n < 1 || rd_bs_check_centres(centres, n, &bad, &why)) {
-        if (bad < 0) return rd_fail_msg(RD_ERR_ARG, "burst search: %d centres, not 1 .. %d", n, RD_BS_MAX_CENTRES);
-        return rd_fail_msg(RD_ERR_ARG, "burst search: centre %d: %s", bad, why);
-    }
-    int rc = rd_burst_decode_check(cfg);
-    if (rc) return rc;                               // (nothing allocated, nothing launched)
-    if (cfg->symbol_length < RD_BD_NB_MIN_SL)
-        return rd_fail_msg(RD_ERR_ARG, "burst search: symbol_length %d, at least %d", cfg->symbol_length, RD_BD_NB_MIN_SL);
-    const size_t n_out = (size_t)cfg->block_size;
-    if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "burst search: stride %zu for %zu outputs", stride, n_out);
-    rc = rd_ensure_device_public();
-    if (rc) return rc;
-    const size_t slot_bytes = rd_bs_slot_bytes(n_ch);
-    uint8_t *d_cur = nullptr, *d_prev = nullptr, *bs = nullptr;
-    uint32_t *d_nb = nullptr;
-    void *d_bs = nullptr;
-#define RD_DBG_CHK(x) do { if ((x) != hipSuccess) { rc = rd_fail_msg(RD_ERR_DEVICE, "%s failed", #x); goto out; } } while (0)
-    RD_DBG_CHK(hipMalloc(&d_cur, (size_t)n_ch * stride));
-    RD_DBG_CHK(hipMemcpy(d_cur, cur, (size_t)n_ch * stride, hipMemcpyHostToDevice));
-    if (prev) {
-        RD_DBG_CHK(hipMalloc(&d_prev, (size_t)n_ch * stride));
-        RD_DBG_CHK(hipMemcpy(d_prev, prev, (size_t)n_ch * stride, hipMemcpyHostToDevice));
-    }
-    RD_DBG_CHK(hipHostMalloc((void **)&bs, slot_bytes, hipHostMallocMapped));
-    memset(bs, 0xA5, slot_bytes);
-    RD_DBG_CHK(hipHostGetDevicePointer(&d_bs, bs, 0));
-    if ((rc = rd_bd_narrow_upload(cfg->symbol_length, &d_nb))) goto out;
-    rc = rd_burst_search_launch(cfg, d_cur, d_prev, stride, n_ch, n_out, clock, seq, centres, n, d_nb, d_bs, nullptr);
-    if (rc) goto out;
-    RD_DBG_CHK(hipDeviceSynchronize());
-    memcpy(msgs_out, bs, rd_bs_header_offset(n_ch));
-    memcpy(hdr_out, bs + rd_bs_header_offset(n_ch), (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * sizeof(rd_bs_header));
-out:
-#undef RD_DBG_CHK
-    if (bs) hipHostFree(bs);
-    if (d_cur) hipFree(d_cur);
-    if (d_prev) hipFree(d_prev);
-    if (d_nb) hipFree(d_nb);
-    return rc;
+    if (!cur || !msgs_out || !hdr_out) return rd_fail_msg(RD_ERR_ARG, "burst search: null argument or %d channels", n_ch);
+    int rc = rd_bs_check_args(cfg, n_ch, centres, n);
+    if (rc || (rc = rd_burst_dbg::check(cfg, stride, "burst search", RD_BD_NB_MIN_SL))) return rc;   // (nothing allocated, nothing launched)
+    rd_burst_dbg D;
+    if ((rc = D.upload(cur, prev, (size_t)n_ch * stride)) || (rc = D.map(0, rd_bs_slot_bytes(n_ch))) || (rc = D.narrow(cfg->symbol_length)) ||
+        (rc = rd_burst_search_launch(cfg, D.d_cur, D.d_prev, stride, n_ch, (size_t)cfg->block_size, clock, seq, centres, n, D.d_nb, D.d_slot[0],
+                                     nullptr)) ||
+        (rc = D.sync()))
+        return rc;
+    memcpy(msgs_out, D.slot[0], rd_bs_header_offset(n_ch));
+    memcpy(hdr_out, D.slot[0] + rd_bs_header_offset(n_ch), (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * sizeof(rd_bs_header));
+    return RD_OK;
 }

@@ -1,9 +1,10 @@
-// CPU harness around rtldavis_amd/csrc/rd_math.h.  TEST INFRASTRUCTURE ONLY: it lets the
+// CPU harness around rtldavis_amd/csrc/rd_math.h and rd_burst_candidate.h.  TEST INFRASTRUCTURE ONLY: it lets the
 // CPU test-suite run the exact arithmetic the HIP kernels execute (same inline functions,
 // same fp32 fma sequence) against the oracle without a GPU.  Nothing in the product links it.
 #include <cstring>
 #include <vector>
 
+#include "../rtldavis_amd/csrc/rd_burst_candidate.h"
 #include "../rtldavis_amd/csrc/rd_math.h"
 
 extern "C" {
@@ -81,5 +82,27 @@ float hh_threshold(float F) { return rd_run_threshold(F); }
 uint32_t hh_exact_bit_f64(double nx, double ny, double npx, double npy) {
     rd_dd2 n = {nx, ny}, np = {npx, npy};
     return rd_exact_bit_f64(n, np);
+}
+
+// The candidate test of k_chan_burst_decode and k_chan_burst_expect (rd_burst_candidate.h) on `rows` candidates: symbol k
+// of row r is s[(r n + k) sl] > 0, the stride the kernels read LDS with.  e[n] = the syndrome table the kernels build
+// (0 below 16); out[6 r ..] = pass, flips, k1, k2 (-1: none), margin, id.  max_flips = 0 runs the form without repair, as
+// the launches do.
+void hh_bd_candidate(const int64_t *s, long rows, int sl, int n, uint32_t sync, int max_flips, uint16_t *e, int64_t *out) {
+    for (int k = 0; k < n; k++) e[k] = k < 16 ? 0 : (uint16_t)rd_bd_syndrome(k, n);
+    for (long r = 0; r < rows; r++) {
+        const int64_t *row = s + r * n * sl;
+        rd_bd_cand c = {0u, 0ull, 0u};
+        const bool ok = max_flips == 0 ? rd_bd_candidate<false>(row, sl, n, sync, 0, nullptr, c)
+                                       : rd_bd_candidate<true>(row, sl, n, sync, max_flips, e, c);
+        const int64_t flips = ok ? (int64_t)(c.flips & 0xFFu) : 0;
+        int64_t *o = out + 6 * r;
+        o[0] = ok ? 1 : 0;
+        o[1] = flips;
+        o[2] = flips >= 1 ? (int64_t)((c.flips >> 8) & 0xFFu) : -1;
+        o[3] = flips == 2 ? (int64_t)((c.flips >> 16) & 0xFFu) : -1;
+        o[4] = ok ? (int64_t)c.margin : 0;
+        o[5] = ok ? (int64_t)c.id : 0;
+    }
 }
 }

@@ -1,8 +1,12 @@
 """The CRC-guided repair of k_chan_burst_decode (include/rtldavis_hip.h, BURST DECODE, steps 5a, 5b, 6') without a device:
 the model of tests/burst_repair_cases.py against the definition's own pieces - the syndrome table against a bitwise CRC,
 single flips at every payload position, the model at max_flips = 0 against burst_decode_cases.decode_model -, the edge of
-every crafted case, the argument rule of the hook, the derived bound on false accepts, and the gain on noisy bursts."""
+every crafted case, the argument rule of the hook, the derived bound on false accepts, and the gain on noisy bursts; and
+the kernels' own candidate test (rtldavis_amd/csrc/rd_burst_candidate.h), compiled for the CPU by tests/host_harness.cpp,
+against the model."""
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -72,6 +76,96 @@ def test_repair_batch_equals_repair_model():
         want = [(-1 if x is None else len(x[0])) for x in (RP.repair_model(row, r) for row in s)]
         assert np.array_equal(got, want), r
     assert {0, 1, 2, -1} <= set(int(x) for x in RP.repair_batch(s, 2))
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def candidate():
+    """hh_bd_candidate of tests/host_harness.cpp: rd_burst_candidate.h, the text both decoders compile, built for the CPU."""
+    so = os.path.join(ROOT, "tests", "_build", "libhostharness.so")
+    src = [os.path.join(ROOT, "tests", "host_harness.cpp")] + [os.path.join(ROOT, "rtldavis_amd", "csrc", h)
+                                                               for h in ("rd_burst_candidate.h", "rd_parse.h", "rd_math.h")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in src):
+        os.makedirs(os.path.dirname(so), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-march=x86-64-v3", "-shared", "-fPIC", "-o", so, src[0]])
+    fn = C.CDLL(so).hh_bd_candidate
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+
+    def run(s, max_flips, sync=RP.SYNC, sl=1):
+        """int64 [rows, 6]: pass, flips, k1, k2, margin, id; and E.  sl > 1: the rows are read with that stride."""
+        s = np.ascontiguousarray(s, np.int64)
+        rows, n = s.shape
+        wide = np.full((rows, n, sl), 1 - 2 ** 62, np.int64)   # what lies between the symbols must not be read
+        wide[:, :, 0] = s
+        e, out = np.full(n, 0xFFFF, np.uint16), np.full((rows, 6), -7, np.int64)
+        word = int("".join(str(int(b)) for b in sync), 2)
+        fn(wide.ctypes.data, rows, sl, n, word, max_flips, e.ctypes.data, out.ctypes.data)
+        return out, e
+    return run
+
+
+def _model_rows(s, max_flips, sync=RP.SYNC):
+    """RP.repair_model for every row in the form of hh_bd_candidate; rows whose first 16 symbols are not the sync word are
+    None by the model's first test and are not handed to it."""
+    s = np.asarray(s, np.int64)
+    want = np.zeros((s.shape[0], 6), np.int64)
+    want[:, 2:4] = -1
+    for j in np.flatnonzero(np.all((s[:, :16] > 0) == np.asarray(sync, bool)[None, :], axis=1)):
+        r = RP.repair_model(s[j], max_flips, tuple(sync))
+        if r is not None:
+            ks, bits, margin = r
+            ident = bits[16] | bits[17] << 1 | bits[18] << 2     # rd_swap_bits8(byte 2) & 7
+            want[j] = (1, len(ks), ks[0] if ks else -1, ks[1] if len(ks) == 2 else -1, margin, ident)
+    return want
+
+
+def test_candidate_function_of_the_kernels_equals_repair_model(candidate):
+    """rd_bd_candidate, compiled for the CPU, on the symbol sums of every candidate tau of every run of the crafted repair
+    launches (the grid at N = 40, 64, 80 among them) and on seeded random rows with the sync word forced and many |s|
+    ties, at max_flips 0, 1, 2: (pass, flips, k1, k2, margin, id) are the model's; E is the model's table."""
+    for n in (40, 64, 80):
+        e = candidate(np.ones((1, n), np.int64), 2)[1]
+        assert np.array_equal(e, RP.syndrome_table(n)), n
+    seen = {0: 0, 1: 0, 2: 0}
+    launches = RP.crafted_launches()
+    assert {(40, 1), (40, 14), (80, 1), (80, 14)} <= set(RP.GRID) and all(RP.grid_launch(n, sl) in launches for n, sl in RP.GRID)
+    for L in launches:
+        n_win = L.cur.shape[1] // (2 * RP.W)
+        sync = DC.shape(L.cfg)[2]
+        for c in range(L.n_ch):
+            for run in range(min(int(L.n_runs[c]), L.runs.shape[1])):
+                first, windows = int(L.runs[c, run]["first"]), int(L.runs[c, run]["windows"])
+                if windows > RP.MAX_W or windows == 0 or first >= n_win or first + windows > n_win:
+                    continue
+                got = L.sums(c, run)
+                if got is None:
+                    continue
+                s = got[1]
+                for r in (0, 1, 2):
+                    out = candidate(s, r, sync, sl=1 if r else 3)[0]
+                    assert np.array_equal(out, _model_rows(s, r, sync)), (L.name, c, run, r)
+                    for k in seen:
+                        seen[k] += int(((out[:, 0] == 1) & (out[:, 1] == k)).sum()) if r == 2 else 0
+    assert min(seen.values()) > 0, seen
+    rng = np.random.default_rng(23)
+    for n in (40, 80):
+        m = 3000
+        s = rng.integers(1, 12, (m, n)) * np.where(rng.integers(0, 2, (m, n)) == 1, 1, -1)   # small magnitudes: ties everywhere
+        s[:, :16] = np.abs(s[:, :16]) * np.where(np.asarray(RP.SYNC) == 1, 1, -1)
+        good = 2 * np.unpackbits(np.frombuffer(DC.packet(n, seed=n + 1), np.uint8)).astype(np.int64) - 1
+        for j in range(m // 2):                              # half of them: a packet with 0 .. 3 flips, the id symbols among them
+            s[j] = np.abs(s[j]) * good
+            for k in rng.integers(16, 16 + (4 if j % 2 else n - 16), j % 4):
+                s[j, k] = -s[j, k]
+        s[m // 2: m // 2 + 50, 5] *= -1                      # a wrong sync symbol
+        s[-50:] *= 2 ** 40                                   # 64-bit magnitudes
+        for r in (0, 1, 2):
+            out = candidate(s, r)[0]
+            assert np.array_equal(out, _model_rows(s, r)), (n, r)
+        assert {0, 1, 2} <= set(int(x) for x in out[out[:, 0] == 1, 1]) and (out[:, 0] == 0).sum() > 50
 
 
 def test_model_without_repair_is_the_decode_model():

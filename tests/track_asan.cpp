@@ -1,6 +1,6 @@
 // track_asan.cpp - the pure-host parts of BURST EXPECT (rtldavis_amd/csrc/rd_host.cpp: rd_bx_check_table, rd_bx_range,
 // rd_bx_repeats) under -fsanitize=address,undefined, driven by tests/test_track_sanitizers.py.  A stand-alone program:
-//   track_asan table                 every rule of the table, the limits on either side
+//   track_asan table                 every rule of the table, the limits on either side; step 7'; the decoders' candidate test
 //   track_asan range <seed> <n>      rd_bx_range against a naive enumeration of every tau, clocks near 0 and near 2^64
 //   track_asan file <in> <out>       cases from a file (7 x int64 each: sl, n_sym, block_size, have_prev, clock, t_lo, t_hi
 //                                    as bit patterns) -> 3 x int32 each (found, tau_a, tau_b)
@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "../rtldavis_amd/csrc/rd_burst_candidate.h"
 #include "../rtldavis_amd/csrc/rd_host.h"
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #c); exit(1); } } while (0)
@@ -145,6 +146,53 @@ static int test_repeats(void) {
     return 0;
 }
 
+// The candidate test both decoders compile (rd_burst_candidate.h) on arrays of exactly the size it may read: a packet
+// with its CRC, then the same with one and with two weak wrong symbols, every |s| else equal - the list's ties -, at
+// strides 1, 3 and 14.
+static int test_candidate(void) {
+    const uint32_t sync = 0xCB89u;
+    for (int n : {40, 64, 80})
+        for (int sl : {1, 3, 14}) {
+            std::vector<uint16_t> e((size_t)n, 0);
+            for (int k = 16; k < n; k++) e[(size_t)k] = (uint16_t)rd_bd_syndrome(k, n);
+            std::vector<uint32_t> air((size_t)(n / 8), 0u);          // the on-air bytes: sync, payload, CRC of the bit-swapped payload
+            air[0] = sync >> 8;
+            air[1] = sync & 0xFFu;
+            uint32_t crc = 0u;
+            for (int b = 2; b < n / 8 - 2; b++) {
+                air[(size_t)b] = (uint32_t)(rnd() & 0xFFu);
+                crc = rd_crc16_step(crc, rd_swap_bits8(air[(size_t)b]));
+            }
+            air[(size_t)(n / 8 - 2)] = rd_swap_bits8(crc >> 8);
+            air[(size_t)(n / 8 - 1)] = rd_swap_bits8(crc & 0xFFu);
+            std::vector<int> bit((size_t)n, 0);
+            uint32_t syn = 0u;                                         // and the table is linear: the syndrome of a packet is 0
+            for (int k = 0; k < n; k++) {
+                bit[(size_t)k] = (int)((air[(size_t)(k >> 3)] >> (7 - (k & 7))) & 1u);
+                if (bit[(size_t)k]) syn ^= e[(size_t)k];
+            }
+            CHECK(syn == 0u);
+            std::vector<int64_t> s((size_t)(sl * (n - 1) + 1), INT64_MIN);   // (what lies between the symbols is never read)
+            for (int k = 0; k < n; k++) s[(size_t)(sl * k)] = bit[(size_t)k] ? 1000 : -1000;
+            rd_bd_cand c;
+            CHECK(rd_bd_candidate<false>(s.data(), sl, n, sync, 0, nullptr, c) && c.flips == 0u && c.margin == 1000u);
+            CHECK(rd_bd_candidate<true>(s.data(), sl, n, sync, 2, e.data(), c) && c.flips == 0u);
+            CHECK(c.id == (uint32_t)(bit[16] | bit[17] << 1 | bit[18] << 2));
+            const int k1 = 16 + (int)(rnd() % 3), k2 = n - 1;
+            s[(size_t)(sl * k1)] = bit[(size_t)k1] ? -7 : 7;
+            CHECK(!rd_bd_candidate<false>(s.data(), sl, n, sync, 0, nullptr, c));
+            CHECK(rd_bd_candidate<true>(s.data(), sl, n, sync, 1, e.data(), c) && c.flips == (1u | (uint32_t)k1 << 8) && c.margin == 1000u);
+            CHECK(c.id == (uint32_t)(bit[16] | bit[17] << 1 | bit[18] << 2));
+            s[(size_t)(sl * k2)] = bit[(size_t)k2] ? -9 : 9;
+            CHECK(!rd_bd_candidate<true>(s.data(), sl, n, sync, 1, e.data(), c));
+            CHECK(rd_bd_candidate<true>(s.data(), sl, n, sync, 2, e.data(), c) && c.flips == (2u | (uint32_t)k1 << 8 | (uint32_t)k2 << 16));
+            s[0] = -s[0];                                          // a wrong sync symbol: never
+            CHECK(!rd_bd_candidate<true>(s.data(), sl, n, sync, 2, e.data(), c));
+        }
+    printf("candidate ok\n");
+    return 0;
+}
+
 static int run_file(const char *in, const char *out) {
     FILE *f = fopen(in, "rb");
     CHECK(f);
@@ -168,7 +216,7 @@ static int run_file(const char *in, const char *out) {
 }
 
 int main(int argc, char **argv) {
-    if (argc >= 2 && !strcmp(argv[1], "table")) return test_table() || test_repeats();
+    if (argc >= 2 && !strcmp(argv[1], "table")) return test_table() || test_repeats() || test_candidate();
     if (argc >= 4 && !strcmp(argv[1], "range")) return test_range(strtoull(argv[2], nullptr, 10), atoi(argv[3]));
     if (argc >= 4 && !strcmp(argv[1], "file")) return run_file(argv[2], argv[3]);
     fprintf(stderr, "usage: track_asan table | range <seed> <n> | file <in> <out>\n");
