@@ -848,6 +848,85 @@ int rd_wb_expected_message_quality(rd_wideband *w, rd_burst_quality *out, int ca
  * p0 .. s1 - 1, noise n0 .. n1 - 1 (n0 = n1 = p0 when nothing of it is left).  Returns 1, or 0 with out zeroed for a record
  * that is not measurable (or a null out). */
 int rd_bq_window(int sl, int n_sym, int block_size, int have_prev, int64_t tau, int gap, int32_t *out);
+/* BURST CLIPS (k_chan_burst_clips, rd_burst_clips.hip): the channelized IQ bytes of every burst, cut out on the device -
+ * the bursts that were decoded, those that were not, those of other devices on the band, with what lies in front of and
+ * behind each.  The host cannot fetch them afterwards: with two chunks in flight chunk k's channelized buffer is being
+ * overwritten by the time the host has read chunk k's records.  With clips on, a chunk carries one more launch behind its
+ * last burst kernel and in front of the demodulator; the kernels in front are not changed.  A clip is a copy of bytes,
+ * nothing else.  Notation of BURST DECODE: B = block_size, K = the chunk's absolute output clock, have_prev,
+ * lo_lim = -B with have_prev else 0; channel c's bytes are continued to t < 0 by chunk k-1's bytes.
+ * Settings: sources = a bit mask, RD_BC_RUNS (every rd_burst of k_chan_bursts) | RD_BC_MESSAGES (every row the decode,
+ * expect and search kernels wrote for this chunk), 0 = off; pre, post = the outputs in front of and behind a request, each
+ * a multiple of 8 in 0 .. RD_BC_MAX_ROLL; quota Q = the outputs per channel and chunk, a multiple of 8 in 8 .. 65536 with
+ * n_channels Q 2 <= 2^26 bytes; RD_BC_PER = 16 clip records per channel and chunk.
+ * A request is a half-open interval [a, e) of outputs of one channel, relative to the chunk's first output:
+ *     source                                          a                 e                              ref
+ *     1 run: an rd_burst k_chan_bursts really wrote   128 first - pre   128 (first + windows) + post   first
+ *     2, 3, 4 message row, first symbol end tau,      P0 - pre          P0 + N SL + post               the row's time
+ *       P0 = tau - SL + 1
+ *     0 tail                                          0                 owed                           0
+ * Runs: the "never writes" rule of BURST DECODE applies - windows = 0, first >= nW, first + windows > nW or a place past
+ * ceil(nW / 2) is skipped; windows > MAX_W is no obstacle here.  Message rows are those of the decode slot of channel c
+ * (source 2), the rows of the expect slot whose channel is c (3) and the rows of the search slot of channel c (4), as the
+ * kernels wrote them - before the host's steps 7 / 7' / 7s.  A slot whose kernel was not launched for this chunk
+ * contributes nothing.  A row whose channel field is not c - out of range included - or that fails the test of BURST
+ * QUALITY (tau as a 64-bit value; lo_lim <= P0 and P0 + N SL <= B) is skipped.
+ * Tail: the post-roll the previous chunk could not deliver.  When the previous chunk of this receiver was submitted with
+ * clips on and its header of channel c says 0 < owed <= RD_BC_MAX_ROLL, the first request of channel c is the tail.
+ * Clamping (rd_bc_window): t0 = max(a, lo_lim) rounded down to a multiple of 8, t1 = min(e, B) rounded up to one,
+ * n = t1 - t0; a request with n <= 0 (or e <= a) is skipped.  lo_lim and B are multiples of 8, so every clip is whole
+ * 16-byte vectors that lie in one chunk each.  flags: bit 0 RD_BC_CUT_START: a < lo_lim; bit 1 RD_BC_CUT_END: e > B; bit 2
+ * RD_BC_FROM_PREV: t0 < 0, bytes of the previous chunk are included.
+ * Order of a channel's requests: the tail; runs in record order; decode rows in record order; expect rows by table index;
+ * search rows by (centre index, place).  Allocation is in that order: a request gets offset = the outputs used so far; it
+ * is dropped whole, and counted in `dropped`, when offset + n > Q or RD_BC_PER records are already written; later
+ * requests are still tried.  Overlapping requests are not merged: each gets its own copy (rtldavis_amd/clips.py merges).
+ * owed for the next chunk = the maximum of e - B over the clips WRITTEN with RD_BC_CUT_END, at most RD_BC_MAX_ROLL; a tail
+ * that is cut again carries its remainder on (B < owed).
+ * A clip's bytes are outputs t0 .. t1 - 1 of the channel as they lie, 2 bytes each.  Header per channel: { n_clips,
+ * dropped, owed, used (outputs), chunk, pad = 0 }.  The same chunks, records and settings give the same bits on every run:
+ * one workgroup per channel, no atomics, the list built in one fixed order.
+ * rd_wb_set_burst_clips: the values for the chunks submitted from now on; sources = 0, the default, is off - then nothing
+ * is launched and every other call returns what it returns without this section, byte for byte.  RD_ERR_ARG (checked
+ * first) for unknown source bits, a roll or quota outside its range or no multiple of 8, or a pool over 2^26 bytes;
+ * RD_ERR_STATE unless the receiver is quiet and bursts are on, and for RD_BC_MESSAGES unless burst decode is on.
+ * rd_wb_set_bursts(w, 0) switches clips off; rd_wb_set_burst_decode(w, 0) clears RD_BC_MESSAGES, and switches clips off
+ * when nothing is left.  rd_wideband_reset keeps the settings and forgets owed.  No device work (safe before fork): the
+ * first submit with clips in force allocates the slots.  rd_wb_burst_clips_config: the values the next submit will use.
+ * rd_wb_burst_clips: the clips of the chunk the last fetch returned, kept by that fetch - which copies only the used part
+ * of each channel's pool - and valid with later chunks in flight, until the next fetch.  Channels ascending, a channel's
+ * clips in their order; `offset` is rewritten to the clip's place in the packed `bytes`, in outputs (2 bytes each).
+ * *n = the records, *n_bytes = the bytes; with cap < *n or bytes_cap < *n_bytes: RD_ERR_CAPACITY, nothing is lost, call
+ * again (out / bytes may be NULL with a capacity of 0).  dropped: NULL, or room for n_channels counts.  RD_ERR_STATE before
+ * any fetch and when that chunk was submitted with clips off. */
+#define RD_BC_RUNS 1u
+#define RD_BC_MESSAGES 2u
+#define RD_BC_MAX_ROLL 1024      /* pre, post and owed at most */
+#define RD_BC_MAX_QUOTA 65536
+#define RD_BC_MAX_POOL (1u << 26) /* n_channels x quota x 2 bytes at most */
+#define RD_BC_PER 16             /* clip records per channel and chunk */
+#define RD_BC_CUT_START 1        /* rd_burst_clip.flags */
+#define RD_BC_CUT_END 2
+#define RD_BC_FROM_PREV 4
+typedef struct rd_burst_clip {
+    int32_t  channel;
+    uint32_t source;   /* 0 tail, 1 run, 2 decode row, 3 expected row, 4 searched row */
+    uint32_t flags;
+    int32_t  t0;       /* first output, relative to the chunk; may be negative */
+    uint32_t n;        /* outputs */
+    uint32_t offset;   /* outputs: where the clip lies (see rd_wb_burst_clips) */
+    uint64_t time;     /* K + t0 */
+    uint64_t ref;
+    uint32_t chunk;    /* low 32 bits of the chunk's sequence number */
+    uint32_t pad;
+} rd_burst_clip;
+int rd_wb_set_burst_clips(rd_wideband *w, int sources, int pre, int post, int quota);
+int rd_wb_burst_clips_config(rd_wideband *w, int *sources, int *pre, int *post, int *quota);
+int rd_wb_burst_clips(rd_wideband *w, rd_burst_clip *out, int cap, int *n, uint8_t *bytes, size_t bytes_cap, size_t *n_bytes,
+                      uint32_t *dropped, int n_channels);
+/* The clamp of one request, on the host (no device is touched): out = { t0, n, flags }.  Returns 1, or 0 with out zeroed for
+ * a request that gives no clip (or a null out, or a block_size that is no positive multiple of 8). */
+int rd_bc_window(int block_size, int have_prev, int64_t a, int64_t e, int32_t *out);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
  * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */
@@ -927,6 +1006,22 @@ int rd_debug_burst_search(const rd_config *cfg, const uint8_t *cur, const uint8_
 #define RD_BQ_DEBUG_CHUNK 0x51A7u
 int rd_debug_burst_quality(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch,
                            int noise_gap, const rd_burst_msg *msgs, const uint32_t *n_msgs_per_channel, rd_burst_quality *out);
+/* rd_debug_burst_clips (tests/test_burst_clips.py): k_chan_burst_clips alone, the same pattern - cur / prev as above;
+ * runs[n_ch][cap] and n_runs[n_ch] go into a burst slot as they are, msgs[n_ch][cap] and n_msgs[n_ch] into a decode slot
+ * (msgs and n_msgs may be NULL without RD_BC_MESSAGES); x_msgs[RD_BX_MAX] with x_hdr[RD_BX_MAX][4] and n_expect (1 .. RD_BX_MAX), or
+ * NULLs and 0: the expect kernel was not launched; s_msgs[RD_BS_MAX_CENTRES][n_ch][RD_BS_PER] with
+ * s_hdr[RD_BS_MAX_CENTRES][n_ch] and n_search (1 .. RD_BS_MAX_CENTRES), or NULLs and 0; owed_prev[n_ch]: `owed` of the
+ * previous chunk's headers, or NULL when no chunk before had clips on.  out: the receiver's slot of rd_bc_slot_size(n_ch,
+ * quota) bytes - [n_ch][RD_BC_PER] rd_burst_clip | [n_ch] six uint32 { n_clips, dropped, owed, used, chunk, pad } | padding
+ * to a multiple of 16 | [n_ch][2 quota] bytes - filled with 0xA5, written by one launch and copied out whole.  RD_ERR_ARG
+ * before any device work for settings rd_wb_set_burst_clips refuses, sources = 0, a block_size that is no multiple of 128,
+ * and with RD_BC_MESSAGES a configuration rd_wb_set_burst_decode refuses. */
+size_t rd_bc_slot_size(int n_ch, int quota);
+int rd_debug_burst_clips(const rd_config *cfg, const uint8_t *cur, const uint8_t *prev, size_t stride, int n_ch, uint64_t clock,
+                         uint64_t seq, const rd_burst *runs, const uint32_t *n_runs, const rd_burst_msg *msgs,
+                         const uint32_t *n_msgs, const rd_burst_msg *x_msgs, const uint32_t *x_hdr, int n_expect,
+                         const rd_burst_msg *s_msgs, const rd_bs_header *s_hdr, int n_search, const uint32_t *owed_prev,
+                         int sources, int pre, int post, int quota, uint8_t *out);
 
 #ifdef __cplusplus
 }

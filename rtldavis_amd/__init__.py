@@ -9,8 +9,11 @@ capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s
 ``WidebandReceiver.set_burst_search`` finds a station never yet heard, with no energy gate, at every output position.
 ``WidebandReceiver.set_burst_quality`` measures every burst message's power and noise on the device, and
 ``rtldavis_amd.burst_packets`` turns the rows into ``dsp.Packet``s with ``rssi`` and ``snr`` for ``protocol.Parser.parse``.
+``WidebandReceiver.set_burst_clips`` records the channelized IQ of every burst on the device; ``rtldavis_amd.clips``
+(``ClipStitcher``, ``write_sigmf``, ``read_sigmf``) turns the clips into SigMF ``cu8`` recordings.
 """
-__all__ = ["dsp", "batch", "synth", "wideband", "track", "WidebandReceiver", "parse_packet", "burst_packets"]
+__all__ = ["dsp", "batch", "synth", "wideband", "track", "clips", "WidebandReceiver", "parse_packet", "burst_packets",
+           "ClipStitcher", "Recording", "write_sigmf", "read_sigmf"]
 
 import os as _os
 
@@ -46,6 +49,9 @@ def __getattr__(name):
     if name == "burst_packets":
         from .wideband import burst_packets
         return burst_packets
+    if name in ("ClipStitcher", "Recording", "write_sigmf", "read_sigmf"):
+        from . import clips
+        return getattr(clips, name)
     if name == "parse_packet":
         from .dsp import parse_packet
         return parse_packet

@@ -82,6 +82,11 @@ class RdBurstMsg(C.Structure):
                 ("data", C.c_uint8 * RD_BURST_MSG_BYTES), ("ones", C.c_uint8), ("id", C.c_uint8), ("pad", C.c_uint8 * 4)]
 
 
+class RdBurstClip(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("source", C.c_uint32), ("flags", C.c_uint32), ("t0", C.c_int32), ("n", C.c_uint32),
+                ("offset", C.c_uint32), ("time", C.c_uint64), ("ref", C.c_uint64), ("chunk", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # rtldavis_hip.h RD_IQ_*: the sample formats of a wideband capture, name -> (code, numpy dtype of one component)
 # (code 3 is unassigned and there is no "f32": float32 I/Q is "cf32", code 4)
 RD_IQ_U8, RD_IQ_S8, RD_IQ_S16, RD_IQ_CF32 = 0, 1, 2, 4
@@ -223,6 +228,10 @@ SIGNATURES = {
     "rd_wb_burst_message_quality": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "rd_wb_expected_message_quality": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "rd_bq_window": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _P]),
+    "rd_wb_set_burst_clips": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rd_wb_burst_clips_config": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rd_wb_burst_clips": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_int]),
+    "rd_bc_window": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),
@@ -242,6 +251,9 @@ SIGNATURES = {
     "rd_debug_burst_search": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, C.c_int,
                                         _P, _P]),
     "rd_debug_burst_quality": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P, _P]),
+    "rd_bc_slot_size": (C.c_size_t, [C.c_int, C.c_int]),
+    "rd_debug_burst_clips": (C.c_int, [C.POINTER(RdConfig), _P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_uint64, _P, _P, _P, _P,
+                                       _P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

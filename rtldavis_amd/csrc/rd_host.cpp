@@ -372,3 +372,14 @@ extern "C" int rd_bq_window(int sl, int n_sym, int block_size, int have_prev, in
     out[4] = w.n1;
     return ok ? 1 : 0;
 }
+
+// BURST CLIPS (include/rtldavis_hip.h): the clamp of one request, through the C ABI (rd_host.h: rd_bc_window_of)
+extern "C" int rd_bc_window(int block_size, int have_prev, int64_t a, int64_t e, int32_t *out) {
+    if (!out) return 0;
+    rd_bc_clamped c;
+    const bool ok = rd_bc_window_of(block_size, have_prev, a, e, &c);
+    out[0] = c.t0;
+    out[1] = c.n;
+    out[2] = c.flags;
+    return ok ? 1 : 0;
+}

@@ -8,6 +8,7 @@
 //   rd_waiter             the polling policy of every host wait: spin, then yield, then sleep, with a deadline
 //   rd_bq_windows_of      BURST QUALITY: a record's packet, sync and noise windows (inline: the kernel evaluates it too)
 //   rd_bs_range           BURST SEARCH: a chunk's candidate positions (inline: the kernel evaluates it too)
+//   rd_bc_window_of       BURST CLIPS: a request's clamp to the two chunks and to whole vectors (inline: the kernel evaluates it too)
 // py = /root/reference/src/rtldavis/dsp.py
 #pragma once
 #include <stddef.h>
@@ -117,6 +118,28 @@ RD_HOST_DEVICE static inline bool rd_bq_windows_of(int sl, int n_sym, int block_
     return true;
 }
 // (rd_bq_window, include/rtldavis_hip.h, is the same through the C ABI)
+
+// BURST CLIPS (include/rtldavis_hip.h): the clamp-and-round rule of one request [a, e) - t0 = max(a, lo_lim) rounded down to
+// a multiple of 8, t1 = min(e, block_size) rounded up, n = t1 - t0, flags bits 0 .. 2.  false, and *c zeroed, for a request
+// that gives no clip: e <= a, nothing of it inside lo_lim .. block_size, or a block_size that is no positive multiple of 8.
+// a and e are 64-bit values and no request overflows the test.  The one definition serves the host (rd_bc_window, the C
+// form the tests call) and k_chan_burst_clips, which bounds every copy by it.
+struct rd_bc_clamped {
+    int32_t t0, n, flags;
+};
+RD_HOST_DEVICE static inline bool rd_bc_window_of(int block_size, int have_prev, int64_t a, int64_t e, rd_bc_clamped *c) {
+    c->t0 = c->n = c->flags = 0;
+    if (block_size < 8 || (block_size & 7)) return false;
+    const int64_t B = block_size, lo_lim = have_prev ? -B : 0;
+    if (e <= a || a >= B || e <= lo_lim) return false;          // (from here on lo_lim - 7 <= every value below <= B)
+    const int64_t t0 = (a > lo_lim ? a : lo_lim) & ~(int64_t)7;  // (two's complement: rounds towards minus infinity)
+    const int64_t t1 = ((e < B ? e : B) + 7) & ~(int64_t)7;
+    c->t0 = (int32_t)t0;
+    c->n = (int32_t)(t1 - t0);
+    c->flags = (a < lo_lim ? RD_BC_CUT_START : 0) | (e > B ? RD_BC_CUT_END : 0) | (t0 < 0 ? RD_BC_FROM_PREV : 0);
+    return true;
+}
+// (rd_bc_window, include/rtldavis_hip.h, is the same through the C ABI)
 
 // Host waits poll (the runtime's blocking waits add 10-20 ms of wake-up latency on this platform).  A wait spins on
 // `pause` for the first ~50 us, then yields the core, then sleeps 50 us at a time; it gives up at its deadline.

@@ -345,6 +345,29 @@ static inline size_t rd_bq_slot_bytes(int n_ch, size_t n_win) { return rd_bq_exp
 int rd_burst_quality_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                             size_t n_out, int noise_gap, const uint32_t *narrow_tab, const rd_burst_msg *recs, size_t cap,
                             const rd_bq_header *hdr, int n_groups, rd_burst_quality *qual, hipStream_t st);
+// Burst clips (rd_burst_clips.hip: k_chan_burst_clips; the definition: include/rtldavis_hip.h, BURST CLIPS), queued behind
+// the chunk's last burst kernel on the same stream.  One workgroup per channel.  It reads, where given, the slots the
+// kernels in front filled - burst_slot (rd_bursts_launch), decode_slot (rd_burst_decode_launch; null: not launched),
+// expect_slot with n_expect entries (null / 0: not launched), search_slot with n_search centres (null / 0) - and prev_hdr,
+// the [n_ch] headers of the clip slot the chunk before wrote (null: that chunk had no clips, or there is none).  All are
+// device addresses of mapped host memory, as is slot, of rd_bc_slot_bytes(n_ch, quota) laid out as
+//   [n_ch][RD_BC_PER] rd_burst_clip | [n_ch] rd_bc_header | padding to a multiple of 16 | [n_ch][2 quota] bytes
+// The kernel writes every header and, per channel, the first header.n_clips record places and the first 2 header.used
+// bytes of its pool.  cfg is read for symbol_length and packet_symbols, and checked, with RD_BC_MESSAGES only.
+struct rd_bc_header {
+    uint32_t n_clips, dropped;
+    uint32_t owed, used;         // outputs
+    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
+    uint32_t pad;
+};
+static inline size_t rd_bc_header_offset(int n_ch) { return (size_t)n_ch * RD_BC_PER * sizeof(rd_burst_clip); }
+static inline size_t rd_bc_pool_offset(int n_ch) { return (rd_bc_header_offset(n_ch) + (size_t)n_ch * sizeof(rd_bc_header) + 15) & ~(size_t)15; }
+static inline size_t rd_bc_slot_bytes(int n_ch, int quota) { return rd_bc_pool_offset(n_ch) + (size_t)n_ch * 2 * (size_t)quota; }
+int rd_burst_clips_check(int n_ch, int sources, int pre, int post, int quota);   // the rule of rd_wb_set_burst_clips: RD_ERR_ARG with a message
+int rd_burst_clips_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
+                          size_t n_out, uint64_t clock, uint64_t seq, int sources, int pre, int post, int quota,
+                          const void *burst_slot, const void *decode_slot, const void *expect_slot, int n_expect,
+                          const void *search_slot, int n_search, const rd_bc_header *prev_hdr, void *slot, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);

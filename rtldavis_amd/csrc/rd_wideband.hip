@@ -77,6 +77,15 @@
 // demodulator launch; it reads d_out[s] and the end of d_out[s ^ 1] under the ordering above and needs the narrow-band
 // tables.  Its slot per parity ([8][n_ch][4] records | [8][n_ch] headers) is allocated by the first submit with a list in
 // force; the fetch checks every header's chunk and runs step 7s.  An empty list: nothing allocated, launched or copied.
+// Burst clips (rd_wb_set_burst_clips / rd_wb_burst_clips; rd_burst_clips.hip): a source mask, two rolls and a quota, kept
+// like repair.  With a source set, k_chan_burst_clips is queued behind the chunk's last burst kernel and in front of its
+// demodulator launch.  It reads, on the device, the burst, decode, expect and search slots of the chunk's parity that the
+// kernels in front wrote (the expect and search slots only when their kernels were launched for this chunk), the headers
+// of the OTHER parity's clip slot when chunk k-1 was submitted with clips on - written by that chunk's launch, earlier on
+// the same stream; reset() forgets them -, d_out[s] and d_out[s ^ 1] under the ordering above, and writes records, headers
+// and bytes into a mapped pinned slot of its own per parity, allocated by the first submit with clips in force (again
+// when the quota grows: the receiver was quiet when it changed).  The fetch checks every header's chunk and copies out
+// the records and only the used part of each channel's pool.  Off: nothing allocated, launched or copied.
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -185,6 +194,18 @@ struct rd_wideband {
     int q_gap = 0;
     uint8_t *h_bq[2] = {nullptr, nullptr};
     std::vector<rd_burst_quality> bq_last, xq_last;
+    // burst clips: the settings of the chunks submitted from now on (sources 0: off; never on without bursts, RD_BC_MESSAGES
+    // never without decode), the mapped pinned slots per parity (rd_internal.h: rd_bc_slot_bytes of bc_slot_quota), what
+    // each parity's chunk was submitted with (its sources - 0: none, the slot holds no header of it - and quota), and the
+    // records, packed bytes and drop counts the last fetch kept
+    int bc_sources = 0, bc_pre = 256, bc_post = 128, bc_quota = 4096;
+    int bc_slot_quota = 0;
+    uint8_t *h_bc[2] = {nullptr, nullptr};
+    int bc_sub[2] = {0, 0}, bc_sub_quota[2] = {0, 0};
+    bool last_clips = false;
+    std::vector<rd_burst_clip> bc_last;
+    std::vector<uint8_t> bc_bytes_last;
+    std::vector<uint32_t> bc_dropped_last;
 };
 #define RD_BU_THR_DEFAULT 0xFFFFFFFFu   // no window's energy reaches it
 
@@ -271,6 +292,7 @@ extern "C" void rd_wideband_destroy(rd_wideband *w) {
             hipHostFree(w->h_bx[i]);
             hipHostFree(w->h_bs[i]);
             hipHostFree(w->h_bq[i]);
+            hipHostFree(w->h_bc[i]);
         }
         hipFree(w->d_lvacc);
         hipFree(w->d_nb);
@@ -382,6 +404,27 @@ static int wb_alloc_decode(rd_wideband *w) {
     return RD_OK;
 }
 
+// the clip slots for the quota in force, when clips are first wanted.  Remade when the quota has grown: the receiver was
+// quiet when it changed, so nothing reads or writes the old ones, and their headers - what the last chunk owes the next -
+// are final and move into the new ones.
+static int wb_alloc_clips(rd_wideband *w) {
+    if (w->bc_slot_quota >= w->bc_quota) return RD_OK;
+    const size_t ho = rd_bc_header_offset(w->n_ch), hb = (size_t)w->n_ch * sizeof(rd_bc_header);
+    for (int i = 0; i < 2; i++) {
+        uint8_t *slot = nullptr;
+        WCHK(hipHostMalloc((void **)&slot, rd_bc_slot_bytes(w->n_ch, w->bc_quota), hipHostMallocMapped));
+        if (w->h_bc[i]) {
+            memcpy(slot + ho, w->h_bc[i] + ho, hb);
+            hipHostFree(w->h_bc[i]);
+        } else {
+            memset(slot + ho, 0xFF, hb);                  // (a clip count no chunk can have)
+        }
+        w->h_bc[i] = slot;
+    }
+    w->bc_slot_quota = w->bc_quota;
+    return RD_OK;
+}
+
 extern "C" int rd_wideband_reset(rd_wideband *w) {
     if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
     int rc = rd_reset(w->dem);   // waits for the chunks in flight: their channelizers ran before their demod launches
@@ -423,6 +466,11 @@ extern "C" int rd_wideband_reset(rd_wideband *w) {
     }
     w->sm_chunk = -2;
     w->sm_prev.clear();
+    w->last_clips = false;        // (the settings stay; what the run before owed goes)
+    for (int i = 0; i < 2; i++) {
+        w->bc_sub[i] = 0;
+        if (w->h_bc[i]) memset(w->h_bc[i] + rd_bc_header_offset(w->n_ch), 0xFF, (size_t)w->n_ch * sizeof(rd_bc_header));
+    }
     return RD_OK;
 }
 
@@ -498,6 +546,7 @@ extern "C" int rd_wb_set_bursts(rd_wideband *w, int enabled) {
         w->quality = false;
         w->expect.clear();
         w->search.clear();
+        w->bc_sources = 0;
     }
     return RD_OK;
 }
@@ -518,6 +567,7 @@ extern "C" int rd_wb_set_burst_decode(rd_wideband *w, int enabled) {
         w->quality = false;
         w->expect.clear();
         w->search.clear();
+        w->bc_sources &= ~(int)RD_BC_MESSAGES;   // (clips of runs go on; nothing left: off)
     }
     return RD_OK;
 }
@@ -686,6 +736,48 @@ extern "C" int rd_wb_searched_messages(rd_wideband *w, rd_burst_msg *out, int ca
     return RD_OK;
 }
 
+extern "C" int rd_wb_set_burst_clips(rd_wideband *w, int sources, int pre, int post, int quota) {
+    if (!w) return rd_fail_msg(RD_ERR_ARG, "null handle");
+    int rc = rd_burst_clips_check(w->n_ch, sources, pre, post, quota);
+    if (rc) return rc;
+    if (rd_demod_inflight(w->dem))
+        return rd_fail_msg(RD_ERR_STATE, "%d chunk(s) in flight: fetch them before burst clips are switched", rd_demod_inflight(w->dem));
+    if (!w->bursts) return rd_fail_msg(RD_ERR_STATE, "burst clips need bursts on (rd_wb_set_bursts)");
+    if ((sources & (int)RD_BC_MESSAGES) && !w->decode)
+        return rd_fail_msg(RD_ERR_STATE, "burst clips of messages need burst decode on (rd_wb_set_burst_decode)");
+    w->bc_sources = sources;
+    w->bc_pre = pre;
+    w->bc_post = post;
+    w->bc_quota = quota;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_clips_config(rd_wideband *w, int *sources, int *pre, int *post, int *quota) {
+    if (!w || !sources || !pre || !post || !quota) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    *sources = w->bc_sources;
+    *pre = w->bc_pre;
+    *post = w->bc_post;
+    *quota = w->bc_quota;
+    return RD_OK;
+}
+
+extern "C" int rd_wb_burst_clips(rd_wideband *w, rd_burst_clip *out, int cap, int *n, uint8_t *bytes, size_t bytes_cap, size_t *n_bytes,
+                                 uint32_t *dropped, int n_channels) {
+    if (!w || !n || !n_bytes || cap < 0 || (!out && cap > 0) || (!bytes && bytes_cap > 0)) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (dropped && n_channels != w->n_ch)
+        return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: room for %d drop counts of %d", n_channels, w->n_ch);
+    if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
+    if (!w->last_clips) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk was submitted with burst clips off (rd_wb_set_burst_clips)");
+    *n = (int)w->bc_last.size();
+    *n_bytes = w->bc_bytes_last.size();
+    if (dropped) memcpy(dropped, w->bc_dropped_last.data(), (size_t)w->n_ch * sizeof(uint32_t));
+    if (cap < *n || bytes_cap < *n_bytes)
+        return rd_fail_msg(RD_ERR_CAPACITY, "%d burst clips of %zu bytes, room for %d of %zu", *n, *n_bytes, cap, bytes_cap);
+    if (*n) memcpy(out, w->bc_last.data(), (size_t)*n * sizeof(rd_burst_clip));
+    if (*n_bytes) memcpy(bytes, w->bc_bytes_last.data(), *n_bytes);
+    return RD_OK;
+}
+
 extern "C" int rd_wb_set_burst_threshold(rd_wideband *w, const uint32_t *thr, int n) {
     if (!w || !thr) return rd_fail_msg(RD_ERR_ARG, "null argument");
     if (n != w->n_ch) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d thresholds for %d channels", n, w->n_ch);
@@ -751,6 +843,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     if (w->spec_n && (rc = wb_alloc_spectrum(w))) return rc;
     if (w->bursts && (rc = wb_alloc_bursts(w))) return rc;
     if (w->decode && (rc = wb_alloc_decode(w))) return rc;
+    if (w->bursts && w->bc_sources && (rc = wb_alloc_clips(w))) return rc;
     rc = rd_demod_check_room(w->dem);   // a third chunk is refused before anything is queued
     if (rc) return rc;
     const int s = (int)(w->n_sub & 1);
@@ -788,6 +881,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                             (uint64_t)w->n_sub, sp, w->st);
         if (rc) return rc;
     }
+    w->bc_sub[s] = 0;   // (whatever chunk k-2 was submitted with: this chunk has clips only once its launch is queued below)
     if (w->bursts) {
         // burst slot s: free by the argument for the level slot; the thresholds travel in it (header comment)
         memcpy(w->h_bu[s] + rd_bu_thr_offset(w->n_ch, wb_bu_windows(w)), w->thr.data(), (size_t)w->n_ch * sizeof(uint32_t));
@@ -795,9 +889,9 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
         WCHK(hipHostGetDevicePointer(&bu, w->h_bu[s], 0));
         rc = rd_bursts_launch(w->d_out[s], 2 * w->B, w->n_ch, w->B, (uint64_t)w->n_sub, bu, w->st);
         if (rc) return rc;
+        void *bd = nullptr, *bx_used = nullptr, *bs_used = nullptr;   // what the clip kernel may read: the slots written for this chunk
         if (w->decode) {
             // decode slot s: free by the argument for the level slot; d_out[s ^ 1] holds chunk k-1 (header comment)
-            void *bd = nullptr;
             WCHK(hipHostGetDevicePointer(&bd, w->h_bd[s], 0));
             rc = rd_burst_decode_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
                                         w->clock, (uint64_t)w->n_sub, w->repair, w->narrow ? w->d_nb : nullptr, bu, bd, w->st);
@@ -824,6 +918,7 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                                             w->clock, (uint64_t)w->n_sub, nx, w->repair, w->narrow ? w->d_nb : nullptr, bx, w->st);
                 if (rc) return rc;
                 w->bx_launched[s] = true;
+                bx_used = bx;
                 if (w->quality) {
                     rc = rd_burst_quality_launch(&w->cfg, w->d_out[s], q_prev, 2 * w->B, w->n_ch, w->B, w->q_gap, w->d_nb, (const rd_burst_msg *)bx,
                                                  1, (const rd_bq_header *)((uint8_t *)bx + RD_BX_HEADER_OFFSET), nx,
@@ -840,7 +935,25 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
                 rc = rd_burst_search_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B,
                                             w->clock, (uint64_t)w->n_sub, w->search.data(), ns, w->d_nb, bs, w->st);
                 if (rc) return rc;
+                bs_used = bs;
             }
+        }
+        if (w->bc_sources) {
+            // clip slot s: free by the argument for the level slot; slot s ^ 1 holds chunk k-1's headers when that chunk
+            // had clips on, written by its launch earlier on this stream (header comment)
+            void *bc = nullptr, *bc_prev = nullptr;
+            WCHK(hipHostGetDevicePointer(&bc, w->h_bc[s], 0));
+            if (w->n_sub >= 1 && w->bc_sub[s ^ 1]) {
+                WCHK(hipHostGetDevicePointer(&bc_prev, w->h_bc[s ^ 1], 0));
+                bc_prev = (uint8_t *)bc_prev + rd_bc_header_offset(w->n_ch);
+            }
+            rc = rd_burst_clips_launch(&w->cfg, w->d_out[s], w->n_sub >= 1 ? w->d_out[s ^ 1] : nullptr, 2 * w->B, w->n_ch, w->B, w->clock,
+                                       (uint64_t)w->n_sub, w->bc_sources, w->bc_pre, w->bc_post, w->bc_quota, bu, bd, bx_used,
+                                       bx_used ? w->bx_n[s] : 0, bs_used, bs_used ? w->bs_n[s] : 0, (const rd_bc_header *)bc_prev, bc,
+                                       w->st);
+            if (rc) return rc;
+            w->bc_sub[s] = w->bc_sources;
+            w->bc_sub_quota[s] = w->bc_quota;
         }
     }
     w->clock += w->B;
@@ -856,6 +969,37 @@ static int wb_fetched(rd_wideband *w, int rc) {
     w->last_bursts = false;
     w->last_decode = false;
     w->last_quality = false;
+    w->last_clips = false;
+    if (w->bc_sub[w->last & 1]) {
+        // as the burst records below: k_chan_burst_clips ran before the demodulator launch that has reported.  Every header
+        // carries the chunk's number; a channel's clips are the first n_clips of its record places, its bytes the first
+        // 2 * used of its pool - only those are copied, packed channel after channel, and `offset` is rewritten to match.
+        const int sc = (int)(w->last & 1);
+        const size_t q = (size_t)w->bc_sub_quota[sc];
+        const rd_burst_clip *recs = (const rd_burst_clip *)w->h_bc[sc];
+        const rd_bc_header *hd = (const rd_bc_header *)(w->h_bc[sc] + rd_bc_header_offset(w->n_ch));
+        const uint8_t *pool = w->h_bc[sc] + rd_bc_pool_offset(w->n_ch);
+        w->bc_last.clear();
+        w->bc_bytes_last.clear();
+        w->bc_dropped_last.assign(w->n_ch, 0u);
+        for (int c = 0; c < w->n_ch; c++) {
+            const rd_bc_header h = hd[c];
+            if (h.chunk != (uint32_t)w->last || h.n_clips > (uint32_t)RD_BC_PER || h.used > q)
+                return rd_fail_msg(RD_ERR_DEVICE, "clip header of channel %d belongs to chunk %u (%u clips, %u outputs), not %ld", c, h.chunk,
+                                   h.n_clips, h.used, w->last);
+            w->bc_dropped_last[c] = h.dropped;
+            const size_t base = w->bc_bytes_last.size() / 2;   // outputs packed so far
+            for (uint32_t i = 0; i < h.n_clips; i++) {
+                rd_burst_clip k = recs[(size_t)c * RD_BC_PER + i];
+                if ((size_t)k.offset + k.n > h.used)
+                    return rd_fail_msg(RD_ERR_DEVICE, "clip %u of channel %d lies at %u + %u of %u outputs", i, c, k.offset, k.n, h.used);
+                k.offset = (uint32_t)(base + k.offset);
+                w->bc_last.push_back(k);
+            }
+            w->bc_bytes_last.insert(w->bc_bytes_last.end(), pool + (size_t)c * 2 * q, pool + (size_t)c * 2 * q + 2 * (size_t)h.used);
+        }
+        w->last_clips = true;
+    }
     if (w->decode) {
         // as the burst records below: k_chan_burst_decode ran before the demodulator launch that has reported.  Every
         // header carries the chunk's number; a channel's messages are the first n_msgs of its record places.

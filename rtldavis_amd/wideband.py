@@ -100,6 +100,36 @@ QUALITY_UNMEASURABLE = 128             # ``flags`` bit 7: the message's channel 
 QUALITY_MAX_GAP = 1024                 # ``noise_gap`` at most
 
 
+# burst_clips(): one row per clip - the layout of rd_burst_clip
+CLIP_DTYPE = np.dtype([("channel", np.int32), ("source", np.uint32), ("flags", np.uint32), ("t0", np.int32), ("n", np.uint32),
+                       ("offset", np.uint32), ("time", np.uint64), ("ref", np.uint64), ("chunk", np.uint32), ("pad", np.uint32)])
+CLIP_RUNS = 1                          # ``sources`` bit 0: every run of ``bursts()``
+CLIP_MESSAGES = 2                      # ``sources`` bit 1: every row the decode, expect and search kernels wrote
+CLIP_MAX_ROLL = 1024                   # ``pre`` and ``post`` at most
+CLIP_MAX_QUOTA = 65536
+CLIP_PER = 16                          # clips per channel and chunk
+CLIP_SOURCE_TAIL, CLIP_SOURCE_RUN, CLIP_SOURCE_DECODE, CLIP_SOURCE_EXPECTED, CLIP_SOURCE_SEARCHED = range(5)
+CLIP_CUT_START = 1                     # ``flags`` bit 0: the request began before the chunk before (or, without one, the chunk)
+CLIP_CUT_END = 2                       # ``flags`` bit 1: the request ends in the next chunk, whose first clip is its tail
+CLIP_FROM_PREV = 4                     # ``flags`` bit 2: the clip begins in the chunk before
+
+
+class BurstClips(NamedTuple):
+    """``WidebandReceiver.burst_clips()``: ``records`` (``CLIP_DTYPE``, channels ascending, a channel's clips in the order
+    tail, runs, decode rows, expected rows, searched rows), ``iq`` (uint8 [total_outputs, 2]: the clips' channelized bytes,
+    I and Q per output, one clip behind the other - row ``records["offset"][i]`` is clip i's first output), ``dropped``
+    (uint32 per channel: requests that did not fit the quota or the ``CLIP_PER`` records) and ``chunk``."""
+    records: np.ndarray
+    iq: np.ndarray
+    dropped: np.ndarray
+    chunk: int
+
+    def clip(self, i: int) -> np.ndarray:
+        """uint8 [n, 2]: a view of clip ``i``'s outputs ``time .. time + n - 1`` of its channel."""
+        r = self.records[i]
+        return self.iq[int(r["offset"]): int(r["offset"]) + int(r["n"])]
+
+
 class BurstMessages(NamedTuple):
     """``WidebandReceiver.burst_messages()``: ``records`` (structured array of ``BURST_MSG_DTYPE``, one row per burst that
     carried a CRC-valid message, channels ascending, a channel's runs ascending), ``long_runs`` (uint32 per channel: runs
@@ -624,6 +654,46 @@ class WidebandReceiver:
     def expected_message_quality(self) -> np.ndarray:
         """``QUALITY_DTYPE`` rows parallel to ``expected_messages().records`` of the same fetch."""
         return self._quality_rows(_lib.lib().rd_wb_expected_message_quality)
+
+    def set_burst_clips(self, sources: int = CLIP_RUNS | CLIP_MESSAGES, pre: int = 256, post: int = 128,
+                        quota: int = 4096) -> None:
+        """From the next chunk on, the device cuts the channelized IQ of every burst out of the chunk and ``burst_clips()``
+        hands it over: with ``CLIP_RUNS`` the outputs of every run of ``bursts()``, with ``CLIP_MESSAGES`` the packet of
+        every row the decode, expect and search kernels wrote (before the fetch drops repeats), each with ``pre`` outputs
+        in front and ``post`` behind (multiples of 8, 0 .. 1024).  A request that begins before the chunk takes the bytes
+        from the chunk before; one that ends behind it is completed by the first clip (source 0, the tail) of the next
+        chunk.  ``quota`` (a multiple of 8, 8 .. 65536, ``n_channels * quota * 2 <= 2**26``) is the room per channel and
+        chunk in outputs; a request that does not fit is dropped whole and counted.  Overlapping requests each get their
+        own copy - ``clips.ClipStitcher`` merges them into recordings.  ``sources = 0`` (the default) is the receiver
+        without it, byte for byte.  ValueError for a value out of range; RuntimeError unless nothing is in flight and
+        ``set_bursts(True)``, and for ``CLIP_MESSAGES`` unless ``set_burst_decode(True)``.  Switching bursts off switches
+        clips off, switching decode off clears ``CLIP_MESSAGES``; ``reset()`` keeps the settings."""
+        _lib.check(_lib.lib().rd_wb_set_burst_clips(self._h, int(sources), int(pre), int(post), int(quota)))
+
+    def burst_clips_config(self):
+        """``(sources, pre, post, quota)`` the next submitted chunk will use."""
+        v = [C.c_int(0) for _ in range(4)]
+        _lib.check(_lib.lib().rd_wb_burst_clips_config(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def burst_clips(self) -> BurstClips:
+        """The clips of the chunk the last fetch returned (``BurstClips``), kept by that fetch: valid with later chunks in
+        flight, until the next fetch.  A clip is matched to a message row by ``(channel, ref == row["time"])``, to a run by
+        ``(channel, source == CLIP_SOURCE_RUN, ref == first)``.  RuntimeError before any fetch and when that chunk was
+        submitted with clips off."""
+        L = _lib.lib()
+        n, nb = C.c_int(0), C.c_size_t(0)
+        dropped = np.zeros(self.n_channels, np.uint32)
+        rc = L.rd_wb_burst_clips(self._h, None, 0, C.byref(n), None, 0, C.byref(nb), dropped.ctypes.data, dropped.size)
+        if rc != _lib.RD_ERR_CAPACITY:
+            _lib.check(rc)
+        recs = np.zeros(max(n.value, 1), CLIP_DTYPE)
+        iq = np.zeros(max(nb.value, 2), np.uint8)
+        _lib.check(L.rd_wb_burst_clips(self._h, recs.ctypes.data, recs.size, C.byref(n), iq.ctypes.data, iq.size, C.byref(nb),
+                                       dropped.ctypes.data, dropped.size))
+        chunk = C.c_uint64(0)
+        _lib.check(L.rd_wb_fetched_chunk(self._h, C.byref(chunk)))
+        return BurstClips(recs[: n.value].copy(), iq[: nb.value].reshape(-1, 2).copy(), dropped, int(chunk.value))
 
     def reset(self) -> None:
         """Back to the state after construction: clock at 0, zero history, demodulators reset, the constructed channel

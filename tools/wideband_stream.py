@@ -14,7 +14,8 @@ Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its 
                                     [--burst-decode [--burst-decode-out FILE]]
                                     [--burst-repair N [--burst-repair-out FILE]]
                                     [--burst-narrow [--burst-narrow-out FILE]] [--track [--track-out FILE]]
-                                    [--burst-quality [--burst-quality-out FILE]] [--json OUT]
+                                    [--burst-quality [--burst-quality-out FILE]]
+                                    [--burst-clips [--burst-clips-out FILE]] [--json OUT]
 
 --parse: the receiver runs Parser.parse's front half in its kernels (WidebandReceiver.set_parse) and parsed() is read
 after every fetch, the next chunk in flight; one more window measures the route without it - a quiet receiver per chunk,
@@ -41,6 +42,9 @@ with the spread of the windows beside the difference.  The kernel's own time is 
 --burst-quality: as --burst-narrow, but the second window of every repeat has WidebandReceiver.set_burst_quality(True) on
 (k_chan_burst_quality behind k_chan_burst_decode) and reads burst_message_quality() per chunk; written to
 --burst-quality-out (default profiles/wideband_burst_quality.txt).
+--burst-clips: the same windows, but the second of every repeat has WidebandReceiver.set_burst_clips() on (both sources, the
+default rolls and quota: k_chan_burst_clips behind k_chan_burst_decode) and reads burst_clips() per chunk; written to
+--burst-clips-out (default profiles/wideband_burst_clips.txt).
 --burst-narrow: as --burst-decode, but the two windows of every repeat are bursts + decode on, and bursts + decode +
 WidebandReceiver.set_burst_narrow(True) on (k_chan_burst_decode<false, true>: the narrow-band filter in front of the
 discriminator, in every chunk that holds a run); the capture is --burst-decode's, an undamaged burst on every channel.
@@ -102,6 +106,10 @@ def main():
                     help="time every window with bursts + decode on, and with burst quality on top; write --burst-quality-out")
     ap.add_argument("--burst-quality-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                                 "wideband_burst_quality.txt"))
+    ap.add_argument("--burst-clips", action="store_true",
+                    help="time every window with bursts + decode on, and with burst clips (both sources) on top; write --burst-clips-out")
+    ap.add_argument("--burst-clips-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                              "wideband_burst_clips.txt"))
     ap.add_argument("--track", action="store_true",
                     help="time every window with bursts + decode on, and with 8 expectations active in every chunk on top; write --track-out")
     ap.add_argument("--track-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
@@ -131,7 +139,10 @@ def main():
     search = args.burst_search
     if search and (args.bursts or args.burst_decode or repair or narrow or track or quality):
         raise SystemExit("--burst-search alone: each run compares two windows")
-    decode = args.burst_decode or repair > 0 or narrow or track or quality or search > 0
+    clips = args.burst_clips
+    if clips and (args.bursts or args.burst_decode or repair or narrow or track or quality or search):
+        raise SystemExit("--burst-clips alone: each run compares two windows")
+    decode = args.burst_decode or repair > 0 or narrow or track or quality or search > 0 or clips
     args.bursts = args.bursts or decode       # (everything --bursts does; the baseline window keeps bursts on)
     cfg = dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 8192)
     B, nk = cfg.block_size, args.capture_chunks
@@ -168,6 +179,7 @@ def main():
     n_narrow = [0]
     track_on, n_xmsgs, n_xcand = [False], [0], [0]
     quality_on, n_qrows, q_snr = [False], [0], []
+    clips_on, n_clips, n_clip_out, n_clip_drop, clip_kinds = [False], [0], [0], [0], [0] * 5
     # the capture's bursts lie on their channels' centres: the nearest grid point first, then its neighbours
     search_on, n_smsgs, n_shits = [False], [0], [0]
     centres = [(48 + d) % 64 for d in (0, -1, 1, -2, 2, -3, 3, -4)][:search]
@@ -199,6 +211,13 @@ def main():
                     n_qrows[0] += len(q)
                     if len(q):
                         q_snr[:] = [q]                       # (turned into decibels after the window, outside the timing)
+                if clips_on[0]:
+                    bc = rx.burst_clips()
+                    n_clips[0] += len(bc.records)
+                    n_clip_out[0] += len(bc.iq)
+                    n_clip_drop[0] += int(bc.dropped.astype(np.int64).sum())
+                    for s_ in bc.records["source"]:
+                        clip_kinds[int(s_)] += 1
                 if search_on[0]:
                     sm = rx.searched_messages()
                     n_smsgs[0] += len(sm.records)
@@ -246,7 +265,7 @@ def main():
             rx.reset()
             if args.bursts:
                 rx.set_bursts(on or decode)
-                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track or quality or search > 0)
+                rx.set_burst_decode((on and decode) or repair > 0 or narrow or track or quality or search > 0 or clips)
                 if search:
                     rx.set_burst_search(centres if on else [])
                 search_on[0] = on and search > 0
@@ -258,9 +277,14 @@ def main():
                 if quality:
                     rx.set_burst_quality(on)
                 quality_on[0] = on and quality
+                if clips:
+                    rx.set_burst_clips(*((wideband.CLIP_RUNS | wideband.CLIP_MESSAGES,) if on else (0,)))
+                clips_on[0] = on and clips
+                n_clips[0] = n_clip_out[0] = n_clip_drop[0] = 0
+                clip_kinds[:] = [0] * 5
                 n_qrows[0] = 0
                 del q_snr[:]
-                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track or quality or search > 0
+                bursts_on[0], decode_on[0] = on or decode, (on and decode) or repair > 0 or narrow or track or quality or search > 0 or clips
                 track_on[0] = on and track
                 n_dmsgs[0] = n_repaired[0] = n_right[0] = n_narrow[0] = n_xmsgs[0] = n_xcand[0] = 0
                 acq.reset()
@@ -408,6 +432,32 @@ def main():
                 f"{n_asked[0]} retunes proposed; last window without: {base_msgs[0]} burst messages",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
+        if clips:
+            res["burst_clips"] = {"clips_last_window": n_clips[0], "outputs_last_window": n_clip_out[0], "dropped_last_window": n_clip_drop[0],
+                                  "by_source_last_window": list(clip_kinds), "settings": list(rx.burst_clips_config()),
+                                  "messages_last_window": n_dmsgs[0], "messages_last_window_without": base_msgs[0]}
+            w_all_off, w_all_on = [r[0] for r in runs_off], walls
+            spread = max(max(w_all_off) - min(w_all_off), max(w_all_on) - min(w_all_on))
+            diff = wall - w_off
+            overlap = min(w_all_on) <= max(w_all_off) and min(w_all_off) <= max(w_all_on)
+            _, c_pre, c_post, c_quota = rx.burst_clips_config()
+            per_chunk = 2.0 * n_clip_out[0] / max(args.chunks, 1)
+            lines = [
+                "WidebandReceiver burst clips (k_chan_burst_clips behind k_chan_burst_decode), bursts + decode + clips on against bursts + "
+                "decode on in the same run: tools/wideband_stream.py --burst-clips" + (" --parse" if args.parse else ""),
+                lines[1] + f"; a burst on every channel; clips of runs and messages, pre {c_pre}, post {c_post}, quota {c_quota} outputs",
+                f"  bursts + decode on:          {args.chunks / w_off:8.1f} chunks/s, submit -> fetch median {np.median(l_off) * 1e3:.3f} ms",
+                f"  bursts + decode + clips on:  {res['chunks_per_s']:8.1f} chunks/s, submit -> fetch median {res['latency_ms']['median']:.3f} ms "
+                f"(burst_messages() and burst_clips() read per chunk, the messages handed to Acquisition.update)",
+                f"  all windows, wall s: decode {' '.join(f'{w:.3f}' for w in w_all_off)}; decode + clips {' '.join(f'{w:.3f}' for w in w_all_on)}",
+                f"  median window: clips {diff * 1e3:+.1f} ms of wall ({100 * diff / w_off:+.1f} %); the windows of one setting spread over "
+                f"{spread * 1e3:.1f} ms, and the windows of the two settings {'overlap: the difference lies inside' if overlap else 'do NOT overlap: the difference lies outside'} their spread",
+                f"  last window with clips: {n_clips[0]} clips (tail / run / decode / expected / searched: {' / '.join(str(v) for v in clip_kinds)}), "
+                f"{n_clip_out[0]} outputs = {per_chunk / 1024:.1f} KiB per chunk of the {rx.n_channels * 2 * B / 1024:.0f} KiB channelized "
+                f"(counted: the bytes burst_clips() handed over), {n_clip_drop[0]} requests dropped, {n_bursts[0]} burst records, {n_dmsgs[0]} burst messages; "
+                f"last window without: {base_msgs[0]} burst messages",
+                "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
+            ]
         if search:
             res["burst_search"] = {"centres": centres, "searched_messages_last_window": n_smsgs[0], "sync_hits_last_window": n_shits[0]}
             w_all_off, w_all_on = [r[0] for r in runs_off], walls
@@ -430,7 +480,7 @@ def main():
                 f"{n_dmsgs[0]} burst messages; last window without: {base_msgs[0]} burst messages",
                 "  measured: wall time per window on the host (time.perf_counter around submit / fetch), this run; the kernel's own time: not measured",
             ]
-        with open(args.burst_search_out if search else args.burst_quality_out if quality else args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
+        with open(args.burst_clips_out if clips else args.burst_search_out if search else args.burst_quality_out if quality else args.track_out if track else args.burst_narrow_out if narrow else args.burst_repair_out if repair else args.burst_decode_out if decode else args.bursts_out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
         print("\n".join(lines))
     if args.parse:
