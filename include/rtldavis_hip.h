@@ -260,6 +260,10 @@ int rd_batch_last_run_forms(rd_batch *b, uint32_t *forms);
 /* Counters of the last run: 32-sample runs with at least one 8-sample group re-evaluated
  * exactly (guard band), raw preamble matches. */
 int rd_batch_get_counters(rd_batch *b, uint64_t *fixup_runs, uint64_t *matches);
+/* The schedule of the handle's last demod launch: tiles per chunk and waves of the persistent grid (a wave takes chunk
+ * number wave first and draws further ones from the work queues when there are more chunks than waves).  b == NULL: of the
+ * last rd_debug_demod_mfma launch of this process.  For tests: results do not depend on the schedule. */
+int rd_k1_schedule(rd_batch *b, uint32_t *tiles_per_chunk, uint32_t *waves);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage functions on host arrays (caller-allocated out-params, like the reference's).

@@ -170,6 +170,7 @@ SIGNATURES = {
     "rd_batch_last_run_forms": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "rd_batch_get_timing": (C.c_int, [_P, C.POINTER(RdTiming)]),
     "rd_batch_get_counters": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rd_k1_schedule": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rd_lut_execute": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
     "rd_rotate_fs4": (C.c_int, [_P, _P, C.c_size_t]),
     "rd_fir9": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

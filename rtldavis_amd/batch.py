@@ -118,7 +118,10 @@ class BatchDemodulator:
     def counters(self) -> dict:
         f, m = C.c_uint64(), C.c_uint64()
         _lib.check(_lib.lib().rd_batch_get_counters(self._b, C.byref(f), C.byref(m)))
-        return {"fixup_runs": f.value, "matches": m.value}
+        ch, wv = C.c_uint32(), C.c_uint32()
+        _lib.check(_lib.lib().rd_k1_schedule(self._b, C.byref(ch), C.byref(wv)))
+        # k1_chunk / k1_waves: tiles per chunk and waves of the demod launch (the schedule; results do not depend on it)
+        return {"fixup_runs": f.value, "matches": m.value, "k1_chunk": ch.value, "k1_waves": wv.value}
 
     # ---- results --------------------------------------------------------------------------
     def results(self) -> np.ndarray:

@@ -540,6 +540,7 @@ extern "C" int rd_batch_run(rd_batch *b, void *hip_stream) {
         HIPCHK(hipStreamWaitEvent(st, b->done, 0));
     }
     b->stream = st;
+    const bool had_upload = b->upload_pending;
     if (b->upload_pending) {  // rd_batch_upload_async: the input is on its way
         HIPCHK(hipStreamWaitEvent(st, b->uploaded, 0));
         b->upload_pending = false;
@@ -567,16 +568,33 @@ extern "C" int rd_batch_run(rd_batch *b, void *hip_stream) {
     uint32_t *fixl = want_ft ? b->ft.fixb : b->d_fix, *bcnt = want_ft ? cnt + b->ft_cnt_off : nullptr;
     const uint32_t fixc = want_ft ? b->ft.fix_bcap : b->fix_cap;
     uint32_t honoured = 0;
+    // The launch code refused the grid (rd_demod_mfma.hip: fewer waves than work queues, more chunks than waves): nothing
+    // ran, so the handle goes back to where it was - the counter set, the pending upload, the timed-run slot - and holds
+    // no run: results() reports an error instead of an earlier run's records.  Checked before any adoption: a run waiting
+    // on this stream keeps waiting for a launch that really happens (or for its own flush).
+    auto refused = [&]() {
+        b->cnt_set ^= 1;
+        b->upload_pending = had_upload;
+        if (b->timing) b->ev_runs--;
+        b->ran = false;
+        b->fetched = true;
+        return fail(RD_ERR_STATE, "the demod kernel's grid has fewer waves than work queues and more chunks than waves: not launched");
+    };
     if (b->timing && b->fast_ok) {
         // the demod kernel's dispatch carries its own start / stop events (no marker packets)
         honoured = rd_launch_demod(lay, fixl, fixc, cnt, st, b->ev[0], b->ev[1], dflags, b->last_launch, bcnt);
+        if (honoured & RD_DEMOD_REFUSED) return refused();
         if (adopt && (rc = batch_adopt(b->device, st, b->ev[1]))) return rc;
     } else if (b->fast_ok && adopt) {
         honoured = rd_launch_demod(lay, fixl, fixc, cnt, st, nullptr, b->kfirst, dflags, b->last_launch, bcnt);
+        if (honoured & RD_DEMOD_REFUSED) return refused();
         if ((rc = batch_adopt(b->device, st, b->kfirst))) return rc;
     } else {
-        if (b->timing) HIPCHK(hipEventRecord(b->ev[0], st));
-        if (b->fast_ok) honoured = rd_launch_demod(lay, fixl, fixc, cnt, st, nullptr, nullptr, dflags, b->last_launch, bcnt);
+        if (b->timing) HIPCHK(hipEventRecord(b->ev[0], st));   // (timed and no fast kernel: the launch below does not happen)
+        if (b->fast_ok) {
+            honoured = rd_launch_demod(lay, fixl, fixc, cnt, st, nullptr, nullptr, dflags, b->last_launch, bcnt);
+            if (honoured & RD_DEMOD_REFUSED) return refused();
+        }
         if (b->timing) HIPCHK(hipEventRecord(b->ev[1], st));
         if (adopt) {  // (an event of THIS run: b->ev is null - or a finished run's - when the handle is untimed)
             hipEvent_t carrier = b->timing ? b->ev[1] : b->kfirst;
@@ -885,6 +903,19 @@ extern "C" int rd_batch_last_run_forms(rd_batch *b, uint32_t *forms) {
     int rc = batch_finish(b);
     if (rc) return rc;
     *forms = (b->dev_order ? RD_FORM_ORDERED_TAIL | RD_FORM_ONE_LAUNCH_TAIL : 0u) | (b->second_pass ? RD_FORM_SECOND_PASS : 0u);
+    return RD_OK;
+}
+
+extern "C" int rd_k1_schedule(rd_batch *b, uint32_t *tiles_per_chunk, uint32_t *waves) {
+    uint32_t v[2] = {0, 0};
+    if (b) {
+        if (!b->ran) return fail(RD_ERR_STATE, "rd_batch_run has not been called");
+        v[0] = b->last_launch[0]; v[1] = b->last_launch[1];
+    } else {
+        rd_debug_last_launch(v);
+    }
+    if (tiles_per_chunk) *tiles_per_chunk = v[0];
+    if (waves) *waves = v[1];
     return RD_OK;
 }
 
@@ -1414,7 +1445,8 @@ static int demod_submit(rd_demod *h, const void *samples, int is_complex, long e
     HIPCHK(hipMemsetAsync(h->d_cnt, 0, RD_CNT_TOTAL * 4, st));
     if (!h->cplx_mode) {
         const rd_layout lay = demod_layout(h, seen_before);
-        if (h->fast_ok) rd_launch_demod(lay, h->d_fix, h->fix_cap, h->d_cnt, st);
+        if (h->fast_ok && (rd_launch_demod(lay, h->d_fix, h->fix_cap, h->d_cnt, st) & RD_DEMOD_REFUSED))
+            return fail(RD_ERR_STATE, "the demod kernel's grid has fewer waves than work queues and more chunks than waves: not launched");
         rd_launch_fixup(lay, h->d_fix, h->fix_cap, h->d_cnt, h->fast_ok ? 0 : 1, nullptr, st);
     } else {
         rd_launch_cplx_bits(demod_clayout(h, seen_before), h->d_blockbits, st);

@@ -759,11 +759,15 @@ static int rd_mf_env(const char *name, int dflt) {
 // Launch parameters read once per process.  A function-local static: initialised exactly once, also when several
 // threads make their first launch together (handles may be used from several threads, rd_api.hip).
 struct rd_mf_params {
-    int dbg = 0, stamp = 0, chunk_env = 0, per_cu_env = 0, n_cu = 256;
+    int dbg = 0, stamp = 0, chunk_env = 0, per_cu_env = 0, n_cu = 256, test_wgs = 0;
     uint32_t stflags = 0;
     rd_mf_params() {
         chunk_env = rd_mf_env("RD_K1_CHUNK", 0);          // tuning knobs: results do not depend on them
         per_cu_env = rd_mf_env("RD_K1_WGS_PER_CU", 0);
+        // test hook: at most this many workgroups, so that small inputs give every wave several chunks and the work
+        // queues run (tests/test_k1_schedule.py).  Never below RD_NQUEUE waves: see the invariant in rd_mf_launch_variant
+        test_wgs = rd_mf_env("RD_TEST_K1_WGS", 0);
+        if (test_wgs > 0 && test_wgs < RD_NQUEUE / RD_MF_WAVES) test_wgs = RD_NQUEUE / RD_MF_WAVES;
 #ifdef RD_DIAG
         // timing ablations and A/B switches, wrong results for most of them: the diagnostic library only
         dbg = rd_mf_env("RD_K1_DEBUG", 0);
@@ -814,8 +818,9 @@ struct rd_mf_launch_args {
     float *dbg_g;
 };
 
+// false: nothing was launched (the grid cannot serve every work queue, see below)
 template <int D, bool STAMP>
-static void rd_mf_launch_variant(const rd_mf_launch_args &a) {
+static bool rd_mf_launch_variant(const rd_mf_launch_args &a) {
     const rd_mf_params &P = rd_mf_get_params();
     // persistent grid sized from the occupancy API (registers and LDS of the variant actually launched)
     static const int per_cu_occ = [] {
@@ -832,7 +837,10 @@ static void rd_mf_launch_variant(const rd_mf_launch_args &a) {
     // fix-up list grows (a chunk's first group is always listed: 0.23 % of the runs against 0.13 %) and k_tail with it by
     // 4 us - the step is 1 % shorter.  With equal shares (RD_K1_STFLAGS & 4096) 28 (profiles/r02_chunk_sweep.txt).
     // A small workload gets shorter chunks, down to one store group, until every resident wave has one.
-    uint32_t chunk = P.chunk_env > 0 ? (uint32_t)P.chunk_env : ((P.stflags & 4096) ? 28 : 8);
+    // RD_K1_CHUNK=1 is raised to 2: the kernel works out the tile after next before it has noted that the next one entered
+    // a new chunk, and with one tile per chunk every wave would take its second chunk twice - the same words stored again,
+    // every entry of those tiles listed twice (tests/test_k1_schedule.py at RD_K1_CHUNK=1)
+    uint32_t chunk = P.chunk_env > 0 ? (uint32_t)(P.chunk_env < 2 ? 2 : P.chunk_env) : ((P.stflags & 4096) ? 28 : 8);
     if (P.chunk_env <= 0) {
         const uint64_t waves = (uint64_t)P.n_cu * per_cu * RD_MF_WAVES;
         while (chunk > RD_MF_STAGE_TILES && a.total64 / chunk < waves) chunk -= RD_MF_STAGE_TILES;
@@ -840,8 +848,17 @@ static void rd_mf_launch_variant(const rd_mf_launch_args &a) {
     if (chunk > a.total) chunk = a.total;
     const uint64_t chunks = (a.total64 + chunk - 1) / chunk;
     uint64_t wgs = (chunks + RD_MF_WAVES - 1) / RD_MF_WAVES;
-    const uint64_t max_wgs = (uint64_t)P.n_cu * per_cu;
+    uint64_t max_wgs = (uint64_t)P.n_cu * per_cu;
+    if (P.test_wgs > 0 && (uint64_t)P.test_wgs < max_wgs) max_wgs = (uint64_t)P.test_wgs;  // RD_TEST_K1_WGS
     if (wgs > max_wgs) wgs = max_wgs;
+    // Invariant of the work queues: nwaves >= RD_NQUEUE || chunks <= nwaves.  Wave w draws from queue w % RD_NQUEUE only, so
+    // with fewer waves than queues the chunks of the queues nobody draws from would never be processed - unless there are
+    // none beyond every wave's first.  (Equal shares - chunks of fewer than four tiles, RD_K1_STFLAGS & 4096 - use no queue.)
+    {
+        const uint64_t nwaves = wgs * RD_MF_WAVES;
+        const bool queues = !(P.stflags & 4096) && chunk >= 4;
+        if (queues && !(nwaves >= RD_NQUEUE || chunks <= nwaves)) return false;
+    }
     float *dbg = a.dbg_g;
     uint32_t stf = P.stflags;
     if (a.bucket_cnt && D == 0 && !STAMP) { dbg = (float *)a.bucket_cnt; stf |= RD_STF_BUCKETS; }
@@ -864,11 +881,13 @@ static void rd_mf_launch_variant(const rd_mf_launch_args &a) {
     else
         hipLaunchKernelGGL((k_demod_mfma<D, STAMP>), dim3((unsigned)wgs), dim3(RD_MF_WG), 0, a.st, a.lay, a.tps, a.total,
                            chunk, a.fix_list, a.fix_cap, a.counters, dbg, stf);
+    return true;
 }
 
-// Returns false when the fix-up entries went to the one global list although buckets were asked for (the stamped and
-// ablated variants of the diagnostic library keep the list): the caller then launches k_fixup as before.
-bool rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
+// Returns 0 when the fix-up entries went to the one global list although buckets were asked for (the stamped and
+// ablated variants of the diagnostic library keep the list): the caller then launches k_fixup as before.  1: they went
+// to the buckets.  -1: nothing was launched (rd_mf_launch_variant's invariant).
+int rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                           hipEvent_t ev_start, hipEvent_t ev_stop, float *dbg_g, uint32_t flags, uint32_t *chunk_out,
                           uint32_t *bucket_cnt) {
     rd_mf_launch_args a;
@@ -877,37 +896,40 @@ bool rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix
     a.lay = lay;
     a.tps = (lay.n_samples + RD_TILE_SAMPLES - 1) / RD_TILE_SAMPLES;
     a.total64 = (uint64_t)lay.n_streams * a.tps;
-    if (a.total64 == 0) return a.bucket_cnt != nullptr;
+    if (a.total64 == 0) return a.bucket_cnt != nullptr ? 1 : 0;
     a.total = (uint32_t)a.total64;
     a.fix_list = fix_list; a.fix_cap = fix_cap; a.counters = counters;
     a.st = st; a.ev_start = ev_start; a.ev_stop = ev_stop; a.dbg_g = dbg_g;
     if (dbg_g) {  // the test hook: raw filter outputs as well
-        rd_mf_launch_variant<3, false>(a);
-        return false;
+        return rd_mf_launch_variant<3, false>(a) ? 0 : -1;
     }
 #ifdef RD_DIAG
     const rd_mf_params &P = rd_mf_get_params();
     if (P.stamp || P.dbg) {
         a.bucket_cnt = nullptr;   // (these variants keep the one fix-up list: the caller runs k_fixup on it, bounded by fix_cap)
-        if (P.stamp && P.dbg == 0) { rd_mf_launch_variant<0, true>(a); return false; }
+        if (P.stamp && P.dbg == 0) return rd_mf_launch_variant<0, true>(a) ? 0 : -1;
         switch (P.dbg) {
-            case 1: rd_mf_launch_variant<1, false>(a); return false;
-            case 2: rd_mf_launch_variant<2, false>(a); return false;
-            case 6: rd_mf_launch_variant<6, false>(a); return false;
-            case 7: rd_mf_launch_variant<7, false>(a); return false;
-            case 8: rd_mf_launch_variant<8, false>(a); return false;
-            case 9: rd_mf_launch_variant<9, false>(a); return false;
-            case 10: rd_mf_launch_variant<10, false>(a); return false;
-            case 11: rd_mf_launch_variant<11, false>(a); return false;
+            case 1: return rd_mf_launch_variant<1, false>(a) ? 0 : -1;
+            case 2: return rd_mf_launch_variant<2, false>(a) ? 0 : -1;
+            case 6: return rd_mf_launch_variant<6, false>(a) ? 0 : -1;
+            case 7: return rd_mf_launch_variant<7, false>(a) ? 0 : -1;
+            case 8: return rd_mf_launch_variant<8, false>(a) ? 0 : -1;
+            case 9: return rd_mf_launch_variant<9, false>(a) ? 0 : -1;
+            case 10: return rd_mf_launch_variant<10, false>(a) ? 0 : -1;
+            case 11: return rd_mf_launch_variant<11, false>(a) ? 0 : -1;
             default:
                 fprintf(stderr, "[rd diag] no kernel variant RD_K1_DEBUG=%d RD_K1_STAMPS=%d is compiled in\n", P.dbg, P.stamp);
                 abort();
         }
     }
 #endif
-    rd_mf_launch_variant<0, false>(a);
-    return a.bucket_cnt != nullptr;
+    if (!rd_mf_launch_variant<0, false>(a)) return -1;
+    return a.bucket_cnt != nullptr ? 1 : 0;
 }
+
+// tiles per chunk and waves of the hook's last launch (rd_api.hip: rd_k1_schedule with a null handle)
+static uint32_t g_dbg_launch[2] = {0, 0};
+void rd_debug_last_launch(uint32_t out[2]) { out[0] = g_dbg_launch[0]; out[1] = g_dbg_launch[1]; }
 
 // Test hook (tests/test_gpu_mfma.py): run the kernel on host data, return the raw filter outputs g
 // (tile-major, [tiles][2048][2] floats in the kernel's units), the packed bits BEFORE any fix-up and
@@ -951,7 +973,11 @@ extern "C" int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32
         lay.valid_from = hist_mode ? -(long)(hist_bytes / 2) : 0;
         lay.bits = d_bits;
         lay.bits_stride = words;
-        rd_launch_demod_mfma(lay, d_fix, fix_cap, d_cnt, nullptr, nullptr, nullptr, d_g);
+        g_dbg_launch[0] = g_dbg_launch[1] = 0;
+        if (rd_launch_demod_mfma(lay, d_fix, fix_cap, d_cnt, nullptr, nullptr, nullptr, d_g, 0, g_dbg_launch) < 0) {
+            rc = RD_ERR_STATE;
+            goto out;
+        }
     }
     RD_DBG_CHK(hipDeviceSynchronize());
     if (g_out) RD_DBG_CHK(hipMemcpy(g_out, d_g, g_floats * 4, hipMemcpyDeviceToHost));

@@ -68,14 +68,19 @@ int rd_ensure_device_public(void);
 // flags: RD_DEMOD_FIX_BUCKETS with bucket_cnt (the groups' entry counters; fix_list = [groups][fix_cap] then).  Returns the
 // flags the launched kernel honoured (the ablated kernels of the diagnostic library keep the one list: none).
 // chunk_out: receives the tiles per chunk the launch used and the number of waves
+// RD_DEMOD_REFUSED in the result: nothing was launched (rd_launch_demod_mfma's -1); the caller reports an error.
+#define RD_DEMOD_REFUSED 0x80000000u
 uint32_t rd_launch_demod(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, uint32_t flags = 0,
                          uint32_t *chunk_out = nullptr, uint32_t *bucket_cnt = nullptr);
 // The kernel itself (rd_demod_mfma.hip).  dbg_g (test hook): when given, the kernel also dumps g[tile][2048][2].
-// Returns true when the fix-up entries went to the buckets.
-bool rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
+// Returns 1 when the fix-up entries went to the buckets, 0 when they went to the one list, -1 when nothing was launched
+// (the grid could not serve every work queue: rd_demod_mfma.hip, rd_mf_launch_variant).
+int rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, float *dbg_g = nullptr,
                           uint32_t flags = 0, uint32_t *chunk_out = nullptr, uint32_t *bucket_cnt = nullptr);
+// the test hook's last launch (rd_debug_demod_mfma): tiles per chunk, waves
+void rd_debug_last_launch(uint32_t out[2]);
 // all != 0: re-evaluate every run exactly (used when the guard list overflowed or the
 // layout does not meet the fast kernel's alignment requirements).
 // zero_next (may be null): RD_CNT_TOTAL words (counters and work queues) to clear for the handle's next run.

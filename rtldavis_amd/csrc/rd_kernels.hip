@@ -26,7 +26,8 @@
 uint32_t rd_launch_demod(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_cap, uint32_t *counters, hipStream_t st,
                          hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t flags, uint32_t *chunk_out, uint32_t *bucket_cnt) {
     if (!bucket_cnt) flags &= ~RD_DEMOD_FIX_BUCKETS;
-    const bool bucketed = rd_launch_demod_mfma(lay, fix_list, fix_cap, counters, st, ev_start, ev_stop, nullptr, flags, chunk_out, bucket_cnt);
+    const int bucketed = rd_launch_demod_mfma(lay, fix_list, fix_cap, counters, st, ev_start, ev_stop, nullptr, flags, chunk_out, bucket_cnt);
+    if (bucketed < 0) return RD_DEMOD_REFUSED;
     return bucketed ? RD_DEMOD_FIX_BUCKETS : 0u;
 }
 

@@ -385,6 +385,9 @@ def _evaluate(c: Case, **mutant) -> Case:
     return c
 
 
+evaluate = _evaluate   # (for other case modules)
+
+
 def margin_ok(c: Case) -> bool:
     lm = c.lane
     bad = np.abs(lm.nm.astype(np.float64) - lm.thr) <= MARGIN * lm.thr
@@ -417,6 +420,21 @@ class _Pool:
         k = (r, kind)
         self.at[k] += 1
         return self.win[k][self.at[k] % len(self.win[k])]
+
+
+def plant(streams, slots, rng, lo, hi, reuse=1):
+    """The planting routine (also for other case modules: tests/k1_schedule_cases.py).  slots: (s, t, kind) with t >= 10,
+    t + 2 inside the stream and no two of a stream closer than 16 samples; sample t of stream s becomes a near-tie of class
+    `kind` with bytes in lo .. hi - samples t - 10 .. t + 2 of `streams` are overwritten in place.  Returns the plants."""
+    pool = _Pool(rng, lo, hi)
+    for s, t, k in slots:
+        pool.want(t % 4, k)
+    pool.draw(reuse)
+    plants = []
+    for s, t, k in slots:
+        _put(streams, s, t, t % 4, pool.take(t % 4, k))
+        plants.append(Plant(s, t, k))
+    return plants
 
 
 def _positions(rng, amp, ns=8, n=7 * TILE + 1000, hist=False, kinds=KINDS):
@@ -456,15 +474,7 @@ def _positions(rng, amp, ns=8, n=7 * TILE + 1000, hist=False, kinds=KINDS):
     for s in range(ns):
         ts = sorted(t for s_, t, _ in slots if s_ == s)
         assert all(b - a >= 16 for a, b in zip(ts, ts[1:])), (s, [b - a for a, b in zip(ts, ts[1:]) if b - a < 16])
-    pool = _Pool(rng, lo, hi)
-    for s, t, k in slots:
-        pool.want(t % 4, k)
-    pool.draw()
-    plants = []
-    for s, t, k in slots:
-        _put(streams, s, t, t % 4, pool.take(t % 4, k))
-        plants.append(Plant(s, t, k))
-    return streams, h, plants
+    return streams, h, plant(streams, slots, rng, lo, hi)
 
 
 def _dense(rng, amp, ns=8, tiles=4, counts=None):
@@ -484,15 +494,7 @@ def _dense(rng, amp, ns=8, tiles=4, counts=None):
                 t = ti * TILE + 32 * int(wd) + 12 + int(rng.integers(0, 20))
                 kind = ("deep", "band")[int(rng.integers(0, 2))]   # half of them deep inside: many wrong fast signs
                 slots.append((s, t, kind))
-    pool = _Pool(rng, lo, hi)
-    for s, t, k in slots:
-        pool.want(t % 4, k)
-    pool.draw(reuse=1 if counts is not None else 4)
-    plants = []
-    for s, t, k in slots:
-        _put(streams, s, t, t % 4, pool.take(t % 4, k))
-        plants.append(Plant(s, t, k))
-    return streams, None, plants
+    return streams, None, plant(streams, slots, rng, lo, hi, reuse=1 if counts is not None else 4)
 
 
 PARTIAL_COUNTS = [[0, 31, 32, 33, 64], [0, 33, 64, 32, 31]]   # model-flagged words per tile of dense_partial's two streams

@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 
 def run_kernel(streams: np.ndarray, hist: np.ndarray | None = None, want_g: bool = True):
-    """want_g = False: the hook launches the instantiation the product uses (no dump of g); g comes back as None."""
+    """want_g = False: the hook launches the instantiation the product uses (no dump of g); g comes back as None.
+    Returns (g, bits, fix, schedule): schedule = {"k1_chunk", "k1_waves"}, the tiles per chunk and the waves of the launch."""
     ns, nbytes = streams.shape
     n = nbytes // 2
     if hist is None:
@@ -38,7 +39,9 @@ def run_kernel(streams: np.ndarray, hist: np.ndarray | None = None, want_g: bool
                                         fix.ctypes.data, cap, C.byref(nfix))
     _lib.check(rc)
     assert nfix.value <= cap
-    return g, bits, fix[: nfix.value]
+    ch, wv = C.c_uint32(), C.c_uint32()
+    _lib.check(_lib.lib().rd_k1_schedule(None, C.byref(ch), C.byref(wv)))
+    return g, bits, fix[: nfix.value], {"k1_chunk": ch.value, "k1_waves": wv.value}
 
 
 def flagged_groups(fix: np.ndarray, ns: int, words: int) -> np.ndarray:
@@ -54,7 +57,7 @@ def flagged_groups(fix: np.ndarray, ns: int, words: int) -> np.ndarray:
 
 def check(streams: np.ndarray, hist=None, chunk=6, want_g=True, want_bits=False):
     """want_bits: also return the packed words (tests/test_gpu_near_ties.py goes on from them)"""
-    g, bits, fix = run_kernel(streams, hist, want_g)
+    g, bits, fix, _ = run_kernel(streams, hist, want_g)
     ns, n = streams.shape[0], streams.shape[1] // 2
     words = (n + 31) // 32
     fl = flagged_groups(fix, ns, words)
