@@ -644,7 +644,8 @@ typedef struct rd_burst_msg {
                                 bit 2 (RD_BURST_MSG_NARROW): step 4n; bit 3 (RD_BURST_MSG_EXPECTED): a record of BURST EXPECT,
                                 whose bit 0 says that the region began before the chunk; bit 4 (RD_BURST_MSG_SEARCHED): a
                                 record of BURST SEARCH, whose bit 0 says that the packet began before the chunk, `first` is
-                                the centre's index in the list and pad = (hits, 0, 0, g) */
+                                the centre's index in the list and pad = (hits, 0, 0, g); bit 5 (RD_BURST_MSG_REPLAYED): a
+                                record of CLIP DECODE, `first` is the job's index */
     uint64_t time;           /* the chunk's absolute output clock + tau */
     uint64_t margin;         /* min_i |s[tau + SL i]|, for a repaired record over the symbols that were not flipped; in
                                 the units of step 4n when bit 2 is set: not comparable across the two kinds */
@@ -931,6 +932,70 @@ int rd_wb_burst_clips(rd_wideband *w, rd_burst_clip *out, int cap, int *n, uint8
 /* The clamp of one request, on the host (no device is touched): out = { t0, n, flags }.  Returns 1, or 0 with out zeroed for
  * a request that gives no clip (or a null out, or a block_size that is no positive multiple of 8). */
 int rd_bc_window(int block_size, int have_prev, int64_t a, int64_t e, int32_t *out);
+/* CLIP DECODE (k_clip_decode, rd_clip_decode.hip): decode RECORDED clips, many per launch.  BURST CLIPS brings the
+ * channelized IQ of every burst home; this section asks of such bytes what a live chunk can be asked only once: would
+ * this burst have decoded with the filter on, with two flips, around another direction?  No receiver, no channelizer and
+ * no chunk are involved.  A POOL is a byte array of channelized IQ (cu8: I, Q per output) that rd_clips_upload copies to
+ * the device; a JOB (rd_clip_job) names a clip in it - `n` outputs from output `offset` - and the places to test.  One
+ * launch takes up to 2^20 jobs, one workgroup each.  All quantities are exact integers.
+ * Semantics: those of BURST EXPECT with the clip taken as a chunk of its own - B = n, clock K = job.clock,
+ * have_prev = 0, the expectation (channel, id, t_lo = K + tau_lo, t_hi = K + tau_hi, corr).  B need not be a multiple of 8
+ * or of 128, nor reach LOOK.  Written out: the candidates are tau_a = max(tau_lo, SL) .. tau_b = min(tau_hi, n - 1 -
+ * SL (N - 1)).  None: the job is idle - no record, and its header reads { 0, 0, 0, 0 }.  Otherwise t0 = tau_a - SL,
+ * t1 = tau_b + SL (N - 1) + 1 (0 <= t0, t1 <= n, t1 - t0 <= 4096); with the filter on zf0 = max(t0 - M, 0), zf1 =
+ * min(t1 + M, n): the filter sees the clip's real samples where the clip holds them and zeros outside the clip.
+ * Steps 4 / 4n, 5, 5a, 5b, 6 / 6' and the id rule of BURST EXPECT run as written, over tau_a .. tau_b only.
+ *   Own direction, corr = (0, 0): F = the sum of p[t] over t0 < t < t1 - unfiltered, from the bytes of the job's region,
+ *   exact, components below 4096 x 2 x 255^2 < 2^30; sh = max(0, bitlength(max(|F.re|, |F.im|)) - 15), ca = F.re >> sh,
+ *   cb = F.im >> sh (arithmetic shifts, as in step 4n).  ca = cb = 0 (F = (0, 0)): candidates is still counted, and there
+ *   is no record.  Otherwise (ca, cb) takes the place of corr everywhere, the choice of g included.
+ *   At most one record per job, a rd_burst_msg: flags = RD_BURST_MSG_REPLAYED | repaired | narrow - bit 0 and bit 3 are
+ *   never set -, first = the job's index, channel = job.channel, tau relative to the clip's output 0, time = clock + tau;
+ *   every other field as for an expected record.
+ *   Header per job: { n_msgs (0 / 1), candidates = tau_b - tau_a + 1, ca, cb = the direction that was used, given or own }.
+ *   Soft values: for a job with a record soft[j][k] = s[tau + SL k], k < N, of the winning tau, before any flip (in the
+ *   units of step 4n behind the filter); zeros for a job without a record.
+ * Isolation: no byte outside outputs 0 .. n - 1 of a job's clip influences that job's record, header or soft values -
+ * the 16-byte loads may touch the 7 outputs past a clip whose n is no multiple of 8, and nothing reads what they bring.
+ * The same pool and jobs give the same bits on every run; the order of the jobs and a clip's neighbours change nothing.
+ * Out of scope: a replay of BURST SEARCH (its per-position direction is another algorithm, and noise chunks stream
+ * through the live search at thousands of chunks per second), the figures of BURST QUALITY, and more than one record per
+ * job (rtldavis_amd/replay.py tiles a long recording with jobs instead).
+ * rd_clips_create: RD_ERR_ARG for a configuration that rd_wb_set_burst_decode refuses, except the block_size rule -
+ * block_size is ignored here.  No device work (safe before fork).
+ * rd_clips_upload: the pool (nbytes even, at least 2), copied to the device and kept until the next upload.
+ * rd_clips_decode: synchronous, its wait under the deadline of every host wait (RD_WAIT_TIMEOUT_MS).  Any number of
+ * calls on one uploaded pool.  msgs[n_jobs] and hdr[n_jobs]: row j is job j, zeros where there is no record / the job is
+ * idle; soft: NULL, or [n_jobs][N].  RD_ERR_ARG, with nothing launched, for max_flips outside 0 .. 2, narrow other than
+ * 0 / 1 or with symbol_length < 4, n_jobs outside 1 .. RD_CD_MAX_JOBS, a null pointer, and any job rd_cd_check_jobs
+ * refuses; RD_ERR_STATE before any upload.  rd_clips_kernel_ms: the kernel time of the last decode, by device events.
+ * rd_cd_check_jobs (no device is touched): RD_OK, or RD_ERR_ARG with *bad = the first offending job (-1: n_jobs itself or
+ * a null pointer) and *why naming the rule - offset % 8 != 0, n < 1, offset + n past the pool's pool_outputs, tau_lo >
+ * tau_hi, tau_hi - tau_lo > RD_CD_MAX_SPAN, |tau_lo| or |tau_hi| above 2^30, an id that is neither below 8 nor
+ * RD_BX_ANY_ID, a corr component outside -2^15 .. 2^15-1, pad != 0.  A job that merely has no candidate is legal and idle. */
+#define RD_BURST_MSG_REPLAYED 32u   /* rd_burst_msg.flags bit 5: a record of CLIP DECODE; `first` is the job's index */
+#define RD_CD_MAX_SPAN 2048         /* tau_hi - tau_lo at most (= RD_BX_MAX_SPAN) */
+#define RD_CD_MAX_JOBS (1 << 20)    /* jobs per call */
+#define RD_CD_MAX_TAU (1 << 30)     /* |tau_lo|, |tau_hi| at most */
+typedef struct rd_clip_job {
+    uint64_t offset;             /* the clip's first output in the pool, in outputs; a multiple of 8 */
+    uint64_t clock;              /* absolute output clock of the clip's output 0 (Recording.time); time = clock + tau */
+    uint32_t n;                  /* outputs in the clip, any number >= 1 */
+    uint32_t id;                 /* 0 .. 7, or RD_BX_ANY_ID */
+    int32_t  tau_lo, tau_hi;     /* candidate range, inclusive, relative to the clip's output 0 */
+    int32_t  corr_re, corr_im;   /* direction to slice around, each in -2^15 .. 2^15-1; (0, 0): the clip's own */
+    int32_t  channel;            /* copied into the record */
+    uint32_t pad;                /* 0 */
+} rd_clip_job;
+typedef struct rd_cd_header { uint32_t n_msgs, candidates; int32_t ca, cb; } rd_cd_header;
+typedef struct rd_clips rd_clips;
+int rd_clips_create(const rd_config *cfg, rd_clips **out);
+void rd_clips_destroy(rd_clips *h);
+int rd_clips_upload(rd_clips *h, const uint8_t *pool, size_t nbytes);
+int rd_clips_decode(rd_clips *h, const rd_clip_job *jobs, int n_jobs, int max_flips, int narrow, rd_burst_msg *msgs,
+                    rd_cd_header *hdr, int64_t *soft);
+int rd_clips_kernel_ms(rd_clips *h, float *ms);
+int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, int n_jobs, size_t pool_outputs, int *bad, const char **why);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
  * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */

@@ -10,10 +10,12 @@ capture chunk by chunk.  The streaming forms can run ``protocol.Parser.parse``'s
 ``WidebandReceiver.set_burst_quality`` measures every burst message's power and noise on the device, and
 ``rtldavis_amd.burst_packets`` turns the rows into ``dsp.Packet``s with ``rssi`` and ``snr`` for ``protocol.Parser.parse``.
 ``WidebandReceiver.set_burst_clips`` records the channelized IQ of every burst on the device; ``rtldavis_amd.clips``
-(``ClipStitcher``, ``write_sigmf``, ``read_sigmf``) turns the clips into SigMF ``cu8`` recordings.
+(``ClipStitcher``, ``write_sigmf``, ``read_sigmf``) turns the clips into SigMF ``cu8`` recordings, and
+``rtldavis_amd.ClipDecoder`` (``rtldavis_amd.replay``) decodes such recordings again on the device, thousands per launch,
+under any of the decoder's forms.
 """
 __all__ = ["dsp", "batch", "synth", "wideband", "track", "clips", "WidebandReceiver", "parse_packet", "burst_packets",
-           "ClipStitcher", "Recording", "write_sigmf", "read_sigmf"]
+           "ClipStitcher", "Recording", "write_sigmf", "read_sigmf", "replay", "ClipDecoder"]
 
 import os as _os
 
@@ -52,6 +54,9 @@ def __getattr__(name):
     if name in ("ClipStitcher", "Recording", "write_sigmf", "read_sigmf"):
         from . import clips
         return getattr(clips, name)
+    if name == "ClipDecoder":
+        from .replay import ClipDecoder
+        return ClipDecoder
     if name == "parse_packet":
         from .dsp import parse_packet
         return parse_packet

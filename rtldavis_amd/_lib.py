@@ -233,6 +233,12 @@ SIGNATURES = {
     "rd_wb_burst_clips_config": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rd_wb_burst_clips": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_int]),
     "rd_bc_window": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "rd_clips_create": (C.c_int, [C.POINTER(RdConfig), C.POINTER(_P)]),
+    "rd_clips_destroy": (None, [_P]),
+    "rd_clips_upload": (C.c_int, [_P, _P, C.c_size_t]),
+    "rd_clips_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rd_clips_kernel_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "rd_cd_check_jobs": (C.c_int, [C.POINTER(RdConfig), _P, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),

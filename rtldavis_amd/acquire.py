@@ -50,6 +50,7 @@ MSG_REPAIRED = 2             # wideband.BURST_MSG_REPAIRED: bit 1 of a burst mes
 MSG_NARROW = 4               # wideband.BURST_MSG_NARROW: bit 2
 MSG_EXPECTED = 8             # wideband.BURST_MSG_EXPECTED: bit 3
 MSG_SEARCHED = 16            # wideband.BURST_MSG_SEARCHED: bit 4
+MSG_REPLAYED = 32            # replay.REPLAYED: bit 5
 SEARCH_GRID = 64             # wideband.BURST_NARROW_GRID: a centre is g / 64 cycles per output
 
 
@@ -106,6 +107,14 @@ def searched(records) -> np.ndarray:
     none of the others.  Such a row proves less than any other (``WidebandReceiver.searched_messages``)."""
     recs = np.asarray(getattr(records, "records", records))
     return (recs["flags"] & MSG_SEARCHED) != 0
+
+
+def replayed(records) -> np.ndarray:
+    """Boolean mask over message rows (or anything with ``records``): the rows that ``replay.ClipDecoder`` decoded from a
+    recording (``flags`` bit 5; ``first`` is the job's index) - all of a ``Replay``'s rows with a message, none of a
+    receiver's."""
+    recs = np.asarray(getattr(records, "records", records))
+    return (recs["flags"] & MSG_REPLAYED) != 0
 
 
 def search_hits(records) -> np.ndarray:

@@ -8,7 +8,7 @@
 // compiled as if it held the phases itself, and the pointers keep their LDS address space.  No phase ends in a barrier
 // unless it says so.
 //   rd_bd_syndrome_table   E[k] of the repair into LDS                                  decode, expect
-//   rd_bd_load_bytes       region bytes -> LDS, 16-byte vectors, seam into chunk k-1    decode, expect, quality
+//   rd_bd_load_bytes       region bytes -> LDS, 16-byte vectors, seam into chunk k-1    decode, expect, quality, clip decode
 //   rd_bd_grid_choice      g of step 4n: 64 centres, a fixed tree of shuffles           decode, expect, quality
 //   rd_bd_load_taps        the taps of H[g] as the two int16 pairs a product wants      decode, expect, search, quality
 //   rd_bd_fill_z16         z as int16 pairs, zeros outside zf0 .. zf1                   decode, expect, quality
@@ -103,12 +103,14 @@ __device__ __forceinline__ void rd_bd_syndrome_table(uint16_t *s_E, int n_sym, u
 }
 
 // The bytes of outputs L0 .. L1 - 1 as they lie, output L0 + i at bytes 2 i, 2 i + 1 of s_z; t < 0 is output t + n_out of
-// the chunk before.  L0, L1 and n_out are multiples of 8: a 16-byte vector lies in one chunk.
+// the chunk before.  L0, L1 and n_out are multiples of 8: a 16-byte vector lies in one chunk.  SEAM = false is the form
+// for bytes that have no chunk before (L0 >= 0; the clip decoder's): src_prev and n_out are not looked at.
+template <bool SEAM = true>
 __device__ __forceinline__ void rd_bd_load_bytes(uint4 *s_z, const uint8_t *src, const uint8_t *src_prev, int L0, int L1, long n_out,
                                                  unsigned tid) {
     for (int v = (int)tid; v < (L1 - L0) / 8; v += RD_BURST_THREADS) {
         const int t = L0 + 8 * v;
-        const uint8_t *g = t < 0 ? src_prev + 2 * ((long)t + n_out) : src + 2 * (long)t;
+        const uint8_t *g = SEAM && t < 0 ? src_prev + 2 * ((long)t + n_out) : src + 2 * (long)t;
         s_z[v] = *(const uint4 *)g;
     }
 }

@@ -299,6 +299,37 @@ bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
     return false;
 }
 
+// CLIP DECODE (include/rtldavis_hip.h): the rules of a job list.  cfg takes no part in them today - a job that has no
+// candidate for its SL and N is legal and idle - and is there so that a rule that needs it changes no signature.
+extern "C" int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, int n_jobs, size_t pool_outputs, int *bad,
+                                const char **why) {
+    static const char *none = "";
+    const char *dummy_why;
+    int dummy_bad;
+    if (!why) why = &dummy_why;
+    if (!bad) bad = &dummy_bad;
+    *why = none;
+    *bad = -1;
+    if (!cfg) { *why = "null configuration"; return RD_ERR_ARG; }
+    if (n_jobs < 1 || n_jobs > RD_CD_MAX_JOBS) { *why = "the number of jobs (1 .. 2^20)"; return RD_ERR_ARG; }
+    if (!jobs) { *why = "null job list"; return RD_ERR_ARG; }
+    for (int i = 0; i < n_jobs; i++) {
+        const rd_clip_job &j = jobs[i];
+        *bad = i;
+        if (j.offset % 8u) { *why = "offset (a multiple of 8)"; return RD_ERR_ARG; }
+        if (j.n < 1u) { *why = "n < 1"; return RD_ERR_ARG; }
+        if (j.offset > (uint64_t)pool_outputs || (uint64_t)j.n > (uint64_t)pool_outputs - j.offset) { *why = "offset + n past the pool"; return RD_ERR_ARG; }
+        if (j.tau_lo > j.tau_hi) { *why = "tau_lo > tau_hi"; return RD_ERR_ARG; }
+        if ((int64_t)j.tau_hi - (int64_t)j.tau_lo > (int64_t)RD_CD_MAX_SPAN) { *why = "tau_hi - tau_lo (at most 2048)"; return RD_ERR_ARG; }
+        if (j.tau_lo < -RD_CD_MAX_TAU || j.tau_lo > RD_CD_MAX_TAU || j.tau_hi < -RD_CD_MAX_TAU || j.tau_hi > RD_CD_MAX_TAU) { *why = "tau (-2^30 .. 2^30)"; return RD_ERR_ARG; }
+        if (j.id >= 8u && j.id != RD_BX_ANY_ID) { *why = "id (0 .. 7 or 0xFF)"; return RD_ERR_ARG; }
+        if (j.corr_re < -32768 || j.corr_re > 32767 || j.corr_im < -32768 || j.corr_im > 32767) { *why = "corr (-32768 .. 32767)"; return RD_ERR_ARG; }
+        if (j.pad != 0u) { *why = "pad != 0"; return RD_ERR_ARG; }
+    }
+    *bad = -1;
+    return RD_OK;
+}
+
 // BURST SEARCH (include/rtldavis_hip.h): the list's rules and step 7s (a chunk's candidates, step 2s: rd_host.h, inline)
 int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why) {
     static const char *none = "";

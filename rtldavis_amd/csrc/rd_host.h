@@ -65,6 +65,9 @@ bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t cloc
                  int32_t *tau_b);
 bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
 
+// CLIP DECODE (include/rtldavis_hip.h): the rule of a job list, rd_cd_check_jobs, is part of the C ABI and declared there
+// (rd_host.cpp, beside rd_bx_check_table).
+
 // BURST SEARCH (include/rtldavis_hip.h), the parts that need no device.
 // rd_bs_check_centres: RD_OK, or RD_ERR_ARG with *why naming the rule and *bad the offending centre's index (-1: the
 // count n outside 0 .. RD_BS_MAX_CENTRES or a null list) - a centre >= RD_BD_NB_GRID, or one that repeats an earlier one.
