@@ -114,9 +114,10 @@ class QLaunch:
         self.cur = np.ascontiguousarray(np.stack(rows), np.uint8)
         self.prev = None if prev is None else np.ascontiguousarray(np.stack(prev), np.uint8)
         bs = int(cfg.block_size)
-        assert self.cur.shape[1] == 2 * bs and (self.prev is None or self.prev.shape == self.cur.shape) and bs == DC.shape(cfg)[3]
+        # (any block_size rd_debug_burst_quality admits and any number of channels: the crafted cases use LOOK and at most 4)
+        assert self.cur.shape[1] == 2 * bs and (self.prev is None or self.prev.shape == self.cur.shape) and bs % W == 0 and bs >= DC.shape(cfg)[3]
         self.n_ch = self.cur.shape[0]
-        assert self.n_ch <= 4 and len(records) == self.n_ch
+        assert len(records) == self.n_ch
         self.cap = BC.cap_of(bs // W)
         self.msgs = np.frombuffer(bytes([FILL]) * (self.n_ch * self.cap * BURST_MSG_DTYPE.itemsize), BURST_MSG_DTYPE).reshape(self.n_ch, self.cap).copy()
         self.n_msgs = np.zeros(self.n_ch, np.uint32)
