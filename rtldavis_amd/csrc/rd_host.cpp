@@ -5,6 +5,7 @@
 
 #include <math.h>
 #include <sched.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -227,17 +228,18 @@ bool rd_waiter::relax() {
     return true;
 }
 
-bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
-    if (!(m.flags & 1u) || sl <= 0) return false;
+bool rd_msg_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl, bool look_back, bool same_centre) {
+    if ((look_back && !(m.flags & 1u)) || sl <= 0) return false;
     for (size_t i = 0; i < n_delivered; i++) {
         const rd_burst_msg &q = delivered[i];
         const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
-        if (q.channel == m.channel && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
+        if (q.channel == m.channel && (!same_centre || q.pad[3] == m.pad[3]) && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl)
+            return true;
     }
     return false;
 }
 
-// BURST EXPECT (include/rtldavis_hip.h): the table's rules, one expectation's candidates in a chunk, step 7'
+// BURST EXPECT (include/rtldavis_hip.h): the table's rules, one expectation's candidates in a chunk
 int rd_bx_check_table(const rd_expect *e, int n, int n_channels, int *bad, const char **why) {
     static const char *none = "";
     const char *dummy_why;
@@ -289,16 +291,6 @@ bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t cloc
     return true;
 }
 
-bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
-    if (sl <= 0) return false;
-    for (size_t i = 0; i < n_delivered; i++) {
-        const rd_burst_msg &q = delivered[i];
-        const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
-        if (q.channel == m.channel && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
-    }
-    return false;
-}
-
 // CLIP DECODE (include/rtldavis_hip.h): the rules of a job list.  cfg takes no part in them today - a job that has no
 // candidate for its SL and N is legal and idle - and is there so that a rule that needs it changes no signature.
 extern "C" int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, int n_jobs, size_t pool_outputs, int *bad,
@@ -330,7 +322,7 @@ extern "C" int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, i
     return RD_OK;
 }
 
-// BURST SEARCH (include/rtldavis_hip.h): the list's rules and step 7s (a chunk's candidates, step 2s: rd_host.h, inline)
+// BURST SEARCH (include/rtldavis_hip.h): the list's rules (a chunk's candidates, step 2s: rd_host.h, inline)
 int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why) {
     static const char *none = "";
     const char *dummy_why;
@@ -349,16 +341,6 @@ int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **wh
     }
     *bad = -1;
     return RD_OK;
-}
-
-bool rd_bs_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl) {
-    if (sl <= 0) return false;
-    for (size_t i = 0; i < n_delivered; i++) {
-        const rd_burst_msg &q = delivered[i];
-        const uint64_t d = m.time - q.time, ad = d < 0ull - d ? d : 0ull - d;   // (the clock wraps at 2^64)
-        if (q.channel == m.channel && q.pad[3] == m.pad[3] && !memcmp(q.data, m.data, sizeof m.data) && ad < (uint64_t)sl) return true;
-    }
-    return false;
 }
 
 // BURST DECODE step 4n (include/rtldavis_hip.h): designed in float64, every product and quotient in the order written
@@ -413,4 +395,146 @@ extern "C" int rd_bc_window(int block_size, int have_prev, int64_t a, int64_t e,
     out[1] = c.n;
     out[2] = c.flags;
     return ok ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// the receiver's fetch (rd_host.h: rd_collect_*)
+// ------------------------------------------------------------------------------------------
+#define COLLECT_FAIL(...) return (snprintf(err->text, sizeof err->text, __VA_ARGS__), RD_ERR_DEVICE)
+
+int rd_collect_levels(const void *slot, int n_ch, long chunk, std::vector<rd_chan_level> &lv, rd_input_level *in, rd_errtext *err) {
+    const rd_chan_level *rec = (const rd_chan_level *)slot;
+    lv.assign(rec, rec + n_ch);
+    memcpy(in, rec + n_ch, sizeof *in);
+    for (int c = 0; c < n_ch; c++)
+        if (lv[c].chunk != (uint32_t)chunk) COLLECT_FAIL("level record of channel %d belongs to chunk %u, not %ld", c, lv[c].chunk, chunk);
+    if (in->chunk != (uint64_t)chunk) COLLECT_FAIL("the input level record belongs to chunk %llu, not %ld", (unsigned long long)in->chunk, chunk);
+    return RD_OK;
+}
+
+int rd_collect_spectrum(const void *slot, int n_bins, long chunk, rd_spectrum_info *info, std::vector<double> &power, rd_errtext *err) {
+    memcpy(info, slot, sizeof *info);
+    if (info->chunk != (uint64_t)chunk || (int)info->n_bins != n_bins)
+        COLLECT_FAIL("the spectrum record belongs to chunk %llu (%u bins), not %ld (%d bins)", (unsigned long long)info->chunk, info->n_bins,
+                     chunk, n_bins);
+    const double *p = (const double *)((const uint8_t *)slot + RD_SPEC_HDR_BYTES);
+    power.assign(p, p + n_bins);
+    return RD_OK;
+}
+
+int rd_collect_bursts(const void *slot, int n_ch, size_t n_win, long chunk, std::vector<rd_burst> &runs, std::vector<rd_burst_floor> &floor,
+                      rd_errtext *err) {
+    const size_t cap = rd_bu_cap(n_win);
+    const rd_burst *recs = (const rd_burst *)slot;
+    const rd_burst_floor *fl = (const rd_burst_floor *)((const uint8_t *)slot + rd_bu_floor_offset(n_ch, n_win));
+    floor.assign(fl, fl + n_ch);
+    runs.clear();
+    for (int c = 0; c < n_ch; c++) {
+        if (floor[c].chunk != (uint32_t)chunk || floor[c].n_bursts > cap)
+            COLLECT_FAIL("burst floor record of channel %d belongs to chunk %u (%u runs), not %ld", c, floor[c].chunk, floor[c].n_bursts, chunk);
+        runs.insert(runs.end(), recs + (size_t)c * cap, recs + (size_t)c * cap + floor[c].n_bursts);
+    }
+    return RD_OK;
+}
+
+int rd_collect_decode(const void *slot, const void *qslot, int n_ch, size_t n_win, long chunk, int sl, rd_delivered &hist,
+                      std::vector<uint32_t> &long_runs, std::vector<rd_burst_quality> &qual, rd_errtext *err) {
+    const size_t cap = rd_bu_cap(n_win);
+    const rd_burst_msg *recs = (const rd_burst_msg *)slot;
+    const rd_bd_header *hd = (const rd_bd_header *)((const uint8_t *)slot + rd_bd_header_offset(n_ch, n_win));
+    const rd_burst_quality *qrecs = (const rd_burst_quality *)qslot;
+    hist.begin(chunk);
+    qual.clear();
+    long_runs.assign(n_ch, 0u);
+    for (int c = 0; c < n_ch; c++) {
+        const rd_bd_header h = hd[c];
+        if (h.chunk != (uint32_t)chunk || h.n_msgs > cap)
+            COLLECT_FAIL("burst message header of channel %d belongs to chunk %u (%u messages), not %ld", c, h.chunk, h.n_msgs, chunk);
+        long_runs[c] = h.long_runs;
+        for (uint32_t i = 0; i < h.n_msgs; i++) {
+            const rd_burst_msg m = recs[(size_t)c * cap + i];
+            if (hist.repeats(m, sl, true, false)) continue;   // step 7
+            hist.last.push_back(m);
+            if (!qrecs) continue;
+            const rd_burst_quality q = qrecs[(size_t)c * cap + i];
+            if (q.chunk != (uint32_t)chunk) COLLECT_FAIL("quality record %u of channel %d belongs to chunk %u, not %ld", i, c, q.chunk, chunk);
+            qual.push_back(q);
+        }
+    }
+    hist.commit(chunk);
+    return RD_OK;
+}
+
+int rd_collect_expect(const void *slot, const void *qslot, int n_ch, size_t n_win, long chunk, int sl, int n, const uint32_t *cand,
+                      rd_delivered &hist, uint32_t *counts, std::vector<rd_burst_quality> &qual, rd_errtext *err) {
+    const rd_burst_msg *recs = (const rd_burst_msg *)slot;
+    const rd_bx_header *hd = (const rd_bx_header *)((const uint8_t *)slot + RD_BX_HEADER_OFFSET);
+    const rd_burst_quality *qrecs = qslot ? (const rd_burst_quality *)((const uint8_t *)qslot + rd_bq_expect_offset(n_ch, n_win)) : nullptr;
+    hist.begin(chunk);
+    qual.clear();
+    for (int i = 0; i < RD_BX_MAX; i++) counts[i] = i < n ? 0u : RD_BX_NO_ENTRY;
+    for (int i = 0; slot && i < n; i++) {
+        const rd_bx_header h = hd[i];
+        if (h.chunk != (uint32_t)chunk || h.n_msgs > 1u || h.candidates != cand[i])
+            COLLECT_FAIL("expectation %d: header of chunk %u (%u messages, %u candidates), not of chunk %ld with %u candidates", i, h.chunk,
+                         h.n_msgs, h.candidates, chunk, cand[i]);
+        counts[i] = h.candidates;
+        if (!h.n_msgs || hist.repeats(recs[i], sl, false, false)) continue;   // step 7'
+        hist.last.push_back(recs[i]);
+        if (!qrecs) continue;
+        const rd_burst_quality q = qrecs[i];
+        if (q.chunk != (uint32_t)chunk) COLLECT_FAIL("quality record of expectation %d belongs to chunk %u, not %ld", i, q.chunk, chunk);
+        qual.push_back(q);
+    }
+    hist.commit(chunk);
+    return RD_OK;
+}
+
+int rd_collect_search(const void *slot, int n_ch, long chunk, int sl, int n, rd_delivered &hist, std::vector<rd_bs_header> &hdr,
+                      rd_errtext *err) {
+    hist.begin(chunk);
+    hdr.clear();
+    if (n) {
+        const rd_burst_msg *recs = (const rd_burst_msg *)slot;
+        const rd_bs_header *hd = (const rd_bs_header *)((const uint8_t *)slot + rd_bs_header_offset(n_ch));
+        hdr.assign(hd, hd + (size_t)n * (size_t)n_ch);
+        for (size_t g = 0; g < hdr.size(); g++) {   // g = centre * n_ch + channel
+            const rd_bs_header h = hdr[g];
+            if (h.chunk != (uint32_t)chunk || h.n_msgs > (uint32_t)RD_BS_PER)
+                COLLECT_FAIL("search header of centre %d, channel %d belongs to chunk %u (%u messages), not %ld", (int)(g / (size_t)n_ch),
+                             (int)(g % (size_t)n_ch), h.chunk, h.n_msgs, chunk);
+            for (uint32_t r = 0; r < h.n_msgs; r++) {
+                const rd_burst_msg m = recs[g * RD_BS_PER + r];
+                if (!hist.repeats(m, sl, false, true)) hist.last.push_back(m);   // step 7s
+            }
+        }
+    }
+    hist.commit(chunk);
+    return RD_OK;
+}
+
+int rd_collect_clips(const void *slot, int n_ch, int quota, long chunk, std::vector<rd_burst_clip> &clips, std::vector<uint8_t> &bytes,
+                     std::vector<uint32_t> &dropped, rd_errtext *err) {
+    const size_t q = (size_t)quota;
+    const rd_burst_clip *recs = (const rd_burst_clip *)slot;
+    const rd_bc_header *hd = (const rd_bc_header *)((const uint8_t *)slot + rd_bc_header_offset(n_ch));
+    const uint8_t *pool = (const uint8_t *)slot + rd_bc_pool_offset(n_ch);
+    clips.clear();
+    bytes.clear();
+    dropped.assign(n_ch, 0u);
+    for (int c = 0; c < n_ch; c++) {
+        const rd_bc_header h = hd[c];
+        if (h.chunk != (uint32_t)chunk || h.n_clips > (uint32_t)RD_BC_PER || h.used > q)
+            COLLECT_FAIL("clip header of channel %d belongs to chunk %u (%u clips, %u outputs), not %ld", c, h.chunk, h.n_clips, h.used, chunk);
+        dropped[c] = h.dropped;
+        const size_t base = bytes.size() / 2;   // outputs packed so far
+        for (uint32_t i = 0; i < h.n_clips; i++) {
+            rd_burst_clip k = recs[(size_t)c * RD_BC_PER + i];
+            if ((size_t)k.offset + k.n > h.used) COLLECT_FAIL("clip %u of channel %d lies at %u + %u of %u outputs", i, c, k.offset, k.n, h.used);
+            k.offset = (uint32_t)(base + k.offset);
+            clips.push_back(k);
+        }
+        bytes.insert(bytes.end(), pool + (size_t)c * 2 * q, pool + (size_t)c * 2 * q + 2 * (size_t)h.used);
+    }
+    return RD_OK;
 }

@@ -9,6 +9,9 @@
 //   rd_bq_windows_of      BURST QUALITY: a record's packet, sync and noise windows (inline: the kernel evaluates it too)
 //   rd_bs_range           BURST SEARCH: a chunk's candidate positions (inline: the kernel evaluates it too)
 //   rd_bc_window_of       BURST CLIPS: a request's clamp to the two chunks and to whole vectors (inline: the kernel evaluates it too)
+//   rd_msg_repeats        steps 7, 7' and 7s: a record that reports again what the fetch of the chunk before delivered
+//   rd_delivered          ... and what that fetch delivered
+//   rd_collect_*          the receiver's fetch: one slot's records into the handle's vectors, every count checked first
 // py = /root/reference/src/rtldavis/dsp.py
 #pragma once
 #include <stddef.h>
@@ -17,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rtldavis_hip.h"
+#include "rd_slots.h"
 
 struct rd_devcfg {
     int32_t S, P, K, B, L, PL, nbytes;  // symbol_length, preamble/packet symbols, block, buffer, preamble_length
@@ -48,10 +52,59 @@ uint32_t rd_ord_bucket_cap(long n_samples);
 // uint8: NS * 2B bytes), else RD_ERR_ARG with *expected set
 int rd_check_block_count(int is_complex, size_t count, size_t B, size_t NS, size_t *expected);
 
-// BURST DECODE step 7 (include/rtldavis_hip.h): record m reports again a packet that the fetch of the chunk before
-// delivered - m looked back (flags & 1), and one of `delivered` has its channel and data and a time less than sl
-// outputs from m's on the 64-bit clock.  The fetch drops such a record (rd_wideband.hip).
-bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
+// Steps 7, 7' and 7s (include/rtldavis_hip.h: BURST DECODE, BURST EXPECT, BURST SEARCH): record m reports again a packet
+// that the fetch of the chunk before delivered - one of `delivered` has its channel and data and a time less than sl
+// outputs from m's on the 64-bit clock.  The fetch drops such a record (rd_collect_*).  look_back: only a record that
+// looked back (flags & 1) can repeat; same_centre: the two also share pad[3], for each centre gives its own record.
+bool rd_msg_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl, bool look_back, bool same_centre);
+static inline bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *d, size_t n, int sl) { return rd_msg_repeats(m, d, n, sl, true, false); }
+static inline bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *d, size_t n, int sl) { return rd_msg_repeats(m, d, n, sl, false, false); }
+static inline bool rd_bs_repeats(const rd_burst_msg &m, const rd_burst_msg *d, size_t n, int sl) { return rd_msg_repeats(m, d, n, sl, false, true); }
+// What the fetch of chunk `chunk` delivered (last) and, while the next fetch collects, what the one before it delivered
+// (prev), against which a record is a repeat.  A chunk that was never fetched delivered nothing: chunk = -1 while a
+// collection is unfinished (it may fail) and -2 after reset(), when the fetch of chunk 0 looks for chunk -1 and must not
+// take the run before for it.
+struct rd_delivered {
+    std::vector<rd_burst_msg> last, prev;
+    long chunk = -1;
+    void begin(long k) {
+        if (chunk == k - 1) prev.swap(last);
+        else prev.clear();
+        chunk = -1;
+        last.clear();
+    }
+    void commit(long k) { chunk = k; }
+    void forget() { chunk = -2; prev.clear(); }
+    bool repeats(const rd_burst_msg &m, int sl, bool look_back, bool same_centre) const {
+        return rd_msg_repeats(m, prev.data(), prev.size(), sl, look_back, same_centre);
+    }
+};
+
+// The receiver's fetch (rd_wideband.hip: wb_fetched), one function per slot kind.  `slot` is what the kernels of chunk
+// `chunk` wrote (rd_slots.h) and is only read; every header is checked - it carries the chunk's number, its counts fit
+// the slot - before a record place it bounds is read.  RD_OK, or RD_ERR_DEVICE with the message in err: a record of
+// another chunk here would be an ordering bug, not something to hand on.  The outputs are undefined after a failure.
+struct rd_errtext { char text[320]; };
+int rd_collect_levels(const void *slot, int n_ch, long chunk, std::vector<rd_chan_level> &lv, rd_input_level *in, rd_errtext *err);
+int rd_collect_spectrum(const void *slot, int n_bins, long chunk, rd_spectrum_info *info, std::vector<double> &power, rd_errtext *err);
+// a channel's runs are the first n_bursts of its cap = rd_bu_cap(n_win) record places
+int rd_collect_bursts(const void *slot, int n_ch, size_t n_win, long chunk, std::vector<rd_burst> &runs, std::vector<rd_burst_floor> &floor,
+                      rd_errtext *err);
+// a channel's messages are the first n_msgs of its cap record places; step 7 against hist, the kept ones into hist.last.
+// qslot (null: quality off): record i of the quality slot belongs to record i of the message slot and goes where it goes.
+int rd_collect_decode(const void *slot, const void *qslot, int n_ch, size_t n_win, long chunk, int sl, rd_delivered &hist,
+                      std::vector<uint32_t> &long_runs, std::vector<rd_burst_quality> &qual, rd_errtext *err);
+// n: the size of the table the chunk was submitted with, cand: the host's candidate counts; slot null: the submit launched
+// nothing, zero records.  counts: RD_BX_MAX of them, RD_BX_NO_ENTRY from n on.  Step 7' against hist.
+int rd_collect_expect(const void *slot, const void *qslot, int n_ch, size_t n_win, long chunk, int sl, int n, const uint32_t *cand,
+                      rd_delivered &hist, uint32_t *counts, std::vector<rd_burst_quality> &qual, rd_errtext *err);
+// n: the size of the list the chunk was submitted with (0: nothing is read).  Step 7s against hist.
+int rd_collect_search(const void *slot, int n_ch, long chunk, int sl, int n, rd_delivered &hist, std::vector<rd_bs_header> &hdr,
+                      rd_errtext *err);
+// a channel's clips are the first n_clips of its record places, its bytes the first 2 * used of its pool of 2 * quota - only
+// those are copied, packed channel after channel, and `offset` is rewritten to match
+int rd_collect_clips(const void *slot, int n_ch, int quota, long chunk, std::vector<rd_burst_clip> &clips, std::vector<uint8_t> &bytes,
+                     std::vector<uint32_t> &dropped, rd_errtext *err);
 
 // BURST EXPECT (include/rtldavis_hip.h), the host's parts.
 // rd_bx_check_table: RD_OK, or RD_ERR_ARG with *bad = the first offending entry (-1: n itself) and *why naming the rule.
@@ -59,11 +112,9 @@ bool rd_bd_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
 // idle there, else *tau_a <= *tau_b, the least and greatest tau with t_lo <= clock + tau <= t_hi on the 64-bit clock
 // (every difference is taken modulo 2^64, so a clock near the wrap is like any other), 0 <= tau + sl (n_sym - 1) <
 // block_size, and tau - sl >= 0 unless have_prev.  Needs t_hi - t_lo <= RD_BX_MAX_SPAN (rd_bx_check_table).
-// rd_bx_repeats: step 7' - one of `delivered` has m's channel and data and a time less than sl outputs from m's.
 int rd_bx_check_table(const rd_expect *e, int n, int n_channels, int *bad, const char **why);
 bool rd_bx_range(int sl, int n_sym, int block_size, int have_prev, uint64_t clock, uint64_t t_lo, uint64_t t_hi, int32_t *tau_a,
                  int32_t *tau_b);
-bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
 
 // CLIP DECODE (include/rtldavis_hip.h): the rule of a job list, rd_cd_check_jobs, is part of the C ABI and declared there
 // (rd_host.cpp, beside rd_bx_check_table).
@@ -73,9 +124,7 @@ bool rd_bx_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t 
 // count n outside 0 .. RD_BS_MAX_CENTRES or a null list) - a centre >= RD_BD_NB_GRID, or one that repeats an earlier one.
 // rd_bs_range: step 2s - false when the chunk has no candidate, else *tau_a .. *tau_b = max(lo + sl, -sl (n_sym - 1)) ..
 // block_size - 1 - sl (n_sym - 1), lo = have_prev ? -look : 0 (defined below, inline).
-// rd_bs_repeats: step 7s - one of `delivered` has m's channel, pad[3] and data and a time less than sl outputs from m's.
 int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why);
-bool rd_bs_repeats(const rd_burst_msg &m, const rd_burst_msg *delivered, size_t n_delivered, int sl);
 
 // BURST QUALITY (include/rtldavis_hip.h): the three windows of a record whose first symbol ends at tau, as half-open
 // ranges of outputs relative to the chunk's first - packet [p0, p1), sync [p0, s1), noise [n0, n1) with n1 - n0 = n_noise

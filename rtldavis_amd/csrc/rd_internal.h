@@ -53,7 +53,7 @@ struct rd_layout {
     size_t bits_stride;       // words
 };
 
-// rd_devcfg: rd_host.h (the pure-host translation unit shares it)
+// rd_devcfg: rd_host.h (the pure-host translation unit shares it); the slots' layouts and headers: rd_slots.h, through it
 
 struct rd_match {
     int32_t stream;
@@ -240,7 +240,6 @@ __device__ __forceinline__ float rd_chan_adm(uint32_t bits) {
 // [0, n_samples) of `wide` (device, 16-byte aligned, sample format fmt); out: RD_SPEC_HDR_BYTES of header {uint64 seq;
 // uint32 segments; uint32 n_bins} + n_bins doubles, a device address (mapped host memory included).
 #define RD_SP_MAX_GROUPS 64
-#define RD_SPEC_HDR_BYTES 16
 struct rd_spec;
 int rd_spec_check(int n_bins, size_t n_samples);
 int rd_spec_prepare(rd_spec **sp, int n_bins, size_t n_samples, hipStream_t st);
@@ -253,12 +252,6 @@ void rd_spec_destroy(rd_spec *sp);
 //   [n_ch][cap] rd_burst | [n_ch] rd_burst_floor | [n_ch] uint32 thresholds           cap = rd_bu_cap(n_win)
 // The caller writes the thresholds before the launch; the kernel writes the floor records and, per channel, the first
 // floor.n_bursts of its cap record places.
-#define RD_BU_WINDOW 128
-#define RD_BU_MAX_WINDOWS 4096
-static inline size_t rd_bu_cap(size_t n_win) { return (n_win + 1) / 2; }
-static inline size_t rd_bu_floor_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst); }
-static inline size_t rd_bu_thr_offset(int n_ch, size_t n_win) { return rd_bu_floor_offset(n_ch, n_win) + (size_t)n_ch * sizeof(rd_burst_floor); }
-static inline size_t rd_bu_slot_bytes(int n_ch, size_t n_win) { return rd_bu_thr_offset(n_ch, n_win) + (size_t)n_ch * sizeof(uint32_t); }
 int rd_bursts_check(size_t n_out);
 int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_t n_out, uint64_t seq, void *slot, hipStream_t st);
 // Burst decode of a channelized chunk (rd_burst_decode.hip: k_chan_burst_decode; the definition: include/rtldavis_hip.h,
@@ -278,13 +271,6 @@ int rd_bursts_launch(const uint8_t *chan_out, size_t out_stride, int n_ch, size_
 #define RD_BD_MAX_LOOK_W 16     /* packet_symbols * symbol_length + 1 <= 2048 */
 #define RD_BD_DATA_BYTES RD_BURST_MSG_BYTES
 #define RD_BD_MAX_FLIPS 2       /* symbols a repair flips at most */
-struct rd_bd_header {
-    uint32_t n_msgs, long_runs;
-    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
-    uint32_t pad;
-};
-static inline size_t rd_bd_header_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst_msg); }
-static inline size_t rd_bd_slot_bytes(int n_ch, size_t n_win) { return rd_bd_header_offset(n_ch, n_win) + (size_t)n_ch * sizeof(rd_bd_header); }
 int rd_bd_look_windows(const rd_config *cfg);
 int rd_burst_decode_check(const rd_config *cfg);
 int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
@@ -298,21 +284,6 @@ int rd_bd_narrow_upload(int sl, uint32_t **d_tab);
 // kernel reads them; returns how many are active - 0: the caller launches nothing.  cand (may be null): n counts.
 // rd_burst_expect_launch: one workgroup per entry; it writes every header below n and, for an expectation that found a
 // packet, its record place.  slot_host / slot_dev: the host and device address of the same slot.
-struct rd_bx_header {
-    uint32_t n_msgs, candidates;
-    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
-    uint32_t pad;
-};
-struct rd_bx_entry {
-    int32_t channel;
-    uint32_t id;
-    int32_t tau_a, tau_b;        // tau_a > tau_b: idle in this chunk
-    int32_t corr_re, corr_im;
-    uint32_t pad[2];
-};
-#define RD_BX_HEADER_OFFSET ((size_t)RD_BX_MAX * sizeof(rd_burst_msg))
-#define RD_BX_ENTRY_OFFSET (RD_BX_HEADER_OFFSET + (size_t)RD_BX_MAX * sizeof(rd_bx_header))
-#define RD_BX_SLOT_BYTES (RD_BX_ENTRY_OFFSET + (size_t)RD_BX_MAX * sizeof(rd_bx_entry))
 int rd_burst_expect_stage(const rd_config *cfg, int have_prev, uint64_t clock, const rd_expect *e, int n, void *slot_host,
                           uint32_t *cand);
 int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
@@ -326,9 +297,6 @@ int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const 
 // places; nothing of a centre index >= n is touched.  centres: host memory, n of them, checked by rd_bs_check_centres
 // (rd_host.h); they travel in the kernel's arguments.  narrow_tab: the device table of rd_bd_narrow_upload for cfg's
 // symbol_length (never null: the search is always a narrow-band one).
-#define RD_BS_MAX_CHANNELS 4096
-static inline size_t rd_bs_header_offset(int n_ch) { return (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * RD_BS_PER * sizeof(rd_burst_msg); }
-static inline size_t rd_bs_slot_bytes(int n_ch) { return rd_bs_header_offset(n_ch) + (size_t)RD_BS_MAX_CENTRES * (size_t)n_ch * sizeof(rd_bs_header); }
 int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                            size_t n_out, uint64_t clock, uint64_t seq, const uint8_t *centres, int n, const uint32_t *narrow_tab,
                            void *slot_dev, hipStream_t st);
@@ -340,13 +308,6 @@ int rd_burst_search_launch(const rd_config *cfg, const uint8_t *chan_out, const 
 // device address (mapped host memory) with room for n_groups x cap records, record [group][place] beside its message.
 // The receiver's quality slot:  [n_ch][cap] rd_burst_quality | [RD_BX_MAX] rd_burst_quality.
 // narrow_tab: the device table of rd_bd_narrow_upload for cfg's symbol_length; may be null with symbol_length < 4 only.
-struct rd_bq_header {
-    uint32_t n_msgs, other;
-    uint32_t chunk;
-    uint32_t pad;
-};
-static inline size_t rd_bq_expect_offset(int n_ch, size_t n_win) { return (size_t)n_ch * rd_bu_cap(n_win) * sizeof(rd_burst_quality); }
-static inline size_t rd_bq_slot_bytes(int n_ch, size_t n_win) { return rd_bq_expect_offset(n_ch, n_win) + (size_t)RD_BX_MAX * sizeof(rd_burst_quality); }
 int rd_burst_quality_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                             size_t n_out, int noise_gap, const uint32_t *narrow_tab, const rd_burst_msg *recs, size_t cap,
                             const rd_bq_header *hdr, int n_groups, rd_burst_quality *qual, hipStream_t st);
@@ -359,15 +320,6 @@ int rd_burst_quality_launch(const rd_config *cfg, const uint8_t *chan_out, const
 //   [n_ch][RD_BC_PER] rd_burst_clip | [n_ch] rd_bc_header | padding to a multiple of 16 | [n_ch][2 quota] bytes
 // The kernel writes every header and, per channel, the first header.n_clips record places and the first 2 header.used
 // bytes of its pool.  cfg is read for symbol_length and packet_symbols, and checked, with RD_BC_MESSAGES only.
-struct rd_bc_header {
-    uint32_t n_clips, dropped;
-    uint32_t owed, used;         // outputs
-    uint32_t chunk;              // the chunk's sequence number since create / reset, its low 32 bits
-    uint32_t pad;
-};
-static inline size_t rd_bc_header_offset(int n_ch) { return (size_t)n_ch * RD_BC_PER * sizeof(rd_burst_clip); }
-static inline size_t rd_bc_pool_offset(int n_ch) { return (rd_bc_header_offset(n_ch) + (size_t)n_ch * sizeof(rd_bc_header) + 15) & ~(size_t)15; }
-static inline size_t rd_bc_slot_bytes(int n_ch, int quota) { return rd_bc_pool_offset(n_ch) + (size_t)n_ch * 2 * (size_t)quota; }
 int rd_burst_clips_check(int n_ch, int sources, int pre, int post, int quota);   // the rule of rd_wb_set_burst_clips: RD_ERR_ARG with a message
 int rd_burst_clips_launch(const rd_config *cfg, const uint8_t *chan_out, const uint8_t *chan_prev, size_t out_stride, int n_ch,
                           size_t n_out, uint64_t clock, uint64_t seq, int sources, int pre, int post, int quota,
