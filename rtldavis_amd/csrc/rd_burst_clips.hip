@@ -288,7 +288,7 @@ extern "C" int rd_debug_burst_clips(const rd_config *cfg, const uint8_t *cur, co
         if (n_runs[c] > cap || (want_msgs && n_msgs[c] > cap))
             return rd_fail_msg(RD_ERR_ARG, "burst clips: more records in channel %d than its %zu places", c, cap);
     if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "burst clips: stride %zu for %zu outputs", stride, n_out);
-    if ((rc = rd_ensure_device_public())) return rc;    // (no device work for a wrong argument)
+    if ((rc = rd_ensure_device())) return rc;    // (no device work for a wrong argument)
     auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
     const size_t o_bu = 0, o_bd = up(o_bu + rd_bu_slot_bytes(n_ch, n_win)), o_bx = up(o_bd + rd_bd_slot_bytes(n_ch, n_win)),
                  o_bs = up(o_bx + RD_BX_SLOT_BYTES), o_ph = up(o_bs + rd_bs_slot_bytes(n_ch)),

@@ -340,8 +340,6 @@ __device__ __forceinline__ void rd_bd_write_record(rd_burst_msg *m, int channel,
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
 // the 16 sync symbols, the first in bit 15
 static inline uint32_t rd_bd_sync_word(const rd_config *cfg) {
     uint32_t sync = 0u;
@@ -404,7 +402,7 @@ struct rd_burst_dbg {
         if (cfg->symbol_length < min_sl) return rd_fail_msg(RD_ERR_ARG, "%s: symbol_length %d, at least %d", what, cfg->symbol_length, min_sl);
         const size_t n_out = (size_t)cfg->block_size;
         if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "%s: stride %zu for %zu outputs", what, stride, n_out);
-        return rd_ensure_device_public();
+        return rd_ensure_device();
     }
     int upload(const uint8_t *cur, const uint8_t *prev, size_t bytes) {
         if (hipMalloc(&d_cur, bytes) != hipSuccess || hipMemcpy(d_cur, cur, bytes, hipMemcpyHostToDevice) != hipSuccess)

@@ -42,8 +42,6 @@
 
 #include "rd_internal.h"
 
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
 #define RD_BU_THREADS 256
 #define RD_BU_LANES 16                           // lanes per window: 16 vectors of 16 bytes
 #define RD_BU_PER_PASS (RD_BU_THREADS / RD_BU_LANES)
@@ -248,7 +246,7 @@ extern "C" int rd_debug_bursts(const uint8_t *chan, size_t stride, int n_ch, siz
     int rc = rd_bursts_check(n_out);
     if (rc) return rc;                               // (nothing allocated, nothing launched)
     if (stride < 2 * n_out || (stride & 15)) return rd_fail_msg(RD_ERR_ARG, "bursts: stride %zu for %zu outputs", stride, n_out);
-    rc = rd_ensure_device_public();
+    rc = rd_ensure_device();
     if (rc) return rc;
     const size_t n_win = n_out / RD_BU_WINDOW, bytes = rd_bu_slot_bytes(n_ch, n_win);
     uint8_t *d_chan = nullptr, *slot = nullptr;

@@ -117,14 +117,11 @@
 #include <cstring>
 #include <type_traits>
 #include <vector>
-#include <unistd.h>
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/rtldavis_hip.h"
 #include "rd_internal.h"
-
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
 
 #define RD_CHAN_TB 4                        // 32-time blocks per wave
 #define RD_CHAN_TT (32 * RD_CHAN_TB)        // output times per workgroup
@@ -186,7 +183,6 @@ struct rd_chan {
     rd_spec *spec = nullptr;       // rd_chan_spectrum's tables and scratch (rd_spectrum.hip), made on first use
     bool dev_ready = false;
     int device = -1;               // the device the buffers live on
-    pid_t pid = 0;                 // the process that allocated them
 };
 
 // x mod m for integer-valued 0 <= x < 2^53, 1 <= m < 2^26 (exact: one fma, one correction step)
@@ -675,11 +671,6 @@ __global__ __launch_bounds__(RD_LV_THREADS) void k_chan_levels(const uint4 *__re
 // ------------------------------------------------------------------------------------------
 // C ABI (include/rtldavis_hip.h)
 // ------------------------------------------------------------------------------------------
-#define CHK(x)                                                                                              \
-    do {                                                                                                    \
-        hipError_t e_ = (x);                                                                                \
-        if (e_ != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));      \
-    } while (0)
 
 static uint16_t f16_rn(double v) {  // round to nearest even f16 (|v| < 65504)
     const _Float16 h = (_Float16)v;
@@ -828,7 +819,7 @@ extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const doub
 extern "C" void rd_chan_destroy(rd_chan *h) {
     if (!h) return;
     // device memory belongs to the process that allocated it: a forked copy only drops its host state
-    if (h->dev_ready && h->pid == getpid()) {
+    if (h->dev_ready && rd_owns_device_state()) {
         if (h->device >= 0) hipSetDevice(h->device);
         hipFree(h->d_amat); hipFree(h->d_dc); hipFree(h->d_shifts); hipFree(h->d_wide);
         hipFree(h->d_phase); hipFree(h->d_taps); hipFree(h->d_rt); hipHostFree(h->h_rt);
@@ -839,28 +830,27 @@ extern "C" void rd_chan_destroy(rd_chan *h) {
 }
 
 static int chan_alloc(rd_chan *h, size_t n_wide) {
-    int rc = rd_ensure_device_public();
+    int rc = rd_ensure_device();
     if (rc) return rc;
-    if (h->dev_ready && h->device >= 0) CHK(hipSetDevice(h->device));
+    if (h->dev_ready && h->device >= 0) HIPCHK(hipSetDevice(h->device));
     if (!h->dev_ready) {
-        CHK(hipGetDevice(&h->device));
-        h->pid = getpid();
-        CHK(hipMalloc(&h->d_amat, h->h_amat.size() * sizeof(uint16_t)));
-        CHK(hipMemcpy(h->d_amat, h->h_amat.data(), h->h_amat.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        CHK(hipMalloc(&h->d_dc, h->h_dc.size() * sizeof(float)));
-        CHK(hipMemcpy(h->d_dc, h->h_dc.data(), h->h_dc.size() * sizeof(float), hipMemcpyHostToDevice));
-        CHK(hipMalloc(&h->d_shifts, h->shifts.size() * sizeof(int64_t)));
-        CHK(hipMemcpy(h->d_shifts, h->shifts.data(), h->shifts.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        CHK(hipMalloc(&h->d_phase, h->phase.size() * sizeof(int64_t)));
-        CHK(hipMemcpy(h->d_phase, h->phase.data(), h->phase.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        CHK(hipMalloc(&h->d_gains, h->gains.size() * sizeof(float)));
-        CHK(hipMemcpy(h->d_gains, h->gains.data(), h->gains.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipGetDevice(&h->device));
+        HIPCHK(hipMalloc(&h->d_amat, h->h_amat.size() * sizeof(uint16_t)));
+        HIPCHK(hipMemcpy(h->d_amat, h->h_amat.data(), h->h_amat.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&h->d_dc, h->h_dc.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(h->d_dc, h->h_dc.data(), h->h_dc.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&h->d_shifts, h->shifts.size() * sizeof(int64_t)));
+        HIPCHK(hipMemcpy(h->d_shifts, h->shifts.data(), h->shifts.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&h->d_phase, h->phase.size() * sizeof(int64_t)));
+        HIPCHK(hipMemcpy(h->d_phase, h->phase.data(), h->phase.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&h->d_gains, h->gains.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(h->d_gains, h->gains.data(), h->gains.size() * sizeof(float), hipMemcpyHostToDevice));
         h->dev_ready = true;
     }
     if (n_wide > h->wide_cap) {
         if (h->d_wide) hipFree(h->d_wide);
         h->d_wide = nullptr;
-        CHK(hipMalloc(&h->d_wide, rd_fmt_in_bps(h->fmt) * n_wide + 16));
+        HIPCHK(hipMalloc(&h->d_wide, rd_fmt_in_bps(h->fmt) * n_wide + 16));
         h->wide_cap = n_wide;
     }
     return RD_OK;
@@ -882,7 +872,7 @@ extern "C" int rd_chan_upload(rd_chan *h, const void *wide_iq, size_t nbytes) {
         return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %zu bytes is not a whole number of %zu-byte IQ pairs", nbytes, bps);
     int rc = chan_alloc(h, nbytes / bps);
     if (rc) return rc;
-    CHK(hipMemcpy(h->d_wide, wide_iq, nbytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_wide, wide_iq, nbytes, hipMemcpyHostToDevice));
     h->wide_n = nbytes / bps;
     return RD_OK;
 }
@@ -911,8 +901,8 @@ static int chan_launch(rd_chan *h, bool stream, const uint8_t *wide, long n_wide
     int xs_bytes = (int)lds;
     void *args[] = {&wide, &n_wide, &amat, &dc, &shifts, &T, &D, &n_ch, &n_early, &out_rate, &gains, &tap_unscale, &n_out,
                     &out, &dst_stride, &xs_bytes, &prev, &t_base_mod, &phase};   // k_channelize's parameters, in order
-    CHK(hipLaunchKernel(chan_kernel(stream, h->fmt), dim3(gx, (unsigned)h->n_groups), dim3(256), args, lds, st));
-    CHK(hipGetLastError());
+    HIPCHK(hipLaunchKernel(chan_kernel(stream, h->fmt), dim3(gx, (unsigned)h->n_groups), dim3(256), args, lds, st));
+    HIPCHK(hipGetLastError());
     return RD_OK;
 }
 
@@ -925,7 +915,7 @@ extern "C" int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_s
     if (dst_stream_stride < 2 * n_out || (dst_stream_stride & 1))
         return rd_fail_msg(RD_ERR_ARG, "destination stride too small for n_out samples");
     const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
-    CHK(hipFuncSetAttribute(chan_kernel(false, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute(chan_kernel(false, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned gx = (unsigned)((n_out + RD_CHAN_TT - 1) / RD_CHAN_TT);
     return chan_launch(h, false, h->d_wide, (long)h->wide_n, nullptr, h->n_early, 0L, (long)n_out, gx, dst_dev,
                        dst_stream_stride, (hipStream_t)hip_stream);
@@ -937,7 +927,7 @@ extern "C" int rd_chan_run_host(rd_chan *h, size_t n_out, uint8_t *out_host, siz
     if (nbytes != need) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: got %zu bytes, expected %zu", nbytes, need);
     if (n_out == 0) return RD_OK;
     uint8_t *d = nullptr;
-    CHK(hipMalloc(&d, need));
+    HIPCHK(hipMalloc(&d, need));
     int rc = rd_chan_run(h, n_out, d, 2 * n_out, nullptr);
     if (rc == RD_OK) {
         hipError_t e = hipMemcpy(out_host, d, need, hipMemcpyDeviceToHost);
@@ -955,7 +945,7 @@ extern "C" int rd_chan_spectrum_dev(rd_chan *h, int n_bins, void *dst_dev, void 
     if (!h->dev_ready || !h->d_wide || !h->wide_n) return rd_fail_msg(RD_ERR_STATE, "no capture resident: rd_chan_upload first");
     int rc = rd_spec_check(n_bins, h->wide_n);
     if (rc) return rc;
-    if (h->device >= 0) CHK(hipSetDevice(h->device));
+    if (h->device >= 0) HIPCHK(hipSetDevice(h->device));
     if ((rc = rd_spec_prepare(&h->spec, n_bins, h->wide_n, (hipStream_t)hip_stream))) return rc;
     return rd_spec_launch(h->spec, h->d_wide, h->fmt, h->wide_n, 0, dst_dev, (hipStream_t)hip_stream);
 }
@@ -967,7 +957,7 @@ extern "C" int rd_chan_spectrum(rd_chan *h, int n_bins, double *power_host, uint
     if (rc) return rc;
     const size_t bytes = RD_SPEC_HDR_BYTES + (size_t)n_bins * sizeof(double);
     uint8_t *d = nullptr;
-    CHK(hipMalloc(&d, bytes));
+    HIPCHK(hipMalloc(&d, bytes));
     std::vector<uint8_t> rec(bytes);
     rc = rd_chan_spectrum_dev(h, n_bins, d, nullptr);
     if (rc == RD_OK) {
@@ -990,15 +980,15 @@ int rd_chan_stream_prepare(rd_chan *h) {
     int rc = chan_alloc(h, 0);
     if (rc) return rc;
     const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
-    CHK(hipFuncSetAttribute(chan_kernel(true, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute(chan_kernel(true, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (!h->d_taps) {   // what a retune needs: the float64 taps, and the records' staging (two pinned slots, one on the device)
         const size_t rt_bytes = (size_t)h->cfg.n_channels * 4 * sizeof(int64_t);
-        CHK(hipMalloc(&h->d_taps, h->taps.size() * sizeof(double)));
-        CHK(hipMemcpy(h->d_taps, h->taps.data(), h->taps.size() * sizeof(double), hipMemcpyHostToDevice));
-        CHK(hipMalloc(&h->d_rt, rt_bytes));
-        CHK(hipHostMalloc((void **)&h->h_rt, 2 * rt_bytes, hipHostMallocDefault));
-        CHK(hipHostMalloc((void **)&h->h_gains, 2 * (size_t)h->cfg.n_channels * sizeof(float), hipHostMallocDefault));
-        CHK(hipFuncSetAttribute((const void *)k_chan_retune, hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIPCHK(hipMalloc(&h->d_taps, h->taps.size() * sizeof(double)));
+        HIPCHK(hipMemcpy(h->d_taps, h->taps.data(), h->taps.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&h->d_rt, rt_bytes));
+        HIPCHK(hipHostMalloc((void **)&h->h_rt, 2 * rt_bytes, hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&h->h_gains, 2 * (size_t)h->cfg.n_channels * sizeof(float), hipHostMallocDefault));
+        HIPCHK(hipFuncSetAttribute((const void *)k_chan_retune, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(h->t_pad * sizeof(float2))));
     }
     return RD_OK;
@@ -1027,11 +1017,11 @@ int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t 
         stage[4 * i] = rec[3 * i]; stage[4 * i + 1] = rec[3 * i + 1]; stage[4 * i + 2] = ((rec[3 * i + 1] % fo) + fo) % fo;
         stage[4 * i + 3] = rec[3 * i + 2];
     }
-    CHK(hipMemcpyAsync(h->d_rt, stage, (size_t)n * 4 * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_rt, stage, (size_t)n * 4 * sizeof(int64_t), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_chan_retune, dim3((unsigned)n), dim3(256), h->t_pad * sizeof(float2), st, (const int64_t *)h->d_rt,
                        (const double *)h->d_taps, h->fmt, h->cfg.n_taps, h->t_pad, h->cfg.decim, (long)h->cfg.out_rate,
                        h->tap_scale, (uint4 *)h->d_amat, (float2 *)h->d_dc, h->d_shifts, h->d_phase);
-    CHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // queued: only now does the host's record of what the tables hold follow (a failure above leaves it, and the
     // caller's pending retune, as they were - the next submit tries again)
     for (int i = 0; i < n; i++) {
@@ -1062,8 +1052,8 @@ extern "C" int rd_chan_set_gain(rd_chan *h, const double *gain, int n) {
     std::vector<float> g(n);
     for (int c = 0; c < n; c++) g[c] = (float)gain[c];
     if (h->dev_ready) {
-        if (h->device >= 0) CHK(hipSetDevice(h->device));
-        CHK(hipMemcpy(h->d_gains, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (h->device >= 0) HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpy(h->d_gains, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     h->gains = g;   // (before the device tables exist chan_alloc uploads them)
     return RD_OK;
@@ -1083,7 +1073,7 @@ int rd_chan_stream_gains(rd_chan *h, const float *gain, int slot, hipStream_t st
         if (!h->h_gains) return rd_fail_msg(RD_ERR_STATE, "rd_chan_stream_prepare first");
         float *stage = h->h_gains + (size_t)slot * n;
         memcpy(stage, gain, n * sizeof(float));
-        CHK(hipMemcpyAsync(h->d_gains, stage, n * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(h->d_gains, stage, n * sizeof(float), hipMemcpyHostToDevice, st));
     }
     h->gains.assign(gain, gain + n);
     return RD_OK;
@@ -1104,7 +1094,7 @@ int rd_chan_stream_levels(rd_chan *h, const uint8_t *wide, size_t n_out, const u
     hipLaunchKernelGGL(k_chan_levels, dim3((unsigned)n_ch + n_in), dim3(RD_LV_THREADS), 0, st, (const uint4 *)chan_out,
                        out_stride / 16, ch_vec, n_ch, (const float *)h->d_gains, (const uint4 *)wide, in_vec, h->fmt, n_in,
                        seq, out, in, acc);
-    CHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return RD_OK;
 }
 

@@ -186,25 +186,16 @@ static int rd_cd_check_config(const rd_config *cfg) {
     return rd_burst_decode_check(&c);
 }
 
-// every host wait of the library has this deadline (rd_host.h: rd_waiter)
+// the library's polling wait with its deadline (rd_hiphost.h); a wait that gave up leaves the handle busy
 static int rd_cd_wait(rd_clips *h, const char *what) {
-    rd_waiter w(rd_wait_timeout_ms());
-    for (;;) {
-        const hipError_t e = hipStreamQuery(h->st);
-        if (e == hipSuccess) {
-            h->busy = false;
-            return RD_OK;
-        }
-        if (e != hipErrorNotReady) return rd_fail_msg(RD_ERR_DEVICE, "clip decode: hipStreamQuery: %s", hipGetErrorString(e));
-        if (!w.relax()) {
-            h->busy = true;
-            return rd_fail_msg(RD_ERR_DEVICE, "clip decode: timed out after %.0f ms waiting for %s", w.waited_ms(), what);
-        }
-    }
+    const int rc = rd_wait_stream(h->st, what);
+    if (!rc) h->busy = false;
+    else if (hipStreamQuery(h->st) == hipErrorNotReady) h->busy = true;
+    return rc ? rd_fail_msg(rc, "clip decode: %s", rd_last_error()) : RD_OK;
 }
 
 static int rd_cd_prepare(rd_clips *h) {
-    int rc = rd_ensure_device_public();
+    int rc = rd_ensure_device();
     if (rc) return rc;
     if (!h->st) {
         if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||

@@ -757,7 +757,7 @@ static int rd_mf_env(const char *name, int dflt) {
 }
 
 // Launch parameters read once per process.  A function-local static: initialised exactly once, also when several
-// threads make their first launch together (handles may be used from several threads, rd_api.hip).
+// threads make their first launch together (handles may be used from several threads, rd_batch.hip).
 struct rd_mf_params {
     int dbg = 0, stamp = 0, chunk_env = 0, per_cu_env = 0, n_cu = 256, test_wgs = 0;
     uint32_t stflags = 0;
@@ -927,7 +927,7 @@ int rd_launch_demod_mfma(const rd_layout &lay, uint32_t *fix_list, uint32_t fix_
     return a.bucket_cnt != nullptr ? 1 : 0;
 }
 
-// tiles per chunk and waves of the hook's last launch (rd_api.hip: rd_k1_schedule with a null handle)
+// tiles per chunk and waves of the hook's last launch (rd_batch.hip: rd_k1_schedule with a null handle)
 static uint32_t g_dbg_launch[2] = {0, 0};
 void rd_debug_last_launch(uint32_t out[2]) { out[0] = g_dbg_launch[0]; out[1] = g_dbg_launch[1]; }
 
@@ -939,7 +939,7 @@ void rd_debug_last_launch(uint32_t out[2]) { out[0] = g_dbg_launch[0]; out[1] = 
 extern "C" int rd_debug_demod_mfma(const uint8_t *iq_host, int n_streams, uint32_t n_samples, int hist_mode,
                                    uint32_t hist_bytes, float *g_out, uint32_t *bits_out, uint32_t *fix_out,
                                    uint32_t fix_cap, uint32_t *n_fix) {
-    int rc = rd_ensure_device_public();
+    int rc = rd_ensure_device();
     if (rc) return rc;
     const size_t stride = (size_t)n_samples * 2 + (hist_mode ? hist_bytes : 0);
     if (stride % 16 || (hist_mode && hist_bytes % 16)) return RD_ERR_ARG;

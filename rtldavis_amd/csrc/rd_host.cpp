@@ -538,3 +538,53 @@ int rd_collect_clips(const void *slot, int n_ch, int quota, long chunk, std::vec
     }
     return RD_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// the streaming demodulator's fetch (rd_host.h: rd_collect_block), a batch run's parsed messages (rd_order_parsed)
+// ------------------------------------------------------------------------------------------
+void rd_collect_block(const uint32_t *counts, size_t n_lists, size_t per, const rd_packet *recs, const int32_t *fe, int S,
+                      rd_block_scratch &sc, std::vector<rd_packet> &last, std::vector<rd_parsed> &parsed) {
+    sc.recs.clear();
+    sc.fe.clear();
+    for (size_t l = 0; l < n_lists; l++) {
+        const size_t c = std::min<size_t>(counts[l], per);
+        sc.recs.insert(sc.recs.end(), recs + l * per, recs + l * per + c);
+        if (fe) sc.fe.insert(sc.fe.end(), fe + l * per, fe + l * per + c);
+    }
+    rd_order_and_dedupe(sc.recs.data(), sc.recs.size(), S, sc.order);
+    last.clear();
+    parsed.clear();
+    for (uint32_t k : sc.order.kept) {
+        const rd_packet &r = sc.recs[k];
+        last.push_back(r);
+        if (!fe || sc.fe[k] == RD_FE_NONE) continue;
+        rd_parsed m;
+        memset(&m, 0, sizeof m);
+        m.stream = r.stream; m.call = r.call; m.index = r.index; m.freq_err = sc.fe[k];
+        m.nbytes = r.nbytes - 2;
+        for (int b = 2; b < r.nbytes && b < RD_MAX_PKT_BYTES; b++) m.data[b - 2] = (uint8_t)rd_swap_bits8(r.data[b]);
+        m.id = m.data[0] & 7;
+        m.rssi = r.rssi; m.snr = r.snr;
+        parsed.push_back(m);
+    }
+}
+
+size_t rd_order_parsed(rd_parsed *recs, size_t n, int S) {
+    std::sort(recs, recs + n, [S](const rd_parsed &x, const rd_parsed &y) {
+        if (x.stream != y.stream) return x.stream < y.stream;
+        if (x.call != y.call) return x.call < y.call;
+        const int px = x.index % S, py = y.index % S;
+        if (px != py) return px < py;
+        return x.index < y.index;
+    });
+    size_t kept = 0, group = 0;
+    for (size_t i = 0; i < n; i++) {
+        const rd_parsed &r = recs[i];
+        if (kept == 0 || r.stream != recs[kept - 1].stream || r.call != recs[kept - 1].call) group = kept;
+        bool dup = false;
+        for (size_t k = group; k < kept && !dup; k++)
+            dup = recs[k].nbytes == r.nbytes && memcmp(recs[k].data, r.data, sizeof r.data) == 0;
+        if (!dup) recs[kept++] = r;
+    }
+    return kept;
+}

@@ -12,6 +12,8 @@
 //   rd_msg_repeats        steps 7, 7' and 7s: a record that reports again what the fetch of the chunk before delivered
 //   rd_delivered          ... and what that fetch delivered
 //   rd_collect_*          the receiver's fetch: one slot's records into the handle's vectors, every count checked first
+//   rd_collect_block      the streaming demodulator's fetch: one slot's records, ordered, and their parsed messages
+//   rd_order_parsed       a batch run's parsed messages in the order parse() sees them, a call's repeats dropped
 // py = /root/reference/src/rtldavis/dsp.py
 #pragma once
 #include <stddef.h>
@@ -105,6 +107,27 @@ int rd_collect_search(const void *slot, int n_ch, long chunk, int sl, int n, rd_
 // those are copied, packed channel after channel, and `offset` is rewritten to match
 int rd_collect_clips(const void *slot, int n_ch, int quota, long chunk, std::vector<rd_burst_clip> &clips, std::vector<uint8_t> &bytes,
                      std::vector<uint32_t> &dropped, rd_errtext *err);
+
+// The streaming demodulator's fetch (rd_stream.hip: demod_fetch) of one slot, which the block's kernels wrote into mapped
+// memory and which is only read.  counts: n_lists counts; list i's records are the first counts[i] of the `per` places
+// from recs + i * per - the one-launch form has a list per stream with per = B + 1, the multi-launch form one list of
+// match_cap places.  A count beyond `per` is clamped to it, so no place outside the slot is read.  fe: null (the block
+// was submitted with parse off) or the entries beside the record places: RD_FE_NONE or the record's frequency error.
+// last: the records in the reference's order, per-call duplicates gone (rd_order_and_dedupe).  parsed: of those, the ones
+// the device found CRC-valid, as messages with the bytes swapped here (rd_parse.h) - the parser's own dedupe on the
+// swapped bytes (protocol.py:293-295) has nothing left to drop: the swap is a bijection and the per-call dedupe has run.
+struct rd_block_scratch {  // kept per handle: no allocation per call once warm
+    std::vector<rd_packet> recs;
+    std::vector<int32_t> fe;
+    rd_order_scratch order;
+};
+void rd_collect_block(const uint32_t *counts, size_t n_lists, size_t per, const rd_packet *recs, const int32_t *fe, int S,
+                      rd_block_scratch &sc, std::vector<rd_packet> &last, std::vector<rd_parsed> &parsed);
+// The parsed messages of a batch run, in place, into the order parse() sees them - packets of a call in _slice's order:
+// (stream, call, index % S, index) - with a call's repeated byte strings dropped (py:203-205, the first occurrence wins:
+// messages with equal bytes come from packets with equal bytes, the sync word being the matched preamble).  Returns how
+// many are kept, at the front.
+size_t rd_order_parsed(rd_parsed *recs, size_t n, int S);
 
 // BURST EXPECT (include/rtldavis_hip.h), the host's parts.
 // rd_bx_check_table: RD_OK, or RD_ERR_ARG with *bad = the first offending entry (-1: n itself) and *why naming the rule.

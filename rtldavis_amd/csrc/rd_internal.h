@@ -1,9 +1,11 @@
-// rd_internal.h - launch interface between rd_api.hip (host logic, C ABI) and rd_kernels.hip.
+// rd_internal.h - launch interface between the host logic of the C ABI (rd_batch.hip, rd_stream.hip, rd_stages.hip,
+// rd_wideband.hip) and the kernels' translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/rtldavis_hip.h"
+#include "rd_hiphost.h"
 #include "rd_host.h"
 
 // counters[] slots (device uint32)
@@ -60,8 +62,12 @@ struct rd_match {
     int32_t pos;  // bit-array coordinate of the first preamble sample
 };
 
-// lazy, fork-aware HIP initialisation (rd_api.hip); RD_OK or RD_ERR_DEVICE
-int rd_ensure_device_public(void);
+// rd_make_devcfg (rd_host.h) with its reason as the error text
+static inline int rd_devcfg_checked(const rd_config *c, rd_devcfg *d) {
+    const char *why = "";
+    const int rc = rd_make_devcfg(c, d, &why);
+    return rc ? rd_fail_msg(rc, "%s", why) : RD_OK;
+}
 
 // --- launches (all asynchronous on `st`) ---
 // ev_start / ev_stop (optional): events that receive the kernel's own begin / end timestamps.
@@ -330,7 +336,7 @@ int rd_chan_n_channels(const rd_chan *h);
 int64_t rd_chan_out_rate(const rd_chan *h);
 int64_t rd_chan_wide_rate(const rd_chan *h);
 int rd_chan_bytes_per_sample(const rd_chan *h);   // of an IQ pair in the handle's sample format
-// rd_api.hip: the handle's device state and its two non-blocking streams (compute, copy)
+// rd_stream.hip: the handle's device state and its two non-blocking streams (compute, copy)
 int rd_demod_prepare(rd_demod *h, hipStream_t *st, hipStream_t *st_copy);
 // drop the blocks a timed-out fetch gave up on, then RD_ERR_STATE if two blocks are in flight
 int rd_demod_check_room(rd_demod *h);

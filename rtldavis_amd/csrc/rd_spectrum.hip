@@ -34,19 +34,11 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include <unistd.h>
 
 #include <hip/hip_runtime.h>
 
 #include "rd_internal.h"
 
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
-#define SCHK(x)                                                                                             \
-    do {                                                                                                    \
-        hipError_t e_ = (x);                                                                                \
-        if (e_ != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));      \
-    } while (0)
 
 #define RD_SP_THREADS 256
 #define RD_SP_MAX_BINS 4096
@@ -193,7 +185,6 @@ struct rd_spec {
     float2 *d_tw = nullptr;
     double *d_part = nullptr;
     uint32_t *d_ticket = nullptr;
-    pid_t pid = 0;
 };
 
 static const void *sp_kernel(int fmt) {
@@ -220,7 +211,7 @@ static unsigned sp_groups(int n_bins, size_t n_samples) {
 
 void rd_spec_destroy(rd_spec *sp) {
     if (!sp) return;
-    if (sp->pid == getpid()) {   // (device memory belongs to the process that allocated it)
+    if (rd_owns_device_state()) {   // (device memory belongs to the process that allocated it)
         hipFree(sp->d_win); hipFree(sp->d_tw); hipFree(sp->d_part); hipFree(sp->d_ticket);
     }
     delete sp;
@@ -235,7 +226,6 @@ int rd_spec_prepare(rd_spec **spp, int n_bins, size_t n_samples, hipStream_t st)
     rd_spec_destroy(*spp);
     *spp = nullptr;
     rd_spec *sp = new rd_spec();
-    sp->pid = getpid();
     sp->n = n_bins;
     while ((1 << sp->log2n) < n_bins) sp->log2n++;
     sp->groups = groups;
@@ -289,7 +279,7 @@ int rd_spec_launch(rd_spec *sp, const uint8_t *wide, int fmt, size_t n_samples, 
     double scale = 1.0 / ((double)n_seg * (double)(n / 2) * (double)(n / 2));
     uint8_t *o = (uint8_t *)out;
     void *args[] = {&wide, &n, &log2n, &segs, &win, &tw, &part, &ticket, &scale, &seq, &o};   // k_chan_spectrum's parameters, in order
-    SCHK(hipLaunchKernel(sp_kernel(fmt), dim3(groups), dim3(RD_SP_THREADS), args, sp_lds_bytes(n), st));
-    SCHK(hipGetLastError());
+    HIPCHK(hipLaunchKernel(sp_kernel(fmt), dim3(groups), dim3(RD_SP_THREADS), args, sp_lds_bytes(n), st));
+    HIPCHK(hipGetLastError());
     return RD_OK;
 }

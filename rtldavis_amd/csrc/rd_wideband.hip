@@ -19,19 +19,10 @@
 // argument that its slot is free and its inputs are ordered stands with each stage.
 #include <cstring>
 #include <vector>
-#include <unistd.h>
 
 #include <hip/hip_runtime.h>
 
 #include "rd_internal.h"
-
-extern int rd_fail_msg(int code, const char *fmt, ...);  // rd_api.hip: sets rd_last_error
-
-#define WCHK(x)                                                                                             \
-    do {                                                                                                    \
-        hipError_t e_ = (x);                                                                                \
-        if (e_ != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));      \
-    } while (0)
 
 // A pair of mapped pinned slots, one per chunk parity: a stage's kernel writes slot s through d[s], the fetch reads h[s].
 // [fill, fill + fill_len) is the part that must never pass for a chunk's: 0xFF at allocation and after reset(), a
@@ -91,7 +82,6 @@ struct rd_wideband {
     long n_sub = 0;               // chunks submitted since create / reset (chunk k uses buffers k & 1)
     long last = -1;               // chunk the last fetch returned
     bool dev_ready = false;
-    pid_t pid = 0;
     hipStream_t st = nullptr, st_copy = nullptr;   // the demodulator's streams
     uint8_t *h_in[2] = {nullptr, nullptr};         // pinned staging of the host's chunk
     uint8_t *d_wide[2] = {nullptr, nullptr};       // device chunk buffers
@@ -226,7 +216,7 @@ extern "C" int rd_wb_create_fmt(const rd_config *cfg, const rd_chan_config *ccfg
 extern "C" void rd_wideband_destroy(rd_wideband *w) {
     if (!w) return;
     rd_destroy(w->dem);   // (waits for its streams, which carry all of this handle's work)
-    if (w->dev_ready && w->pid == getpid()) {
+    if (w->dev_ready && rd_owns_device_state()) {
         for (int i = 0; i < 2; i++) {
             hipHostFree(w->h_in[i]); hipFree(w->d_wide[i]); hipFree(w->d_out[i]);
             if (w->e_in[i]) hipEventDestroy(w->e_in[i]);
@@ -247,14 +237,13 @@ static int wb_alloc(rd_wideband *w) {
     if (rc || w->dev_ready) return rc;
     rc = rd_chan_stream_prepare(w->chan);
     if (rc) return rc;
-    w->pid = getpid();
     const size_t out_bytes = (size_t)w->n_ch * 2 * w->B + RD_INPUT_PAD;
     for (int i = 0; i < 2; i++) {
-        WCHK(hipHostMalloc((void **)&w->h_in[i], w->chunk_bytes, hipHostMallocDefault));
-        WCHK(hipMalloc(&w->d_wide[i], w->chunk_bytes + 16));
-        WCHK(hipMalloc(&w->d_out[i], out_bytes));
-        WCHK(hipEventCreateWithFlags(&w->e_in[i], hipEventDisableTiming));
-        WCHK(hipEventCreateWithFlags(&w->e_chan[i], hipEventDisableTiming));
+        HIPCHK(hipHostMalloc((void **)&w->h_in[i], w->chunk_bytes, hipHostMallocDefault));
+        HIPCHK(hipMalloc(&w->d_wide[i], w->chunk_bytes + 16));
+        HIPCHK(hipMalloc(&w->d_out[i], out_bytes));
+        HIPCHK(hipEventCreateWithFlags(&w->e_in[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&w->e_chan[i], hipEventDisableTiming));
     }
     w->dev_ready = true;
     return RD_OK;
@@ -268,7 +257,7 @@ static size_t wb_wide_samples(const rd_wideband *w) { return w->chunk_bytes / (s
 static int wb_prepare_tables(rd_wideband *w) {
     if (w->levels && !w->d_lvacc) {
         uint32_t *acc = nullptr;
-        WCHK(hipMalloc(&acc, RD_LV_ACC_WORDS * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&acc, RD_LV_ACC_WORDS * sizeof(uint32_t)));
         hipError_t e = hipMemsetAsync(acc, 0, RD_LV_ACC_WORDS * sizeof(uint32_t), w->st);   // (ordered before the first launch)
         if (e != hipSuccess) { hipFree(acc); return rd_fail_msg(RD_ERR_DEVICE, "hipMemsetAsync: %s", hipGetErrorString(e)); }
         w->d_lvacc = acc;
@@ -789,20 +778,20 @@ extern "C" int rd_wideband_submit(rd_wideband *w, const void *wide_iq, size_t nb
     const bool prev = w->n_sub >= 1;
     const wb_chunk c = {s, (uint64_t)w->n_sub, prev ? 1 : 0, prev ? w->d_out[s ^ 1] : nullptr};
     // the pinned slot's previous copy (chunk k-2) has completed: its demod block has been fetched or dropped
-    if (w->n_sub >= 2) WCHK(hipEventSynchronize(w->e_in[s]));
+    if (w->n_sub >= 2) HIPCHK(hipEventSynchronize(w->e_in[s]));
     memcpy(w->h_in[s], wide_iq, nbytes);
     // buffer s holds chunk k-2, the history chunk k-1's channelizer reads: overwrite it once that has run
-    if (prev) WCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s ^ 1], 0));
-    WCHK(hipMemcpyAsync(w->d_wide[s], w->h_in[s], nbytes, hipMemcpyHostToDevice, w->st_copy));
-    WCHK(hipEventRecord(w->e_in[s], w->st_copy));
+    if (prev) HIPCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s ^ 1], 0));
+    HIPCHK(hipMemcpyAsync(w->d_wide[s], w->h_in[s], nbytes, hipMemcpyHostToDevice, w->st_copy));
+    HIPCHK(hipEventRecord(w->e_in[s], w->st_copy));
     // The retune records and the gain table travel through pinned slots of parity s as well, copied on the COMPUTE stream:
     // e_in[s] above (the copy stream's event) does not order that copy; they are free by wb_chunk's argument.
     if ((rc = wb_apply_tuning(w, s))) return rc;
     if ((rc = rd_chan_stream_gains(w->chan, w->gain.data(), s, w->st))) return rc;
-    WCHK(hipStreamWaitEvent(w->st, w->e_in[s], 0));
+    HIPCHK(hipStreamWaitEvent(w->st, w->e_in[s], 0));
     rc = rd_chan_stream_launch(w->chan, w->d_wide[s], prev ? w->d_wide[s ^ 1] : nullptr, w->B, w->clock, w->d_out[s], 2 * w->B, w->st);
     if (rc) return rc;
-    WCHK(hipEventRecord(w->e_chan[s], w->st));
+    HIPCHK(hipEventRecord(w->e_chan[s], w->st));
     if (w->levels && (rc = wb_queue_levels(w, c))) return rc;
     if (w->spec_n && (rc = wb_queue_spectrum(w, c))) return rc;
     w->note[s] = wb_note();   // (whatever chunk k-2 was submitted with: this chunk has a feature only once its launch is queued)
@@ -881,9 +870,9 @@ extern "C" int rd_wideband_copy_channelized(rd_wideband *w, uint8_t *out, size_t
     if (w->last < 0) return rd_fail_msg(RD_ERR_STATE, "no chunk fetched since create / reset");
     if (w->n_sub - w->last > 2) return rd_fail_msg(RD_ERR_STATE, "the last fetched chunk's buffer has been reused by a later submit");
     const int s = (int)(w->last & 1);
-    WCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s], 0));
-    WCHK(hipMemcpyAsync(out, w->d_out[s], need, hipMemcpyDeviceToHost, w->st_copy));
-    WCHK(hipStreamSynchronize(w->st_copy));
+    HIPCHK(hipStreamWaitEvent(w->st_copy, w->e_chan[s], 0));
+    HIPCHK(hipMemcpyAsync(out, w->d_out[s], need, hipMemcpyDeviceToHost, w->st_copy));
+    HIPCHK(hipStreamSynchronize(w->st_copy));
     return RD_OK;
 }
 

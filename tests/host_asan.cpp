@@ -8,9 +8,13 @@
 //   host_asan config <rounds> <seed>   rd_make_devcfg / rd_check_block_count / rd_ord_bucket_cap on random and extreme input
 //   host_asan waiter                   rd_waiter: deadline 0, a short deadline, the override hook
 //   host_asan repeats <msgs> <delivered> <out> <SL>   rd_burst_msg records through rd_bd_repeats, kept indices (uint32) to <out>
+//   host_asan block <n_lists> <per> <S> <counts> <recs> <fe|-> <last> <parsed>   one streaming slot through rd_collect_block
+//   host_asan parsed <in> <out> <S>    rd_parsed records from <in> through rd_order_parsed, the kept ones to <out>
+//   host_asan parsed-soak <rounds> <seed>   random rd_parsed sets through rd_order_parsed against a naive model
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <vector>
 #include <algorithm>
@@ -174,11 +178,128 @@ static int repeats_mode(const char *msgs, const char *delivered, const char *out
     return 0;
 }
 
+// A file's bytes in a heap block of exactly its size (what a slot is to the fetch: one byte past it is a sanitizer report);
+// false unless it holds `want` bytes
+static bool exact_block(const char *path, size_t want, std::unique_ptr<uint8_t[]> *blk) {
+    FILE *f = fopen(path, "rb");
+    if (!f) return false;
+    blk->reset(new uint8_t[want]);
+    uint8_t more;
+    const bool ok = fread(blk->get(), 1, want, f) == want && fread(&more, 1, 1, f) == 0;
+    fclose(f);
+    return ok;
+}
+
+static bool write_all(const char *path, const void *p, size_t n) {
+    FILE *f = fopen(path, "wb");
+    if (!f) return false;
+    const bool ok = n == 0 || fwrite(p, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
+}
+
+// The streaming demodulator's fetch of one slot: n_lists counts, n_lists x per record places and (fe != "-") as many fe
+// entries, each from its file into a heap block of exactly that size; the kept records and the messages go to the outputs.
+// Run twice on one scratch, like a handle's second fetch: the outputs must not change.
+static int block_mode(size_t n_lists, size_t per, int S, const char *counts, const char *recs, const char *fe, const char *last_out,
+                      const char *parsed_out) {
+    std::unique_ptr<uint8_t[]> c, r, e;
+    const bool parse = strcmp(fe, "-") != 0;
+    if (!exact_block(counts, n_lists * sizeof(uint32_t), &c) || !exact_block(recs, n_lists * per * sizeof(rd_packet), &r) ||
+        (parse && !exact_block(fe, n_lists * per * sizeof(int32_t), &e)))
+        return fail("a slot file of the wrong size");
+    rd_block_scratch sc;
+    std::vector<rd_packet> last, last2;
+    std::vector<rd_parsed> parsed, parsed2;
+    rd_collect_block((const uint32_t *)c.get(), n_lists, per, (const rd_packet *)r.get(), parse ? (const int32_t *)e.get() : nullptr, S, sc,
+                     last2, parsed2);
+    rd_collect_block((const uint32_t *)c.get(), n_lists, per, (const rd_packet *)r.get(), parse ? (const int32_t *)e.get() : nullptr, S, sc,
+                     last, parsed);
+    if (last.size() != last2.size() || parsed.size() != parsed2.size() ||
+        (!last.empty() && memcmp(last.data(), last2.data(), last.size() * sizeof(rd_packet))) ||
+        (!parsed.empty() && memcmp(parsed.data(), parsed2.data(), parsed.size() * sizeof(rd_parsed))))
+        return fail("a second fetch of the same slot gave something else");
+    if (!parse && !parsed.empty()) return fail("messages from a block submitted with parse off");
+    if (!write_all(last_out, last.data(), last.size() * sizeof(rd_packet)) || !write_all(parsed_out, parsed.data(), parsed.size() * sizeof(rd_parsed)))
+        return fail("cannot write the outputs");
+    printf("block ok: %zu records, %zu messages\n", last.size(), parsed.size());
+    return 0;
+}
+
+// rd_order_parsed's rule, spelled out naively: stable order by (stream, call, index % S, index), then the first occurrence
+// of (nbytes, all of data) inside (stream, call) wins
+static std::vector<rd_parsed> naive_parsed(std::vector<rd_parsed> r, int S) {
+    std::stable_sort(r.begin(), r.end(), [S](const rd_parsed &x, const rd_parsed &y) {
+        if (x.stream != y.stream) return x.stream < y.stream;
+        if (x.call != y.call) return x.call < y.call;
+        if (x.index % S != y.index % S) return x.index % S < y.index % S;
+        return x.index < y.index;
+    });
+    std::vector<rd_parsed> kept;
+    for (const rd_parsed &m : r) {
+        bool dup = false;
+        for (const rd_parsed &k : kept)
+            if (k.stream == m.stream && k.call == m.call && k.nbytes == m.nbytes && !memcmp(k.data, m.data, sizeof m.data)) { dup = true; break; }
+        if (!dup) kept.push_back(m);
+    }
+    return kept;
+}
+
+static int parsed_file_mode(const char *in, const char *out, int S) {
+    FILE *f = fopen(in, "rb");
+    if (!f) return fail("cannot open input");
+    std::vector<rd_parsed> r;
+    rd_parsed p;
+    while (fread(&p, sizeof p, 1, f) == 1) r.push_back(p);
+    fclose(f);
+    std::vector<rd_parsed> exact(r);   // (capacity = size: the call may not touch a place past the last record)
+    exact.shrink_to_fit();
+    const size_t kept = rd_order_parsed(exact.data(), exact.size(), S);
+    if (kept > exact.size()) return fail("kept more than there were");
+    if (!write_all(out, exact.data(), kept * sizeof(rd_parsed))) return fail("cannot write the output");
+    printf("parsed ok: %zu of %zu\n", kept, r.size());
+    return 0;
+}
+
+// a few and a few thousand records; few distinct payloads, a function of the position like a real message's bytes, so
+// that equal-bytes groups occur inside a (stream, call) and across them, and records with equal keys are equal
+static int parsed_soak(int rounds, unsigned seed) {
+    std::mt19937 g(seed);
+    for (int round = 0; round < rounds; round++) {
+        const int S = 1 + (int)(g() % 20);
+        const size_t n = (round % 3 == 0) ? g() % 12 : (round % 3 == 1) ? 100 + g() % 300 : 2000 + g() % 3000;
+        const int n_streams = 1 + (int)(g() % 6), n_calls = 1 + (int)(g() % 8), n_index = 1 + (int)(g() % 9000), n_payloads = 1 + (int)(g() % 5);
+        std::vector<rd_parsed> r(n);
+        for (auto &m : r) {
+            memset(&m, 0, sizeof m);
+            m.stream = (int)(g() % n_streams);
+            m.call = (int)(g() % n_calls);
+            m.index = (int)(g() % n_index);
+            const unsigned pay = (unsigned)(m.index % n_payloads);
+            m.nbytes = 8 - (int)(pay & 1u);             // (equal leading bytes with another length are another message)
+            for (int k = 0; k < m.nbytes; k++) m.data[k] = (uint8_t)((pay >> 1) * 37 + k);
+            m.id = m.data[0] & 7;
+            m.freq_err = m.index - 4000;
+        }
+        const std::vector<rd_parsed> want = naive_parsed(r, S);
+        r.shrink_to_fit();
+        const size_t kept = rd_order_parsed(r.data(), r.size(), S);
+        if (kept != want.size()) return fail("kept count differs from the naive model");
+        if (kept && memcmp(r.data(), want.data(), kept * sizeof(rd_parsed))) return fail("kept messages differ from the naive model");
+    }
+    if (rd_order_parsed(nullptr, 0, 14) != 0) return fail("empty input kept something");
+    printf("parsed soak ok: %d rounds\n", rounds);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 10 && !strcmp(argv[1], "block"))
+        return block_mode((size_t)atol(argv[2]), (size_t)atol(argv[3]), atoi(argv[4]), argv[5], argv[6], argv[7], argv[8], argv[9]);
+    if (argc >= 5 && !strcmp(argv[1], "parsed")) return parsed_file_mode(argv[2], argv[3], atoi(argv[4]));
+    if (argc >= 4 && !strcmp(argv[1], "parsed-soak")) return parsed_soak(atoi(argv[2]), (unsigned)atoi(argv[3]));
     if (argc >= 6 && !strcmp(argv[1], "repeats")) return repeats_mode(argv[2], argv[3], argv[4], atoi(argv[5]));
     if (argc >= 4 && !strcmp(argv[1], "soak")) return soak(atoi(argv[2]), (unsigned)atoi(argv[3]));
     if (argc >= 5 && !strcmp(argv[1], "file")) return file_mode(argv[2], argv[3], atoi(argv[4]));
     if (argc >= 4 && !strcmp(argv[1], "config")) return config(atoi(argv[2]), (unsigned)atoi(argv[3]));
     if (argc >= 2 && !strcmp(argv[1], "waiter")) return waiter();
-    return fail("usage: soak <rounds> <seed> | file <in> <out> <S> | config <rounds> <seed> | waiter");
+    return fail("usage: soak <rounds> <seed> | file <in> <out> <S> | config <rounds> <seed> | waiter | repeats .. | block .. | parsed .. | parsed-soak ..");
 }

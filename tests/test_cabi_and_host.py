@@ -187,3 +187,171 @@ def test_traffic_stamp_of_the_built_demod_kernel():
     with open(os.path.join(ROOT, "profiles", "r03_traffic.json")) as fh:
         tj = json.load(fh)
     assert len(tj["kernel_isa_sha256"]) == 64 and tj["traffic_bytes"] > tj["algorithmic_bytes"]
+
+
+def _refusal_env():
+    import ctypes as C
+    from rtldavis_amd import _lib, dsp
+    from rtldavis_amd.dsp import _cfg_struct
+    L = _lib.lib()
+    cfg = _cfg_struct(dsp.PacketConfig(19200, 14, 16, 80, "1100101110001001", 512))
+    handles = {}
+    for name, ns in (("h1", 1), ("h3", 3)):
+        h = C.c_void_p()
+        assert L.rd_create_multi(C.byref(cfg), ns, C.byref(h)) == _lib.RD_OK
+        handles[name] = h
+    return C, _lib, L, cfg, handles
+
+
+def test_streaming_refusals_decided_before_any_device_call():
+    """Every argument and state refusal of the streaming entry points that is decided before a device call, on fresh
+    handles (rd_create is lazy: no GPU needed) of block_size 512 - B = 512, L = 2048 - with one stream and with three:
+    the return code and the whole rd_last_error text, and which refusal wins where two apply."""
+    C, _lib, L, _, hs = _refusal_env()
+    h1, h3 = hs["h1"], hs["h3"]
+    ARG, STATE, OK = _lib.RD_ERR_ARG, _lib.RD_ERR_STATE, _lib.RD_OK
+    buf = np.ones(4 * 3072, np.float64)        # never read: every row below is refused first
+    p = buf.ctypes.data_as(C.c_void_p)
+    n = C.c_int(-7)
+    pn = C.byref(n)
+    sizes = "Incompatible array sizes: got %d, expected %d"
+    rows = [
+        # rd_demod_submit(h, samples, count, is_complex)
+        (L.rd_demod_submit, (None, p, 1024, 0), ARG, "null argument"),
+        (L.rd_demod_submit, (h1, None, 1024, 0), ARG, "null argument"),
+        (L.rd_demod_submit, (h1, p, 1023, 0), ARG, sizes % (1023, 1024)),
+        (L.rd_demod_submit, (h1, p, 512, 0), ARG, sizes % (512, 1024)),
+        (L.rd_demod_submit, (h1, p, 1024, 1), ARG, sizes % (1024, 512)),
+        (L.rd_demod_submit, (h1, p, 0, 1), ARG, sizes % (0, 512)),
+        (L.rd_demod_submit, (h3, p, 1024, 0), ARG, sizes % (1024, 3072)),
+        (L.rd_demod_submit, (h3, p, 512, 1), STATE, "complex input needs a single-stream handle"),
+        (L.rd_demod_submit, (h3, p, 7, 1), STATE, "complex input needs a single-stream handle"),   # (before the size)
+        (L.rd_demod_submit, (h3, None, 7, 1), ARG, "null argument"),                                 # (before both)
+        # rd_demod_submit_from(h, offset, count, is_complex): no buffer registered, whatever else is wrong
+        (L.rd_demod_submit_from, (None, 0, 1024, 0), ARG, "null handle"),
+        (L.rd_demod_submit_from, (h1, 0, 1024, 0), STATE, "no input buffer registered (rd_demod_register_input)"),
+        (L.rd_demod_submit_from, (h1, 8, 1000, 0), STATE, "no input buffer registered (rd_demod_register_input)"),
+        (L.rd_demod_submit_from, (h3, 0, 512, 1), STATE, "no input buffer registered (rd_demod_register_input)"),
+        # rd_demod_block(h, samples, count, is_complex, out, cap, n)
+        (L.rd_demod_block, (None, p, 1024, 0, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_block, (h1, None, 1024, 0, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_block, (h1, p, 1024, 0, None, 0, None), ARG, "null argument"),
+        (L.rd_demod_block, (h3, p, 3072, 0, None, 0, pn), STATE, "handle holds 3 streams: use rd_demod_blocks"),
+        (L.rd_demod_block, (h3, p, 5, 1, None, 0, pn), STATE, "handle holds 3 streams: use rd_demod_blocks"),   # (before the size)
+        (L.rd_demod_block, (h1, p, 1000, 0, None, 0, pn), ARG, sizes % (1000, 1024)),
+        (L.rd_demod_block, (h1, p, 1024, 1, None, 0, pn), ARG, sizes % (1024, 512)),
+        (L.rd_demod_block, (h1, p, 513, 1, None, 0, pn), ARG, sizes % (513, 512)),
+        # rd_demod_blocks(h, iq, nbytes, out, cap, n): the one that says "bytes"
+        (L.rd_demod_blocks, (None, p, 1024, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_blocks, (h1, None, 1024, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_blocks, (h1, p, 1024, None, 0, None), ARG, "null argument"),
+        (L.rd_demod_blocks, (h1, p, 1000, None, 0, pn), ARG, "Incompatible array sizes: got 1000 bytes, expected 1024"),
+        (L.rd_demod_blocks, (h3, p, 1024, None, 0, pn), ARG, "Incompatible array sizes: got 1024 bytes, expected 3072"),
+        (L.rd_demod_blocks, (h3, p, 3073, None, 0, pn), ARG, "Incompatible array sizes: got 3073 bytes, expected 3072"),
+        # fetch / parsed / set_parse on a handle that has seen no block
+        (L.rd_demod_fetch, (None, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_fetch, (h1, None, 0, None), ARG, "null argument"),
+        (L.rd_demod_fetch, (h1, None, 0, pn), STATE, "no block in flight"),
+        (L.rd_demod_fetch, (h3, None, 0, pn), STATE, "no block in flight"),
+        (L.rd_demod_refetch, (None, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_refetch, (h1, None, 0, None), ARG, "null argument"),
+        (L.rd_demod_parsed, (None, None, 0, pn), ARG, "null argument"),
+        (L.rd_demod_parsed, (h1, None, 0, None), ARG, "null argument"),
+        (L.rd_demod_parsed, (h1, None, 0, pn), STATE, "no block fetched since create / reset"),
+        (L.rd_demod_set_parse, (None, 1), ARG, "null handle"),
+        # state accessors: rd_copy_discriminated_stream(h, stream, out, n), rd_copy_filtered(h, out, n), rd_copy_quantized(h, out, n)
+        (L.rd_copy_discriminated_stream, (None, 0, p, 1024), ARG, "null argument"),
+        (L.rd_copy_discriminated_stream, (h1, 0, None, 1024), ARG, "null argument"),
+        (L.rd_copy_discriminated_stream, (h1, 1, p, 1024), ARG, "stream out of range"),
+        (L.rd_copy_discriminated_stream, (h1, -1, p, 1024), ARG, "stream out of range"),
+        (L.rd_copy_discriminated_stream, (h3, 3, p, 7), ARG, "stream out of range"),                 # (before the size)
+        (L.rd_copy_discriminated_stream, (h3, 2, p, 1023), ARG, "discriminated has 1024 elements"),
+        (L.rd_copy_discriminated, (None, p, 1024), ARG, "null argument"),
+        (L.rd_copy_discriminated, (h1, p, 512), ARG, "discriminated has 1024 elements"),
+        (L.rd_copy_filtered, (None, p, 513), ARG, "null argument"),
+        (L.rd_copy_filtered, (h1, None, 513), ARG, "null argument"),
+        (L.rd_copy_filtered, (h1, p, 512), ARG, "filtered has 513 elements"),
+        (L.rd_copy_filtered, (h3, p, 1026), ARG, "filtered has 513 elements"),
+        (L.rd_copy_quantized, (None, p, 2048), ARG, "null argument"),
+        (L.rd_copy_quantized, (h1, None, 2048), ARG, "null argument"),
+        (L.rd_copy_quantized, (h1, p, 1024), ARG, "quantized has 2048 elements"),
+        (L.rd_copy_quantized, (h3, p, 2049), ARG, "quantized has 2048 elements"),
+    ]
+    for fn, args, code, text in rows:
+        rc = fn(*args)
+        assert (rc, L.rd_last_error().decode()) == (code, text), (fn.__name__, args[1:])
+    assert n.value == -7                                   # no refusal wrote a count
+    # what a fresh handle answers without a device: no packets, all-zero state (dsp.py:134-135)
+    for h in (h1, h3):
+        assert L.rd_demod_inflight(h) == 0
+        assert L.rd_demod_refetch(h, None, 0, pn) == OK and n.value == 0
+        n.value = -7
+        for enabled in (1, 0):                             # parse may be switched on a quiet handle; still nothing fetched
+            assert L.rd_demod_set_parse(h, enabled) == OK
+            assert (L.rd_demod_parsed(h, None, 0, pn), L.rd_last_error().decode()) == (STATE, "no block fetched since create / reset")
+        d = np.ones(1024)
+        assert L.rd_copy_discriminated_stream(h, 0, d.ctypes.data_as(C.c_void_p), 1024) == OK and not d.any()
+        f = np.ones(2 * 513)
+        assert L.rd_copy_filtered(h, f.ctypes.data_as(C.c_void_p), 513) == OK and not f.any()
+        q = np.ones(2048, np.uint8)
+        assert L.rd_copy_quantized(h, q.ctypes.data_as(C.c_void_p), 2048) == OK and not q.any()
+    d = np.ones(1024)
+    assert L.rd_copy_discriminated(h1, d.ctypes.data_as(C.c_void_p), 1024) == OK and not d.any()
+    d = np.ones(1024)
+    assert L.rd_copy_discriminated_stream(h3, 2, d.ctypes.data_as(C.c_void_p), 1024) == OK and not d.any()
+    for h in (h1, h3):
+        L.rd_destroy(h)
+
+
+def test_stage_function_refusals_decided_before_any_device_call():
+    """The stage functions' argument refusals (and the empty calls that succeed without a device): code and whole text,
+    and the size rule before the null check where both apply."""
+    C, _lib, L, cfg, hs = _refusal_env()
+    for h in hs.values():
+        L.rd_destroy(h)
+    ARG, OK = _lib.RD_ERR_ARG, _lib.RD_OK
+    buf = np.ones(4096)
+    p = buf.ctypes.data_as(C.c_void_p)
+    cnt = C.c_int(-7)
+    pc = C.byref(cnt)
+    bad = type(cfg)()
+    C.memmove(C.byref(bad), C.byref(cfg), C.sizeof(cfg))
+    bad.symbol_length = 0
+    rows = [
+        (L.rd_lut_execute, (p, 10, p, 4), ARG, "Incompatible array sizes: in_bytes.size=10, out_cplx.size=4"),
+        (L.rd_lut_execute, (None, 10, None, 4), ARG, "Incompatible array sizes: in_bytes.size=10, out_cplx.size=4"),
+        (L.rd_lut_execute, (p, 0, p, 0), OK, None),
+        (L.rd_lut_execute, (None, 8, p, 4), ARG, "null argument"),
+        (L.rd_lut_execute, (p, 8, None, 4), ARG, "null argument"),
+        (L.rd_rotate_fs4, (None, None, 0), OK, None),
+        (L.rd_rotate_fs4, (None, p, 4), ARG, "null argument"),
+        (L.rd_rotate_fs4, (p, None, 4), ARG, "null argument"),
+        (L.rd_fir9, (p, 8, p, 0), ARG, "fir9: n_out must be <= n_in - 8"),
+        (L.rd_fir9, (p, 10, p, 3), ARG, "fir9: n_out must be <= n_in - 8"),
+        (L.rd_fir9, (None, 10, None, 3), ARG, "fir9: n_out must be <= n_in - 8"),
+        (L.rd_fir9, (None, 9, None, 0), OK, None),
+        (L.rd_fir9, (None, 10, p, 2), ARG, "null argument"),
+        (L.rd_fir9, (p, 10, None, 2), ARG, "null argument"),
+        (L.rd_discriminate, (p, 0, p, 0), ARG, "discriminate: n_out must be n_in - 1"),
+        (L.rd_discriminate, (p, 5, p, 3), ARG, "discriminate: n_out must be n_in - 1"),
+        (L.rd_discriminate, (None, 5, None, 5), ARG, "discriminate: n_out must be n_in - 1"),
+        (L.rd_discriminate, (None, 1, None, 0), OK, None),
+        (L.rd_discriminate, (None, 5, p, 4), ARG, "null argument"),
+        (L.rd_discriminate, (p, 5, None, 4), ARG, "null argument"),
+        (L.rd_quantize, (None, None, 0), OK, None),
+        (L.rd_quantize, (None, p, 4), ARG, "null argument"),
+        (L.rd_quantize, (p, None, 4), ARG, "null argument"),
+        # rd_search(cfg, quantized, n, indices, cap, count); a preamble spans (16 - 1) * 14 = 210 samples
+        (L.rd_search, (C.byref(cfg), p, 4096, p, 0, None), ARG, "null count"),
+        (L.rd_search, (None, p, 4096, p, 0, pc), ARG, "null config"),
+        (L.rd_search, (None, p, 4096, p, 0, None), ARG, "null count"),
+        (L.rd_search, (C.byref(bad), p, 4096, p, 0, pc), ARG, "unsupported packet configuration"),
+        (L.rd_search, (C.byref(cfg), None, 211, p, 0, pc), ARG, "null argument"),
+    ]
+    for fn, args, code, text in rows:
+        rc = fn(*args)
+        assert rc == code, (fn.__name__, args, rc, L.rd_last_error())
+        if text is not None:
+            assert L.rd_last_error().decode() == text, (fn.__name__, args)
+    cnt.value = -7
+    assert L.rd_search(C.byref(cfg), None, 210, None, 0, pc) == OK and cnt.value == 0   # too short to hold a preamble
