@@ -2,7 +2,7 @@
 // the error slot, the device context, the host waits and the host-push probe.  The handles themselves: rd_batch.hip
 // (batch demodulator), rd_stream.hip (streaming demodulator), rd_stages.hip (stage functions on host arrays).
 //
-// Host-side orchestration only.  All arithmetic of the path runs in the kernels of rd_kernels.hip; there is no CPU
+// Host-side orchestration only.  All arithmetic of the path runs in the kernel files (rd_device.h names them); there is no CPU
 // fallback - without a usable HIP device every compute entry point returns RD_ERR_DEVICE.
 #include <unistd.h>
 #include <hsa/hsa.h>

@@ -2,7 +2,7 @@
 //
 // Host-side orchestration only: buffer management, kernel sequencing, and the per-call ordering/dedupe of
 // Demodulator._slice (py:190-205) where the device has not done it.  All arithmetic of the path runs in the kernels of
-// rd_kernels.hip and rd_demod_mfma.hip.  py = /root/reference/src/rtldavis/dsp.py
+// rd_tail.hip, rd_tail_kernels.hip, rd_parse_kernels.hip and rd_demod_mfma.hip.  py = /root/reference/src/rtldavis/dsp.py
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -186,7 +186,7 @@ static int batch_alloc(rd_batch *b) {
         // the per-stream match lists short so that the fallback runs on ordinary inputs (test hook)
         const char *ti = getenv("RD_TAIL_IMPL");
         const bool legacy = ti && ti[0] == 'l';
-        b->ft_ok = !legacy && b->fast_ok && b->dc.S == 14 && b->dc.P == 16 && b->dc.K == 80 && b->dc.pre_mask == 0x91D3ull &&
+        b->ft_ok = !legacy && b->fast_ok && rd_davis_shape(b->dc) &&
                    b->n_samples < (1l << 30) && b->dc.B < (1 << 24) && b->bits_stride % 4 == 0 && b->dc.L >= b->dc.B &&
                    (long)(b->n_blocks + 1) * b->dc.B - b->dc.L >= 0 &&   // (a batch shorter than a packet has no position to report)
                    ((long)(b->n_blocks + 1) * b->dc.B - b->dc.L) / 32 + 16 <= (long)b->bits_stride;

@@ -1,7 +1,7 @@
 // rd_demod_mfma.hip - k_demod_mfma: the fused IQ -> sign-bit kernel with the FIR on the matrix pipe.
 //
 // Reads lay.iq once, writes the packed sign bits and lists the 8-sample groups whose sign is not certain (the tail
-// re-evaluates those exactly: k_tail / k_fixup in rd_kernels.hip).  Reference stages: LUT py:38-39 + rotate_fs4
+// re-evaluates those exactly: k_tail in rd_tail.hip / k_fixup in rd_tail_kernels.hip).  Reference stages: LUT py:38-39 + rotate_fs4
 // py:46-49 + fir9 py:71-73 + discriminate numerator py:89 + quantize py:98 (py = /root/reference/src/rtldavis/dsp.py).
 // Arithmetic and its error bound: rd_mfma.h.
 //
@@ -58,7 +58,7 @@ typedef uint32_t rd_u4v __attribute__((ext_vector_type(4)));
 typedef float rd_f4v __attribute__((ext_vector_type(4)));
 typedef uint32_t rd_u2v __attribute__((ext_vector_type(2)));
 
-static const rd_mf_taps h_mf_taps = rd_mf_make_taps();   // (the 16-output tap matrix: the RSSI windows of rd_kernels.hip use it)
+static const rd_mf_taps h_mf_taps = rd_mf_make_taps();   // (the 16-output tap matrix: the RSSI windows of rd_device.h use it)
 __device__ const rd_mf_taps8 g_mf_taps8 = rd_mf_make_taps8();
 static const rd_mf_taps8 h_mf_taps8 = rd_mf_make_taps8();
 extern "C" void rd_debug_mfma_taps8(uint16_t *out) { memcpy(out, &h_mf_taps8, sizeof h_mf_taps8); }

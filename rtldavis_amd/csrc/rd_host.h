@@ -30,6 +30,13 @@ struct rd_devcfg {
     double fs;                          // sample rate = bit_rate * symbol_length (protocol.py:309)
 };
 
+// The Davis shape (protocol.py:68-76), the one the compile-time kernels are built for: 14 samples per symbol, the preamble
+// 1100101110001001 (bit m of the mask = symbol m -> 0x91D3), 80 packet symbols.  The search has no use for the packet's
+// length, the slice none for the preamble.
+static inline bool rd_davis_search(const rd_devcfg &c) { return c.S == 14 && c.P == 16 && c.pre_mask == 0x91D3ull; }
+static inline bool rd_davis_slice(const rd_devcfg &c) { return c.S == 14 && c.K == 80; }
+static inline bool rd_davis_shape(const rd_devcfg &c) { return rd_davis_search(c) && c.K == 80; }
+
 // RD_OK or RD_ERR_ARG; *why (never null on failure) names the offending field
 int rd_make_devcfg(const rd_config *c, rd_devcfg *d, const char **why);
 

@@ -19,7 +19,7 @@ enum { RD_CNT_FIX = 0, RD_CNT_MATCH = 1, RD_CNT_REC = 2, RD_CNT_TASKS = 3, RD_CN
 // rd_launch_demod flags
 #define RD_DEMOD_FIX_BUCKETS 4u    /* the fix-up entries go to per-group buckets (the one-launch tail, k_tail): fix_list =
                                       [groups][fix_cap] entries, bucket_cnt = [groups] counters, group = stream >> RD_FT_GSH */
-// The one-launch tail (rd_kernels.hip: k_tail): a workgroup owns RD_FT_STREAMS consecutive streams
+// The one-launch tail (rd_tail.hip: k_tail): a workgroup owns RD_FT_STREAMS consecutive streams
 #define RD_FT_GSH 2
 #define RD_FT_STREAMS (1 << RD_FT_GSH)
 struct rd_ft_bufs {
@@ -143,7 +143,7 @@ void rd_launch_window_update(uint32_t *win_out, const uint32_t *win_in, long n_w
                              long n_block_bits, int n_streams, size_t win_stride, size_t block_stride,
                              hipStream_t st);
 
-// The streaming handle's one-launch block (k_stream_block, rd_kernels.hip): everything of one demodulate() call - ring
+// The streaming handle's one-launch block (k_stream_block, rd_tail_kernels.hip): everything of one demodulate() call - ring
 // roll, exact bits, window, search, slice + RSSI, results into mapped host memory - for NS streams in lock step.
 #define RD_SB_THREADS 1024
 #ifndef RD_SBC_THREADS
@@ -162,7 +162,7 @@ struct rd_sb_args {
     uint32_t seq;
     long seen_before;         // blocks since reset
     uint64_t *stamps;         // diagnostic library: phase stamps (else null)
-    int parse;                // also run Parser.parse's front half for every record (rd_kernels.hip: rd_wave_parse) ...
+    int parse;                // also run Parser.parse's front half for every record (rd_device.h: rd_wave_parse) ...
     int32_t *fe_host;         // ... into mapped host memory laid out like recs_host: RD_FE_NONE or the frequency error
 };
 // 1 when the kernel was launched, 0 when the configuration is not one it is built for

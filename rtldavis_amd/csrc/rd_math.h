@@ -44,6 +44,7 @@
 #define RD_C2 0.122424706672
 #define RD_C3 0.197408519126
 #define RD_C4 0.228626345955
+#define RD_TAPS9 {RD_C0, RD_C1, RD_C2, RD_C3, RD_C4, RD_C3, RD_C2, RD_C1, RD_C0}   /* c[0 .. 8], double or float */
 // sum_m c_m j^m = 2c0 - 2c2 + c4 (real): response of the filter to the rotated DC term.
 #define RD_CDC (2.0 * RD_C0 - 2.0 * RD_C2 + RD_C4)
 #define RD_DC ((float)(127.4 * RD_CDC))
@@ -470,7 +471,7 @@ RD_HD rd_d2 rd_sample_f64(const rd_cplx_view &v, long n) {
 // readable sample is the zero state of py:133.
 template <class View>
 RD_HD rd_d2 rd_f_f64(const View &v, long t) {
-    const double c[9] = {RD_C0, RD_C1, RD_C2, RD_C3, RD_C4, RD_C3, RD_C2, RD_C1, RD_C0};
+    const double c[9] = RD_TAPS9;
     rd_d2 f = {0.0, 0.0};
     if (t < v.valid_from) return f;
 #pragma unroll

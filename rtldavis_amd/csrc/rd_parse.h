@@ -1,5 +1,5 @@
 // rd_parse.h - arithmetic of protocol.Parser.parse's front half (protocol.py:282-318), shared by the host (rd_host.cpp:
-// rd_parse_packet; rd_collect_block: the streaming handles' rd_parsed records) and the kernels (rd_kernels.hip: k_parse_select
+// rd_parse_packet; rd_collect_block: the streaming handles' rd_parsed records) and the kernels (rd_parse_kernels.hip: k_parse_select
 // and k_freq_err of the batch path, rd_wave_parse of the streaming blocks).  Plain host + device functions, no HIP
 // runtime needed: rd_host.cpp is pure host code whichever compiler builds it.
 //   bit swap        every byte bit-reversed (protocol.py:79-83, :290)

@@ -1,6 +1,6 @@
 // rd_stages.hip - the stage functions of the C ABI on host arrays (include/rtldavis_hip.h: rd_lut_execute .. rd_search):
 // one stage of the path at a time, for tests and for callers that want a single step.  Each uploads its input, launches
-// the stage's float64 kernel (rd_kernels.hip) on the null stream and downloads the result.
+// the stage's float64 kernel (rd_stage_kernels.hip) on the null stream and downloads the result.
 #include <algorithm>
 #include <vector>
 

@@ -2,7 +2,7 @@
 // py:128-253) and the entry points the wideband receiver reaches it through (rd_internal.h: rd_demod_prepare ..).
 //
 // Host-side orchestration only: the slots of the two blocks in flight, which launch form a block takes, the waits.  The
-// arithmetic runs in the kernels of rd_kernels.hip, the fetch from a slot's device-written counts to host copies in
+// arithmetic runs in the kernels of rd_stream_kernels.hip and rd_tail_kernels.hip, the fetch from a slot's device-written counts to host copies in
 // rd_host.cpp (rd_collect_block).  py = /root/reference/src/rtldavis/dsp.py
 #include <immintrin.h>
 
@@ -189,7 +189,7 @@ static int demod_alloc(rd_demod *h) {
     // one launch per block where the kernel exists for the configuration; RD_STREAM_IMPL=legacy: the multi-launch form (A/B)
     const char *e = getenv("RD_STREAM_IMPL");
     const rd_devcfg &c = h->dc;
-    h->one_ok = !(e && e[0] == 'l') && h->fast_ok && c.S == 14 && c.P == 16 && c.K == 80 && c.pre_mask == 0x91D3ull &&
+    h->one_ok = !(e && e[0] == 'l') && h->fast_ok && rd_davis_shape(c) &&
                 c.L == 2 * c.B && c.B % 32 == 0 && c.B >= 2048 && c.B <= 16384;
     h->dev_ready = true;
     return RD_OK;

@@ -7,6 +7,7 @@
 //   host_asan file <in> <out> <S>      rd_packet records from <in>, kept indices (uint32) to <out>
 //   host_asan config <rounds> <seed>   rd_make_devcfg / rd_check_block_count / rd_ord_bucket_cap on random and extreme input
 //   host_asan waiter                   rd_waiter: deadline 0, a short deadline, the override hook
+//   host_asan shape                    rd_davis_shape / _search / _slice: the condition of each of their seven sites
 //   host_asan repeats <msgs> <delivered> <out> <SL>   rd_burst_msg records through rd_bd_repeats, kept indices (uint32) to <out>
 //   host_asan block <n_lists> <per> <S> <counts> <recs> <fe|-> <last> <parsed>   one streaming slot through rd_collect_block
 //   host_asan parsed <in> <out> <S>    rd_parsed records from <in> through rd_order_parsed, the kept ones to <out>
@@ -140,6 +141,35 @@ static int config(int rounds, unsigned seed) {
         rd_check_block_count(1, 16384, 8192, 1, &want) != RD_ERR_ARG || want != 8192 || rd_check_block_count(0, 3 * 16384, 8192, 3, nullptr) != RD_OK)
         return fail("block count");
     printf("config ok: %d of %d random configurations accepted\n", ok, rounds);
+    return 0;
+}
+
+// The Davis-shape predicates against the conditions their seven sites spelled out before they shared them: the one-launch
+// tail (rd_launch_tail_fused, the batch handle's ft_ok), the one-launch streaming blocks (both launches, the streaming
+// handle's one_ok) test S, P, K and the preamble; rd_launch_search does not test K; rd_launch_slice tests S and K only.
+static int shape() {
+    const rd_config prod = {19200, 14, 16, 80, 8192, {1, 1, 0, 0, 1, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0, 1}};
+    int n = 0, davis = 0;
+    for (int sl : {14, 8, 1, 15})
+        for (int ps : {16, 8, 15})
+            for (int pk : {80, 64, 88})
+                for (int flip : {-1, 0, 7, 15}) {
+                    rd_config c = prod;
+                    c.symbol_length = sl; c.preamble_symbols = ps; c.packet_symbols = pk;
+                    if (flip >= 0) c.preamble[flip] ^= 1;
+                    rd_devcfg d;
+                    const char *why;
+                    if (rd_make_devcfg(&c, &d, &why) != RD_OK) return fail("a shape the library takes was refused");
+                    const bool whole = d.S == 14 && d.P == 16 && d.K == 80 && d.pre_mask == 0x91D3ull;
+                    const bool search = d.S == 14 && d.P == 16 && d.pre_mask == 0x91D3ull;
+                    const bool slice = d.S == 14 && d.K == 80;
+                    if (rd_davis_shape(d) != whole || rd_davis_search(d) != search || rd_davis_slice(d) != slice)
+                        return fail("a Davis-shape predicate differs from its site's condition");
+                    n++;
+                    davis += whole;
+                }
+    if (davis != 1) return fail("exactly one of the shapes is the Davis one");
+    printf("shape ok: %d shapes\n", n);
     return 0;
 }
 
@@ -301,5 +331,6 @@ int main(int argc, char **argv) {
     if (argc >= 5 && !strcmp(argv[1], "file")) return file_mode(argv[2], argv[3], atoi(argv[4]));
     if (argc >= 4 && !strcmp(argv[1], "config")) return config(atoi(argv[2]), (unsigned)atoi(argv[3]));
     if (argc >= 2 && !strcmp(argv[1], "waiter")) return waiter();
-    return fail("usage: soak <rounds> <seed> | file <in> <out> <S> | config <rounds> <seed> | waiter | repeats .. | block .. | parsed .. | parsed-soak ..");
+    if (argc >= 2 && !strcmp(argv[1], "shape")) return shape();
+    return fail("usage: soak <rounds> <seed> | file <in> <out> <S> | config <rounds> <seed> | waiter | shape | repeats .. | block .. | parsed .. | parsed-soak ..");
 }

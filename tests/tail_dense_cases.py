@@ -1,7 +1,7 @@
 """Inputs and expected values for the batch tail on dense match lists (no tests in here; tests/test_tail_dense_cpu.py
 checks every condition named below on the CPU, tests/test_tail_dense.py runs the batches on the device).
 
-k_tail (rd_kernels.hip) searches, slices, dedupes, ranks and writes the records of four streams per workgroup, with a
+k_tail (rd_tail.hip) searches, slices, dedupes, ranks and writes the records of four streams per workgroup, with a
 match list per stream in LDS: 32 entries for these short streams, doubled by the host after every upload that
 overflowed it, up to 512.  The other tail tests give a stream at most 16 raw preamble matches, or about a hundred spread
 over hundreds of blocks; here a stream of four blocks of 8192 holds up to 530.

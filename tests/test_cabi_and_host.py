@@ -189,6 +189,36 @@ def test_traffic_stamp_of_the_built_demod_kernel():
     assert len(tj["kernel_isa_sha256"]) == 64 and tj["traffic_bytes"] > tj["algorithmic_bytes"]
 
 
+def test_isa_kernels_lines_follow_the_code_not_its_place():
+    """tools/profile_collect.py::isa_kernels, the per-kernel comparison of two builds: a kernel's line (symbol, sha256 of
+    its instructions, their count, the figures of its .amdhsa_ block) does not depend on the file's order, its label
+    numbers or its comments, and one changed operand changes exactly that kernel's hash."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("profile_collect", os.path.join(ROOT, "tools", "profile_collect.py"))
+    pc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pc)
+
+    def kernel(name, n, offset, note, vgpr):
+        return ["\t.type\t%s,@function" % name, "%s: ; @%s" % (name, name), "; %bb.0:", "\ts_load_dword s0, s[4:5], %s ; %s" % (offset, note),
+                ".LBB%d_2: ; %s" % (n, note), "\tv_add_u32_e32 v0, s0, v0", "\ts_cbranch_scc1 .LBB%d_2" % n, "\ts_endpgm", ".Lfunc_end%d:" % n,
+                "\t.section\t.rodata", "\t.amdhsa_kernel %s" % name, "\t\t.amdhsa_group_segment_fixed_size 48",
+                "\t\t.amdhsa_private_segment_fixed_size 0", "\t\t.amdhsa_next_free_vgpr %d" % vgpr, "\t\t.amdhsa_next_free_sgpr 20",
+                "\t\t.amdhsa_accum_offset 8", "\t.end_amdhsa_kernel", "\t.text"]
+
+    def text(order, offset_a="0x0", note="c"):
+        parts = {"a": kernel("_Z3k_av", 3 if order == "ab" else 9, offset_a, note, 6),
+                 "b": kernel("_Z3k_bv", 4 if order == "ab" else 1, "0x8", note, 7)}
+        return "\n".join(["\t.text"] + parts[order[0]] + parts[order[1]] + ["_Z6helperv:", "\ts_setpc_b64 s[30:31]"])
+
+    one, two = pc.isa_kernels(text("ab")), pc.isa_kernels(text("ba", note="another comment"))
+    assert one == two and [ln.split()[0] for ln in one] == ["_Z3k_av", "_Z3k_bv"]
+    name, sha, count, *figures = one[0].split()
+    assert len(sha) == 64 and count == "4" and figures == ["vgpr=6", "sgpr=20", "private=0", "lds=48", "accum=8"]
+    assert one[1].split()[2:] == ["4", "vgpr=7", "sgpr=20", "private=0", "lds=48", "accum=8"] and one[1].split()[1] != sha
+    changed = pc.isa_kernels(text("ab", offset_a="0x4"))
+    assert changed[0].split()[1] != sha and changed[0].split()[2:] == one[0].split()[2:] and changed[1] == one[1]
+
+
 def _refusal_env():
     import ctypes as C
     from rtldavis_amd import _lib, dsp

@@ -256,7 +256,7 @@ def test_twins():
 
 
 def fp32_rssi(call, q):
-    """Whether k_tail evaluates this record's RSSI window on its fp32 route: rd_rssi_prepare's `ok` (rd_kernels.hip,
+    """Whether k_tail evaluates this record's RSSI window on its fp32 route: rd_rssi_prepare's `ok` (rd_device.h,
     the line `j.ok = t_lo >= 1 && ...`) is false when the 32 columns of the matrix form would reach outside the stream."""
     pl = TD.REP
     ns, pe = max(q - pl, 0), min(q + pl, B + 1)

@@ -5,6 +5,7 @@ import glob
 import hashlib
 import json
 import os
+import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +15,15 @@ DEMOD_KERNEL_SYMBOL = "_Z12k_demod_mfmaILi0ELb0EE"   # k_demod_mfma<0, false>: t
 STAMP_FILE = os.path.join(ROOT, "rtldavis_amd", "librtldavis_hip.stamp")
 
 
+def _isa_instruction(line: str):
+    """An assembly line as the hashes see it: None for comments, directives and local labels, else the instruction with its
+    comment dropped and basic-block label numbers normalised (they count the functions in front of the kernel)."""
+    t = line.split(";")[0].strip()
+    if not t or t.startswith("."):
+        return None
+    return re.sub(r"LBB\d+_", "LBB_", t)
+
+
 def isa_sha256(asm_text: str, symbol_prefix: str = DEMOD_KERNEL_SYMBOL) -> str:
     """sha256 over the INSTRUCTIONS of the dominant kernel, from the device assembly hipcc writes for
     rd_demod_mfma.hip (-S --cuda-device-only, the product's flags): the kernel's body from its label to s_endpgm,
@@ -21,20 +31,55 @@ def isa_sha256(asm_text: str, symbol_prefix: str = DEMOD_KERNEL_SYMBOL) -> str:
     kernel).  Any change to the kernel's code changes it; other kernels, host code, diagnostic variants and comments
     do not.  (The bytes inside the .so are no use for this: their pc-relative literals move with every function added
     to the file.)  '' when the kernel is not in the text."""
-    import re
     body, inside = [], False
     for line in asm_text.splitlines():
         if not inside:
             if line.startswith(symbol_prefix) and line.rstrip().split(";")[0].rstrip().endswith(":"):
                 inside = True
             continue
-        t = line.split(";")[0].strip()
-        if not t or t.startswith(".L") or t.startswith("."):
+        t = _isa_instruction(line)
+        if t is None:
             continue
-        body.append(re.sub(r"LBB\d+_", "LBB_", t))
+        body.append(t)
         if t == "s_endpgm":
             return hashlib.sha256("\n".join(body).encode()).hexdigest()
     return ""
+
+
+AMDHSA_FIGURES = (("vgpr", "next_free_vgpr"), ("sgpr", "next_free_sgpr"), ("private", "private_segment_fixed_size"),
+                  ("lds", "group_segment_fixed_size"), ("accum", "accum_offset"))
+
+
+def isa_kernels(asm_text: str) -> list:
+    """One line per kernel of a device assembly text, sorted by mangled name: the symbol, the sha256 over its
+    instructions (label to the end of the function, normalised as isa_sha256 does), their count and the figures of its
+    .amdhsa_ block.  Two builds of a kernel give equal lines exactly when the compiler produced the same code for it,
+    whichever file it was compiled from and whatever stands around it."""
+    figures, cur = {}, None
+    for line in asm_text.splitlines():
+        t = line.strip()
+        if t.startswith(".amdhsa_kernel "):
+            cur = figures.setdefault(t.split()[1], {})
+        elif t == ".end_amdhsa_kernel":
+            cur = None
+        elif cur is not None and t.startswith(".amdhsa_"):
+            key, _, value = t[len(".amdhsa_"):].partition(" ")
+            cur[key] = value.strip()
+    bodies, body = {}, None
+    for line in asm_text.splitlines():
+        if line.startswith(".Lfunc_end"):
+            body = None
+        elif body is None:
+            name = line.split(";")[0].rstrip()
+            if name.endswith(":") and name[:-1] in figures:
+                body = bodies.setdefault(name[:-1], [])
+        else:
+            t = _isa_instruction(line)
+            if t is not None:
+                body.append(t)
+    return ["%s %s %d %s" % (name, hashlib.sha256("\n".join(bodies.get(name, [])).encode()).hexdigest(), len(bodies.get(name, [])),
+                             " ".join("%s=%s" % (short_key, figures[name].get(key, "-")) for short_key, key in AMDHSA_FIGURES))
+            for name in sorted(figures)]
 
 
 def kernel_isa_stamp() -> str:
@@ -149,5 +194,11 @@ if __name__ == "__main__":
         if not st:
             sys.exit("k_demod_mfma not found in " + sys.argv[2])
         print(st)
+    elif cmd == "isa-kernels":   # isa-kernels <device assembly> [...]: one line per kernel, for comparing two builds
+        lines = []
+        for path in sys.argv[2:]:
+            with open(path) as fh:
+                lines += isa_kernels(fh.read())
+        print("\n".join(sorted(lines)))
     elif cmd == "stamp":
         print(kernel_isa_stamp())
