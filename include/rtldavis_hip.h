@@ -427,7 +427,7 @@ int rd_wb_tuning(rd_wideband *w, int64_t *shift_hz, int64_t *phase, int n);
  * rd_wideband_reset drops a pending change and returns to cfg.gain. */
 int rd_wb_set_gain(rd_wideband *w, const double *gain, int n);
 int rd_wb_gains(rd_wideband *w, double *gain, int n);
-/* Level metering (k_chan_levels, rd_channelizer.hip): with levels on, every chunk carries one more launch behind its
+/* Level metering (k_chan_levels, rd_chan_levels.hip): with levels on, every chunk carries one more launch behind its
  * channelizer.  All quantities are exact integers.
  *   per channel, over the 2 * block_size bytes b of its channelized chunk, a = 2 b - 255:
  *     peak = max |a|, clipped = bytes equal to 0 or 255, power = sum a^2, gain = the float32 gain in force for the chunk

@@ -92,7 +92,7 @@
 // staged sample is the four 16-bit lanes Ilo Ihi Qlo Qhi in int16's fragment order - one aligned ds_read_b128 per B
 // fragment, no VALU work in the loop; both digits meet the SAME tap (no 2^-8), the epilogue's scale is gains[ch].
 // Products stay exact: 11 x 11 bits, the smallest non-zero one 2^-24 2^-24 = 2^-48.  Bound: tests/chan_bound_cf32.py.
-// Levels: k = clip(rint(2^15 adm(v)), -32768, 32767) per component, i.e. int16 units (k_chan_levels).
+// Levels: k = clip(rint(2^15 adm(v)), -32768, 32767) per component, i.e. int16 units (rd_chan_levels.hip: k_chan_levels).
 //
 // RETUNE (streaming form only; rd_wideband.hip: rd_wb_retune).  With a phase accumulator P_c, an integer in [0, Fo) that is
 // 0 after create and reset, and t the absolute output time,
@@ -108,8 +108,6 @@
 // lane and channel beside shifts[ch] and phase[ch]; the bound of a channel is error_bound at that channel's gain.
 // rd_chan_set_gain rewrites the table for the one-shot form; the streaming form's updates are rd_chan_stream_gains
 // (rd_wideband.hip: rd_wb_set_gain), a copy queued between two chunks' k_channelize as the retune kernel is.
-// LEVELS (k_chan_levels, streaming form): what the gains leave of the byte range, per channel and chunk, and how hard the
-// capture drives the ADC - exact integers for a gain control on the host (rtldavis_amd/agc.py).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -121,58 +119,26 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/rtldavis_hip.h"
+#include "rd_chan_tables.h"
 #include "rd_internal.h"
 
-#define RD_CHAN_TB 4                        // 32-time blocks per wave
-#define RD_CHAN_TT (32 * RD_CHAN_TB)        // output times per workgroup
-#define RD_CHAN_RBG 4                       // row blocks (32 rows = 16 channels) per workgroup: one per wave
-#define RD_CHAN_KC 8                        // window samples per K step of the 8-bit formats (taps are padded to a multiple)
-#define RD_CHAN_TERMS 2                     // f16 digits per tap
-#define RD_CHAN_Q_BYTES (RD_CHAN_TERMS * RD_CHAN_RBG * 64 * 16)  // A bytes per K step: terms x 4 row blocks x 64 lanes x 16 B
 #ifndef RD_CHAN_NPF
 #define RD_CHAN_NPF 2                       // A chunks in flight in registers
 #endif
 #ifndef RD_CHAN_MINWAVES
 #define RD_CHAN_MINWAVES 4                  // waves per SIMD the register allocation aims at (26 KiB of LDS admit 6)
 #endif
-#define RD_CHAN_EARLY 64                    // outputs per channel with a partial-history DC term kept in a table
-#define RD_CHAN_DCN (RD_CHAN_EARLY + 2)     // table entries per channel: the early DC terms, the steady one, and the
-                                            // phasor of 32 output times e^{-j 2 pi frac(32 shift / Fo)} (cos, sin)
-
-// per sample format (rtldavis_hip.h: RD_IQ_*): bytes of an IQ pair in memory and staged in LDS, window samples per K step
-__host__ __device__ constexpr int rd_fmt_in_bps(int f) { return f == RD_IQ_CF32 ? 8 : f == RD_IQ_S16 ? 4 : 2; }
-__host__ __device__ constexpr int rd_fmt_lds_bps(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32 ? 8 : 2; }
-__host__ __device__ constexpr int rd_fmt_kc(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32 ? RD_CHAN_KC / 2 : RD_CHAN_KC; }
-// two 16-bit digits per component (four lanes per staged sample): the formats whose B fragment is one ds_read_b128
-__host__ __device__ constexpr bool rd_fmt_digits(int f) { return f == RD_IQ_S16 || f == RD_IQ_CF32; }
-// RD_CF32_CLAMP (adm: |v| <= 8) and rd_chan_adm: rd_internal.h (k_chan_spectrum admits float32 components the same way)
-#define RD_CF32_PRESCALE_LOG2 12            // staged s = 2^12 adm(v), |s| <= 2^15 < 65504
 
 typedef float rd_f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 rd_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 rd_f16x2 __attribute__((ext_vector_type(2)));
 
-struct rd_chan {
-    rd_chan_config cfg;
-    int fmt = RD_IQ_U8;            // sample format of the capture
-    int n_groups = 0;              // groups of 64 channels
-    int t_pad = 0;                 // taps rounded up to RD_CHAN_KC (zero taps appended)
-    int n_early = 0;               // outputs whose window reaches before the capture: ceil((t_pad - 1) / D)
-    float tap_unscale = 1.0f;      // 2^-s: the taps in h_amat are scaled by 2^s
-    std::vector<uint16_t> h_amat;  // f16 A operand in fragment order [group][K step][term][row block][lane][8]
-    std::vector<float> h_dc;       // [channel][RD_CHAN_DCN][2]: -127.4 (1+j) sum of the taps a given output sees; the 32-step phasor
-    std::vector<int64_t> shifts;   // Hz, reduced mod out_rate
-    // the tuning the tables hold (rd_chan_retune): the shifts as given, and the phase accumulators P_c in [0, out_rate)
-    std::vector<int64_t> shift_hz, phase;
-    std::vector<double> taps;      // the float64 prototype (a retune rebuilds a channel's tables from it)
-    double tap_scale = 1.0;        // 2^s
+// The handle: the host's state (rd_chan_tables.h) and what lives on the device
+struct rd_chan : rd_chan_tables {
     uint16_t *d_amat = nullptr;
     float *d_dc = nullptr;
     int64_t *d_shifts = nullptr;
     int64_t *d_phase = nullptr;
-    // GAIN: the per-channel gains the table holds (float32, (float)cfg.gain each at create), the device table, and two
-    // pinned slots of [n_channels] for the streaming form's updates (rd_chan_stream_gains)
-    std::vector<float> gains;
+    // GAIN: the device table, and two pinned slots of [n_channels] for the streaming form's updates (rd_chan_stream_gains)
     float *d_gains = nullptr;
     float *h_gains = nullptr;
     double *d_taps = nullptr;      // streaming form only: k_chan_retune's input, uploaded once
@@ -184,14 +150,6 @@ struct rd_chan {
     bool dev_ready = false;
     int device = -1;               // the device the buffers live on
 };
-
-// x mod m for integer-valued 0 <= x < 2^53, 1 <= m < 2^26 (exact: one fma, one correction step)
-__device__ __forceinline__ double rd_chan_mod(double x, double m) {
-    double r = fma(-floor(x / m), m, x);
-    if (r < 0.0) r += m;
-    if (r >= m) r -= m;
-    return r;
-}
 
 // T is the padded tap count (multiple of RD_CHAN_KC, zero taps appended), D a multiple of 4.
 // Round 3: the window is staged as the RAW bytes - a byte in the low half of a 16-bit lane IS the f16 subnormal
@@ -421,9 +379,9 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
 
 // RETUNE (rd_chan_retune; rd_wideband.hip: rd_wb_retune): the tables of the channels whose tuning changes, rebuilt in
 // place between two chunks of a stream.  One workgroup per record (channel, shift, shift mod Fo, P); it writes what
-// chan_build_channel writes for that channel, by the same expressions - the fp32 taps g through the exact 64-bit
-// remainder (shift k) mod Fw and float64 sine / cosine, their two-term f16 split in the A operand's fragment order (every
-// K step, both lane halves, both terms, the zero taps included: one 16-byte store per fragment), the DC entries summed in
+// rd_chan_tables_build writes for that channel, through the same functions (rd_chan_tables.h) - the fp32 taps g through
+// the exact 64-bit remainder (shift k) mod Fw and float64 sine / cosine, their two-term f16 split in the A operand's fragment
+// order (every K step, both lane halves, both terms, the zero taps included: one 16-byte store per fragment), the DC entries summed in
 // float64 in the host's order (one lane: t_pad dependent additions while the rest of its wave idles, beside the other
 // waves' stores; not measured yet), the 32-output rotation, shift mod Fo and P.
 // Equal to the host's tables UP TO LIBM: the device's float64 sin / cos need not equal glibc's in the last bit.  Every
@@ -432,336 +390,39 @@ __global__ __launch_bounds__(256, RD_CHAN_MINWAVES) void k_channelize(const uint
 // reset after a retune with a fresh one byte for byte (tests/test_wideband_retune.py) rely on that, not on a guarantee.
 // Should one fail on a new ROCm with a single differing table entry: the definition holds either way (both are the
 // correctly-derived fp32 taps within half an ulp + libm's error, inside term 1 of tests/chan_bound.py) - change that test's
-// seed or compare it through the model's bound, do not loosen the kernel.  The f16 values: a 2^s is an fp32 number and so is what the first digit leaves of it,
-// so both digits are one rounding each, float -> half.  The stream orders it behind the previous chunk's k_channelize and
-// in front of the next one's: no second copy of the tables.
+// seed or compare it through the model's bound, do not loosen the kernel.  (The f16 values: rd_chan_tables.h.)  The stream
+// orders it behind the previous chunk's k_channelize and in front of the next one's: no second copy of the tables.
 __global__ __launch_bounds__(256) void k_chan_retune(const int64_t *__restrict__ rec, const double *__restrict__ taps,
                                                      int fmt, int T, int t_pad, int D, long out_rate, double tap_scale,
                                                      uint4 *amat, float2 *dc, int64_t *shifts, int64_t *phase) {
     extern __shared__ uint8_t lds[];
-    float2 *g = (float2 *)lds;                    // the channel's fp32 taps (g_r, g_i), k < t_pad
+    rd_chan_g *g = (rd_chan_g *)lds;              // the channel's fp32 taps (g_r, g_i), k < t_pad
     const int c = (int)rec[4 * blockIdx.x];
     const long shift = rec[4 * blockIdx.x + 1], smod = rec[4 * blockIdx.x + 2];
     const long fw = out_rate * D;
-    const double wide_rate = (double)out_rate * D;
-    for (int k = threadIdx.x; k < t_pad; k += blockDim.x) {
-        float2 v = float2{0.0f, 0.0f};
-        if (k < T) {
-            long r = (shift * k) % fw;            // |shift| <= Fw / 2 < 2^37, k < 2^13: exact in 64 bits
-            if (r < 0) r += fw;
-            const double ph = 2.0 * M_PI * ((double)r / wide_rate);
-            v = float2{(float)(taps[k] * cos(ph)), (float)(taps[k] * sin(ph))};
-        }
-        g[k] = v;
-    }
+    for (int k = threadIdx.x; k < t_pad; k += blockDim.x) g[k] = k < T ? rd_chan_tap(taps[k], shift, k, fw) : rd_chan_g{0.0f, 0.0f};
     __syncthreads();
+    float *dcc = (float *)(dc + (size_t)c * RD_CHAN_DCN);
     if (threadIdx.x == 0) {
         shifts[c] = smod;
         phase[c] = rec[4 * blockIdx.x + 3];
-        const long inc = (smod * 32) % out_rate;
-        const double ph = -2.0 * M_PI * ((double)inc / (double)out_rate);
-        dc[(size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1] = float2{(float)cos(ph), (float)sin(ph)};
+        rd_chan_rotation(smod, out_rate, dcc + 2 * (RD_CHAN_EARLY + 1));
     }
-    if (threadIdx.x == 64 && !rd_fmt_digits(fmt)) {   // (a lane of the second wave: the first one's has the rotation)
-        const double dc_level = fmt == RD_IQ_U8 ? 127.4 : 128.0;
-        double sr = 0.0, si = 0.0;
-        int kdone = 0;
-        for (int t = 0; t <= RD_CHAN_EARLY; t++) {
-            const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)D * t : (long)t_pad - 1;
-            for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += (double)g[kdone].x; si += (double)g[kdone].y; }
-            dc[(size_t)c * RD_CHAN_DCN + t] = float2{(float)(-dc_level * (sr - si)), (float)(-dc_level * (sr + si))};
-        }
-    }
-    const int kc = rd_fmt_kc(fmt), per_lane = kc / 2, n_q = t_pad / kc + 1;
-    const bool two = rd_fmt_digits(fmt);          // two digits per component; int16's low one meets taps scaled 2^-8, cf32's does not
-    const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
+    // (a lane of the second wave: the first one's has the rotation)
+    if (threadIdx.x == 64 && !rd_fmt_digits(fmt)) rd_chan_dc_entries(fmt, g, t_pad, D, dcc);
+    const int n_q = t_pad / rd_fmt_kc(fmt) + 1;
     // one fragment (8 f16 = 16 bytes) per item: K step q, term, lane half hh, part
     for (int it = threadIdx.x; it < 8 * n_q; it += blockDim.x) {
         const int part = it & 1, hh = (it >> 1) & 1, tm = (it >> 2) & 1, q = it >> 3;
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int el = 0; el < 8; el++) {
-            // the inverse of chan_build_channel's element position: (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi) x 2 (int16, cf32)
-            const int comp = (el >> 1) & 1;
-            const int sl = two ? el >> 2 : 2 * (el >> 2) + (el & 1), dig = two ? el & 1 : 1;
-            const int k = t_pad - (q * kc + hh * per_lane + sl);
-            if (k < 0 || k >= t_pad) continue;
-            const float2 gk = g[k];
-            const double a = part == 0 ? (comp == 0 ? (double)gk.x : -(double)gk.y) : (comp == 0 ? (double)gk.y : (double)gk.x);
-            const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
-            const _Float16 hi = (_Float16)(float)as;
-            const _Float16 lo = (_Float16)(float)(as - (double)hi);
-            const uint32_t bits = (uint32_t)__builtin_bit_cast(uint16_t, tm == 0 ? hi : lo);
-            w[el >> 1] |= bits << (16 * (el & 1));
-        }
-        const int lane = 32 * hh + r0 + part;
-        amat[((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane] = uint4{w[0], w[1], w[2], w[3]};
+        uint32_t w[4];
+        rd_chan_fragment(fmt, g, t_pad, tap_scale, q, tm, hh, part, w);
+        amat[rd_chan_amat_index(c, n_q, q, tm, hh, part)] = uint4{w[0], w[1], w[2], w[3]};
     }
-}
-
-// LEVELS (rd_wideband.hip: rd_wb_set_levels / rd_wb_levels): the level records of one streamed chunk, every one an exact
-// integer, so the order of summation does not matter.  One launch of n_channels + n_in workgroups behind the chunk's
-// k_channelize.
-//   workgroup c < n_channels: the 2 B bytes b of channel c's channelized chunk, a = 2 b - 255: peak = max |a|, clipped =
-//     bytes 0 or 255, power = sum a^2 = 4 sum b^2 - 1020 sum b + 65025 (2 B), and the float32 gain in force.
-//   the n_in workgroups behind them: the capture chunk's components in slices (a grid-stride loop over 16-byte vectors),
-//     combined by integer atomics on five device words (max, max, add, 64-bit adds); the workgroup that draws the last
-//     ticket takes the totals out (an exchange with 0, which leaves the words clear for the next launch) and writes the
-//     record.  uint8: a = 2 k - 255 as above.  int8: bit 7 flipped, u = k + 128, is the same byte arithmetic with
-//     a = u - 128, power = sum u^2 - 256 sum u + 16384 n, the ends -128 / 127 are u = 0 / 255.  int16: a = k per component.
-//     float32: a = k = clip(rint(2^15 adm(v)), -32768, 32767) per component - int16 units, full scale 32768 -, clipped =
-//     components with k at either end plus NaN components (a NaN is the value 0 for peak and power).
-// Sum b and sum b^2 of a dword are one packed-byte dot product each (v_dot4_u32_u8 against 0x01010101 and against
-// itself); the byte maxima are packed 16-bit maxima over the even and the odd bytes; a byte at an end of the range is a
-// zero byte of w or of ~w, counted by the carry-free zero-byte test and a population count.  A lane adds a vector's two
-// sums (<= 16 x 65025) to 64-bit totals; then a wave reduction by shuffles, LDS across the four waves, and lane 0 writes
-// the record with plain stores - straight into the mapped host slot of the chunk's parity, which the host reads after
-// the chunk's demodulator launch, later on the same stream, has reported.
-// Overflow: a chunk has at most 2^32 - 2 components (rd_chan_stream_launch: n_out decim <= 2^31 - 1 IQ pairs), a^2 <=
-// 65025 < 2^16 for the bytes and <= 2^30 for int16: power < 2^62, the 32-bit counts < 2^32 - no chunk
-// rd_wb_create_fmt admits can overflow a field.  The device-side totals of the int8 / uint8 forms (sum u^2 < 2^48) likewise.
-#define RD_LV_THREADS 256
-#define RD_LV_MAX_SLICES 256                // workgroups over the capture chunk (8 vectors per lane and pass below that)
-// RD_LV_ACC_WORDS (rd_internal.h) = 8: max b, max 255 - b (or max |k|), ends, ticket, sum u (64 bit), sum u^2 (64 bit)
-
-typedef unsigned short rd_u16x2 __attribute__((ext_vector_type(2)));
-
-struct rd_lv_sums {
-    uint32_t hi, lo;       // packed 16-bit lanes while a lane runs, then scalars: max b and max (255 - b); int16, cf32: max |k|, 0
-    uint32_t ends;
-    uint64_t s1, s2;       // sum u, sum u^2 (int16: 0, sum k^2)
-};
-
-__device__ __forceinline__ uint32_t rd_lv_pkmax(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(rd_u16x2, a), __builtin_bit_cast(rd_u16x2, b)));
-}
-// bytes of n that are zero (no carry crosses a byte: 0x7F + 0x7F < 0x100)
-__device__ __forceinline__ uint32_t rd_lv_zero_bytes(uint32_t n) {
-    return (uint32_t)__builtin_popcount(~((((n & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | n) | 0x7F7F7F7Fu));
-}
-__device__ __forceinline__ void rd_lv_bytes(rd_lv_sums &a, uint4 v, uint32_t flip) {
-    const uint32_t w[4] = {v.x ^ flip, v.y ^ flip, v.z ^ flip, v.w ^ flip};
-    uint32_t s1 = 0u, s2 = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t e = w[i] & 0x00FF00FFu, o = (w[i] >> 8) & 0x00FF00FFu;
-        a.hi = rd_lv_pkmax(rd_lv_pkmax(a.hi, e), o);
-        a.lo = rd_lv_pkmax(rd_lv_pkmax(a.lo, e ^ 0x00FF00FFu), o ^ 0x00FF00FFu);
-        a.ends += rd_lv_zero_bytes(w[i]) + rd_lv_zero_bytes(~w[i]);
-        s1 = __builtin_amdgcn_udot4(w[i], 0x01010101u, s1, false);
-        s2 = __builtin_amdgcn_udot4(w[i], w[i], s2, false);
-    }
-    a.s1 += s1;
-    a.s2 += s2;
-}
-__device__ __forceinline__ void rd_lv_words(rd_lv_sums &a, uint4 v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int k0 = (int)(int16_t)(w[i] & 0xFFFFu), k1 = (int)w[i] >> 16;
-        const uint32_t m0 = (uint32_t)(k0 < 0 ? -k0 : k0), m1 = (uint32_t)(k1 < 0 ? -k1 : k1);   // 0 .. 32768
-        a.hi = max(a.hi, max(m0, m1));
-        a.ends += (uint32_t)(k0 == -32768 || k0 == 32767) + (uint32_t)(k1 == -32768 || k1 == 32767);
-        a.s2 += (uint64_t)(m0 * m0 + m1 * m1);   // <= 2^31
-    }
-}
-// float32 components in int16 units (header: RD_IQ_CF32): k = clip(rint(2^15 adm(v)), -32768, 32767), the product exact
-// in fp32, rint ties-to-even; a NaN is the value 0 and counts as clipped
-__device__ __forceinline__ void rd_lv_floats(rd_lv_sums &a, uint4 v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float f = __builtin_bit_cast(float, w[i]);
-        const int k = (int)fminf(fmaxf(rintf(rd_chan_adm(w[i]) * 32768.0f), -32768.0f), 32767.0f);
-        const uint32_t m = (uint32_t)(k < 0 ? -k : k);   // 0 .. 32768
-        a.hi = max(a.hi, m);
-        a.ends += (uint32_t)(k == -32768 || k == 32767 || f != f);
-        a.s2 += (uint64_t)(m * m);   // <= 2^30
-    }
-}
-// the workgroup's totals in thread 0 (hi / lo as scalars)
-__device__ __forceinline__ void rd_lv_reduce(rd_lv_sums &a, bool packed) {
-    __shared__ uint32_t r32[3][RD_LV_THREADS / 64];
-    __shared__ uint64_t r64[2][RD_LV_THREADS / 64];
-    if (packed) {
-        a.hi = max(a.hi & 0xFFFFu, a.hi >> 16);
-        a.lo = max(a.lo & 0xFFFFu, a.lo >> 16);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.hi = max(a.hi, (uint32_t)__shfl_xor((int)a.hi, off));
-        a.lo = max(a.lo, (uint32_t)__shfl_xor((int)a.lo, off));
-        a.ends += (uint32_t)__shfl_xor((int)a.ends, off);
-        a.s1 += (uint64_t)__shfl_xor((unsigned long long)a.s1, off);
-        a.s2 += (uint64_t)__shfl_xor((unsigned long long)a.s2, off);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { r32[0][wave] = a.hi; r32[1][wave] = a.lo; r32[2][wave] = a.ends; r64[0][wave] = a.s1; r64[1][wave] = a.s2; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < RD_LV_THREADS / 64; w++) {
-            a.hi = max(a.hi, r32[0][w]); a.lo = max(a.lo, r32[1][w]); a.ends += r32[2][w]; a.s1 += r64[0][w]; a.s2 += r64[1][w];
-        }
-}
-
-__global__ __launch_bounds__(RD_LV_THREADS) void k_chan_levels(const uint4 *__restrict__ chan, size_t ch_stride_vec, size_t ch_vec,
-                                                               int n_ch, const float *__restrict__ gains,
-                                                               const uint4 *__restrict__ wide, size_t in_vec, int fmt, unsigned n_in,
-                                                               uint64_t seq, rd_chan_level *out, rd_input_level *in, uint32_t *acc) {
-    rd_lv_sums a = {0u, 0u, 0u, 0ull, 0ull};
-    if ((int)blockIdx.x < n_ch) {
-        const int c = (int)blockIdx.x;
-        const uint4 *src = chan + (size_t)c * ch_stride_vec;
-#pragma unroll 4
-        for (size_t q = threadIdx.x; q < ch_vec; q += RD_LV_THREADS) rd_lv_bytes(a, src[q], 0u);
-        rd_lv_reduce(a, true);
-        if (threadIdx.x == 0) {
-            const uint64_t n = 16 * (uint64_t)ch_vec;
-            out[c].power = 4 * a.s2 + 65025 * n - 1020 * a.s1;
-            out[c].peak = max(2 * a.hi, 2 * a.lo) - 255u;     // (one of the two is >= 128)
-            out[c].clipped = a.ends;
-            out[c].gain = gains[c];
-            out[c].chunk = (uint32_t)seq;
-        }
-        return;
-    }
-    const unsigned slice = blockIdx.x - (unsigned)n_ch;
-    const size_t stride = (size_t)n_in * RD_LV_THREADS;
-    if (fmt == RD_IQ_S16) {
-#pragma unroll 4
-        for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_words(a, wide[q]);
-    } else if (fmt == RD_IQ_CF32) {
-#pragma unroll 4
-        for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_floats(a, wide[q]);
-    } else {
-        const uint32_t flip = fmt == RD_IQ_S8 ? 0x80808080u : 0u;
-#pragma unroll 4
-        for (size_t q = (size_t)slice * RD_LV_THREADS + threadIdx.x; q < in_vec; q += stride) rd_lv_bytes(a, wide[q], flip);
-    }
-    rd_lv_reduce(a, !rd_fmt_digits(fmt));
-    if (threadIdx.x != 0) return;
-    unsigned long long *acc64 = (unsigned long long *)(acc + 4);
-    atomicMax(&acc[0], a.hi);
-    atomicMax(&acc[1], a.lo);
-    atomicAdd(&acc[2], a.ends);
-    atomicAdd(&acc64[0], (unsigned long long)a.s1);
-    atomicAdd(&acc64[1], (unsigned long long)a.s2);
-    __threadfence();
-    if (atomicAdd(&acc[3], 1u) != n_in - 1) return;
-    __threadfence();
-    // the last ticket: every slice's atomics have been performed; take the totals and leave zeros
-    const uint32_t hi = atomicExch(&acc[0], 0u), lo = atomicExch(&acc[1], 0u), ends = atomicExch(&acc[2], 0u);
-    const uint64_t s1 = atomicExch(&acc64[0], 0ull), s2 = atomicExch(&acc64[1], 0ull);
-    atomicExch(&acc[3], 0u);
-    const uint64_t n = 16 * (uint64_t)in_vec;                // bytes of the chunk
-    if (fmt == RD_IQ_U8) {
-        in->power = 4 * s2 + 65025 * n - 1020 * s1;
-        in->peak = max(2 * hi, 2 * lo) - 255u;
-    } else if (fmt == RD_IQ_S8) {
-        in->power = s2 + 16384 * n - 256 * s1;
-        in->peak = max(hi + 127u, lo + 128u) - 255u;         // max(max u - 128, 128 - min u)
-    } else {
-        in->power = s2;
-        in->peak = hi;
-    }
-    in->clipped = ends;
-    in->chunk = seq;
 }
 
 // ------------------------------------------------------------------------------------------
 // C ABI (include/rtldavis_hip.h)
 // ------------------------------------------------------------------------------------------
-
-static uint16_t f16_rn(double v) {  // round to nearest even f16 (|v| < 65504)
-    const _Float16 h = (_Float16)v;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-static double f16_val(uint16_t b) {
-    _Float16 h;
-    memcpy(&h, &b, 2);
-    return (double)h;
-}
-
-// LDS bytes of a workgroup's staged window (a multiple of 16, one spare vector)
-static size_t chan_lds_bytes(int fmt, int decim, int t_pad) {
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * decim + t_pad + rd_fmt_kc(fmt);
-    return (rd_fmt_lds_bps(fmt) * span + 15 + 16) & ~(size_t)15;
-}
-
-// The tables of channel c for the shift `shift_hz` (Hz, as given) and the phase accumulator `phase` (header: RETUNE; 0 at
-// create): its two rows of the A operand, its DC entries and 32-output rotation, shifts[c].  On the host - rd_chan_create_fmt
-// for every channel, rd_chan_retune for a channel retuned before the device tables exist; k_chan_retune is the same on
-// the device.
-static void chan_build_channel(rd_chan *h, int c, int64_t shift_hz, int64_t phase) {
-    const rd_chan_config *cfg = &h->cfg;
-    const int fmt = h->fmt, T = cfg->n_taps, t_pad = h->t_pad, kc = rd_fmt_kc(fmt), n_q = t_pad / kc + 1;
-    const double *taps = h->taps.data();
-    const double tap_scale = h->tap_scale;
-    const double wide_rate = (double)cfg->out_rate * cfg->decim;
-    const double dc_level = fmt == RD_IQ_U8 ? 127.4 : fmt == RD_IQ_S8 ? 128.0 : 0.0;
-    h->shift_hz[c] = shift_hz;
-    h->phase[c] = phase;
-    h->shifts[c] = ((shift_hz % cfg->out_rate) + cfg->out_rate) % cfg->out_rate;  // shift mod Fo in [0, Fo): all the output phasor needs
-    std::vector<double> gr(t_pad), gi(t_pad);
-    for (int k = 0; k < t_pad; k++) {
-        gr[k] = gi[k] = 0.0;
-        if (k >= T) continue;
-        // g_c[k] = h[k] e^{+j 2 pi shift k / Fw}; the phase through an exact integer remainder
-        const __int128 prod = (__int128)shift_hz * k;
-        const long fw = (long)cfg->out_rate * cfg->decim;
-        long r = (long)(prod % fw);
-        if (r < 0) r += fw;
-        const double ph = 2.0 * M_PI * ((double)r / wide_rate);
-        gr[k] = (double)(float)(taps[k] * cos(ph));  // the fp32 taps are the definition's taps on the device
-        gi[k] = (double)(float)(taps[k] * sin(ph));
-    }
-    // DC term: output t sees taps k <= D t (zero history before)
-    double sr = 0.0, si = 0.0;
-    int kdone = 0;
-    for (int t = 0; t <= RD_CHAN_EARLY; t++) {
-        // (RD_IQ_S8 stages 0x80 = the value 0 before the capture: every output sees all the taps)
-        const long kmax = t < RD_CHAN_EARLY && fmt == RD_IQ_U8 ? (long)cfg->decim * t : (long)t_pad - 1;
-        for (; kdone < t_pad && kdone <= kmax; kdone++) { sr += gr[kdone]; si += gi[kdone]; }
-        // lut(b) = (b - 127.4) / 127.6 and the kernel sums g b: the constant is -127.4 (1 + j)(sr + j si)
-        // (128 for the offset-binary bytes of RD_IQ_S8, nothing for RD_IQ_S16)
-        h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2] = (float)(-dc_level * (sr - si));
-        h->h_dc[((size_t)c * RD_CHAN_DCN + t) * 2 + 1] = (float)(-dc_level * (sr + si));
-    }
-    {   // the rotation that takes the output phasor 32 output times on (exact remainder, float64 sin / cos)
-        const long inc = (long)(((__int128)h->shifts[c] * 32) % cfg->out_rate);
-        const double ph = -2.0 * M_PI * ((double)inc / (double)cfg->out_rate);
-        h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2] = (float)cos(ph);
-        h->h_dc[((size_t)c * RD_CHAN_DCN + RD_CHAN_EARLY + 1) * 2 + 1] = (float)sin(ph);
-    }
-    // rows 2c (re) and 2c+1 (im); kappa = 2 i + comp, window sample i = t_pad - 1 - k
-    const int grp = c / (16 * RD_CHAN_RBG), rb = (c / 16) % RD_CHAN_RBG, r0 = 2 * (c % 16);
-    // RD_IQ_S16: kappa = 4 i + 2 comp + digit, a lane holds two samples (Ilo Ihi Qlo Qhi each); the low digit's taps
-    // are scaled by 2^-8 against the high digit's.  RD_IQ_CF32: the same layout, both digits against the same tap
-    const int per_lane = kc / 2, n_dig = rd_fmt_digits(fmt) ? 2 : 1;
-    for (int i = 0; i < kc * n_q; i++) {   // window sample i of a column <-> tap k = t_pad - i (the window starts at D t - t_pad)
-        const int k = t_pad - i;
-        if (k < 0 || k >= t_pad) continue;  // (zero taps: the entries stay 0)
-        const int q = i / kc, hh = (i % kc) / per_lane, sl = i % per_lane;  // K step, lane half, sample within the lane's
-        for (int part = 0; part < 2; part++)
-            for (int comp = 0; comp < 2; comp++)
-                for (int dig = 0; dig < n_dig; dig++) {
-                    const double a = part == 0 ? (comp == 0 ? gr[k] : -gi[k]) : (comp == 0 ? gi[k] : gr[k]);
-                    const double as = a * tap_scale * (fmt == RD_IQ_S16 && dig == 0 ? 1.0 / 256.0 : 1.0);
-                    const uint16_t hi = f16_rn(as), lo = f16_rn(as - f16_val(hi));
-                    const uint16_t term[RD_CHAN_TERMS] = {hi, lo};
-                    const int lane = 32 * hh + r0 + part;
-                    // element position inside the fragment, see the kernel's B fragments:
-                    // (I0 I1 Q0 Q1 | I2 I3 Q2 Q3), or (Ilo Ihi Qlo Qhi | the same of the second sample)
-                    const int el = rd_fmt_digits(fmt) ? 4 * sl + 2 * comp + dig : 4 * (sl / 2) + 2 * comp + (sl % 2);
-                    for (int tm = 0; tm < RD_CHAN_TERMS; tm++) {
-                        const size_t at = (((((size_t)grp * n_q + q) * RD_CHAN_TERMS + tm) * RD_CHAN_RBG + rb) * 64 + lane) * 8 + el;
-                        h->h_amat[at] = term[tm];
-                    }
-                }
-    }
-}
 
 extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, const int64_t *shift_hz, rd_chan **out) {
     return rd_chan_create_fmt(cfg, RD_IQ_U8, taps, shift_hz, out);
@@ -769,51 +430,12 @@ extern "C" int rd_chan_create(const rd_chan_config *cfg, const double *taps, con
 
 extern "C" int rd_chan_create_fmt(const rd_chan_config *cfg, int fmt, const double *taps, const int64_t *shift_hz,
                                   rd_chan **out) {
-    if (!cfg || !taps || !shift_hz || !out) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (fmt != RD_IQ_U8 && fmt != RD_IQ_S8 && fmt != RD_IQ_S16 && fmt != RD_IQ_CF32) return rd_fail_msg(RD_ERR_ARG, "unknown sample format %d", fmt);
-    if (cfg->decim < 4 || cfg->decim > 4096 || cfg->decim % 4 || cfg->n_taps < 1 || cfg->n_taps > 8192 ||
-        cfg->n_channels < 1 || cfg->n_channels > 4096 || cfg->out_rate < 1 || cfg->out_rate >= (1 << 26) ||
-        !(cfg->gain > 0.0))
-        return rd_fail_msg(RD_ERR_ARG, "channelizer config out of range (decim: a multiple of 4)");
-    const int t_pad = (cfg->n_taps + RD_CHAN_KC - 1) / RD_CHAN_KC * RD_CHAN_KC;
-    const int kc = rd_fmt_kc(fmt);
-    const size_t span = (size_t)(RD_CHAN_TT - 1) * cfg->decim + t_pad + kc;
-    if (rd_fmt_lds_bps(fmt) * span + 16 > 160 * 1024)
-        return rd_fail_msg(RD_ERR_ARG, "decim x 127 + n_taps samples of %d bytes do not fit the 160 KiB LDS", rd_fmt_lds_bps(fmt));
-    // (RD_IQ_S16 and RD_IQ_CF32 have no DC term, hence no table of early ones and no limit from it)
-    const int n_early = rd_fmt_digits(fmt) ? 0 : (t_pad - 1 + cfg->decim - 1) / cfg->decim;
-    if (n_early > RD_CHAN_EARLY) return rd_fail_msg(RD_ERR_ARG, "n_taps / decim too large");
+    if (!out) return rd_fail_msg(RD_ERR_ARG, "null argument");
     rd_chan *h = new rd_chan();
-    h->cfg = *cfg;
-    h->fmt = fmt;
-    const int T = cfg->n_taps;
-    h->t_pad = t_pad;
-    h->n_early = n_early;
-    h->n_groups = (cfg->n_channels + 16 * RD_CHAN_RBG - 1) / (16 * RD_CHAN_RBG);
-    const int n_q = t_pad / kc + 1;  // the window starts one sample early (aligned): one more K step
-    h->h_amat.assign((size_t)h->n_groups * n_q * (RD_CHAN_Q_BYTES / 2), 0);
-    h->h_dc.assign((size_t)cfg->n_channels * RD_CHAN_DCN * 2, 0.0f);
-    h->shifts.resize(cfg->n_channels);
-    h->shift_hz.resize(cfg->n_channels);
-    h->phase.resize(cfg->n_channels);
-    h->gains.assign(cfg->n_channels, (float)cfg->gain);
-    h->taps.assign(taps, taps + T);
-    // every |g_c[k]| <= max |h[k]|: scale the taps by the power of two that brings that just below 2^15 (f16: 11
-    // significant bits from 2^-14 up), the kernel multiplies the sums back
-    double hmax = 0.0;
-    for (int k = 0; k < T; k++) hmax = std::max(hmax, std::fabs(taps[k]));
-    int sexp = 0;
-    if (hmax > 0.0) sexp = 14 - (int)std::ceil(std::log2(hmax));
-    if (sexp > 60) sexp = 60;
-    if (sexp < -60) sexp = -60;
-    h->tap_scale = std::ldexp(1.0, sexp);
-    // (+24: the samples enter as k 2^-24; RD_IQ_S16: the low digit's taps carry 2^-8 more, so that the high digit's
-    // factor 256 stays inside f16; RD_IQ_CF32: the samples enter as 2^12 x, real f16 values, not raw patterns)
-    h->tap_unscale = fmt == RD_IQ_CF32 ? (float)std::ldexp(1.0, -sexp - RD_CF32_PRESCALE_LOG2)
-                                       : (float)std::ldexp(1.0, -sexp + 24 + (fmt == RD_IQ_S16 ? 8 : 0));
-    for (int c = 0; c < cfg->n_channels; c++) chan_build_channel(h, c, shift_hz[c], 0);
-    *out = h;
-    return RD_OK;
+    const int rc = rd_chan_tables_create(h, cfg, fmt, taps, shift_hz);   // (the argument rules; no device)
+    if (rc) delete h;
+    else *out = h;
+    return rc;
 }
 
 extern "C" void rd_chan_destroy(rd_chan *h) {
@@ -890,7 +512,7 @@ static const void *chan_kernel(bool stream, int fmt) {
 static int chan_launch(rd_chan *h, bool stream, const uint8_t *wide, long n_wide, const uint8_t *prev, int n_early,
                        long t_base_mod, long n_out, unsigned gx, void *dst, size_t dst_stride, hipStream_t st) {
     int T = h->t_pad, D = h->cfg.decim, n_ch = h->cfg.n_channels;
-    const size_t lds = chan_lds_bytes(h->fmt, D, T);
+    const size_t lds = rd_chan_lds_bytes(h->fmt, D, T);
     const uint4 *amat = (const uint4 *)h->d_amat;
     const float2 *dc = (const float2 *)h->d_dc;
     const int64_t *shifts = h->d_shifts, *phase = h->d_phase;
@@ -914,7 +536,7 @@ extern "C" int rd_chan_run(rd_chan *h, size_t n_out, void *dst_dev, size_t dst_s
         return rd_fail_msg(RD_ERR_ARG, "n_out exceeds capture length / decim");
     if (dst_stream_stride < 2 * n_out || (dst_stream_stride & 1))
         return rd_fail_msg(RD_ERR_ARG, "destination stride too small for n_out samples");
-    const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
+    const size_t lds = rd_chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
     HIPCHK(hipFuncSetAttribute(chan_kernel(false, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned gx = (unsigned)((n_out + RD_CHAN_TT - 1) / RD_CHAN_TT);
     return chan_launch(h, false, h->d_wide, (long)h->wide_n, nullptr, h->n_early, 0L, (long)n_out, gx, dst_dev,
@@ -979,7 +601,7 @@ int rd_chan_stream_prepare(rd_chan *h) {
     if (!h) return rd_fail_msg(RD_ERR_ARG, "null argument");
     int rc = chan_alloc(h, 0);
     if (rc) return rc;
-    const size_t lds = chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
+    const size_t lds = rd_chan_lds_bytes(h->fmt, h->cfg.decim, h->t_pad);
     HIPCHK(hipFuncSetAttribute(chan_kernel(true, h->fmt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (!h->d_taps) {   // what a retune needs: the float64 taps, and the records' staging (two pinned slots, one on the device)
         const size_t rt_bytes = (size_t)h->cfg.n_channels * 4 * sizeof(int64_t);
@@ -1008,13 +630,13 @@ int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t 
             return rd_fail_msg(RD_ERR_ARG, "retune: record %d out of range", i);
     if (n == 0) return RD_OK;
     if (!h->dev_ready) {
-        for (int i = 0; i < n; i++) chan_build_channel(h, (int)rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]);
+        for (int i = 0; i < n; i++) rd_chan_tables_build(h, (int)rec[3 * i], rec[3 * i + 1], rec[3 * i + 2]);
         return RD_OK;
     }
     if (!h->d_taps) return rd_fail_msg(RD_ERR_STATE, "rd_chan_stream_prepare first");
     int64_t *stage = h->h_rt + (size_t)slot * n_ch * 4;
     for (int i = 0; i < n; i++) {
-        stage[4 * i] = rec[3 * i]; stage[4 * i + 1] = rec[3 * i + 1]; stage[4 * i + 2] = ((rec[3 * i + 1] % fo) + fo) % fo;
+        stage[4 * i] = rec[3 * i]; stage[4 * i + 1] = rec[3 * i + 1]; stage[4 * i + 2] = rd_chan_shift_mod(rec[3 * i + 1], fo);
         stage[4 * i + 3] = rec[3 * i + 2];
     }
     HIPCHK(hipMemcpyAsync(h->d_rt, stage, (size_t)n * 4 * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -1033,21 +655,13 @@ int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t 
     return RD_OK;
 }
 
-// GAIN: n = n_channels gains, every one finite and > 0 (the rule of cfg.gain), as the float32 values the table takes
-static int chan_check_gains(const rd_chan *h, const double *gain, int n) {
-    if (!h || !gain) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (n != h->cfg.n_channels) return rd_fail_msg(RD_ERR_ARG, "Incompatible array sizes: %d gains for %d channels", n, h->cfg.n_channels);
-    for (int c = 0; c < n; c++)
-        if (!(gain[c] > 0.0) || !std::isfinite(gain[c]) || !((float)gain[c] > 0.0f) || !std::isfinite((float)gain[c]))
-            return rd_fail_msg(RD_ERR_ARG, "channel %d: a gain must be finite and > 0 (in float32 too)", c);
-    return RD_OK;
-}
-int rd_chan_check_gains(const rd_chan *h, const double *gain, int n) { return chan_check_gains(h, gain, n); }
+// GAIN: the argument check of rd_chan_set_gain / rd_wb_set_gain (rd_chan_tables.cpp: rd_chan_tables_check_gains)
+int rd_chan_check_gains(const rd_chan *h, const double *gain, int n) { return rd_chan_tables_check_gains(h, gain, n); }
 
 // One-shot form: the gains of the runs that follow.  A quiet handle: the caller has waited for the streams its earlier
 // rd_chan_run calls were queued on (the copy below is not ordered against them).
 extern "C" int rd_chan_set_gain(rd_chan *h, const double *gain, int n) {
-    int rc = chan_check_gains(h, gain, n);
+    int rc = rd_chan_check_gains(h, gain, n);
     if (rc) return rc;
     std::vector<float> g(n);
     for (int c = 0; c < n; c++) g[c] = (float)gain[c];
@@ -1079,25 +693,6 @@ int rd_chan_stream_gains(rd_chan *h, const float *gain, int slot, hipStream_t st
     return RD_OK;
 }
 
-// LEVELS: one launch behind a streamed chunk's k_channelize on st.  out / in: device addresses of mapped host memory
-// (the caller's pinned slot of the chunk's parity); acc: RD_LV_ACC_WORDS words of device memory, zero between launches.
-int rd_chan_stream_levels(rd_chan *h, const uint8_t *wide, size_t n_out, const uint8_t *chan_out, size_t out_stride,
-                          uint64_t seq, rd_chan_level *out, rd_input_level *in, uint32_t *acc, hipStream_t st) {
-    if (!h || !wide || !chan_out || !out || !in || !acc) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (!h->dev_ready) return rd_fail_msg(RD_ERR_STATE, "rd_chan_stream_prepare first");
-    if (n_out == 0 || n_out % RD_CHAN_TT || out_stride < 2 * n_out || (out_stride & 15))
-        return rd_fail_msg(RD_ERR_ARG, "levels: a chunk of %zu outputs, stride %zu", n_out, out_stride);
-    const int n_ch = h->cfg.n_channels;
-    // 16-byte vectors: 2 n_out bytes per channel (n_out % 128 == 0), n_out decim IQ pairs of the capture (decim % 4 == 0)
-    const size_t ch_vec = 2 * n_out / 16, in_vec = (size_t)rd_fmt_in_bps(h->fmt) * n_out * (size_t)h->cfg.decim / 16;
-    const unsigned n_in = (unsigned)std::min<size_t>(RD_LV_MAX_SLICES, (in_vec + RD_LV_THREADS * 8 - 1) / (RD_LV_THREADS * 8));
-    hipLaunchKernelGGL(k_chan_levels, dim3((unsigned)n_ch + n_in), dim3(RD_LV_THREADS), 0, st, (const uint4 *)chan_out,
-                       out_stride / 16, ch_vec, n_ch, (const float *)h->d_gains, (const uint4 *)wide, in_vec, h->fmt, n_in,
-                       seq, out, in, acc);
-    HIPCHK(hipGetLastError());
-    return RD_OK;
-}
-
 void rd_chan_tuning(const rd_chan *h, const int64_t **shift_hz, const int64_t **phase) {
     *shift_hz = h->shift_hz.data();
     *phase = h->phase.data();
@@ -1123,6 +718,8 @@ int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, 
 
 int rd_chan_format(const rd_chan *h) { return h ? h->fmt : RD_IQ_U8; }
 int rd_chan_n_channels(const rd_chan *h) { return h ? h->cfg.n_channels : 0; }
+int rd_chan_decim(const rd_chan *h) { return h ? h->cfg.decim : 0; }
+const float *rd_chan_device_gains(const rd_chan *h) { return h && h->dev_ready ? h->d_gains : nullptr; }
 int64_t rd_chan_out_rate(const rd_chan *h) { return h ? h->cfg.out_rate : 0; }
 int64_t rd_chan_wide_rate(const rd_chan *h) { return h ? (int64_t)h->cfg.out_rate * h->cfg.decim : 0; }
 int rd_chan_bytes_per_sample(const rd_chan *h) { return h ? rd_fmt_in_bps(h->fmt) : 0; }

@@ -220,13 +220,13 @@ int rd_chan_stream_launch(rd_chan *h, const uint8_t *wide, const uint8_t *prev, 
 // ordering) and k_chan_retune, queued on st.  rd_chan_tuning: the shifts (as given) and phases the tables hold.
 int rd_chan_retune(rd_chan *h, const int64_t *rec, int n, int slot, hipStream_t st);
 void rd_chan_tuning(const rd_chan *h, const int64_t **shift_hz, const int64_t **phase);
-// Gains (rd_channelizer.hip: GAIN): the argument check of rd_chan_set_gain / rd_wb_set_gain; the float32 table the
+// Gains (rd_channelizer.hip: GAIN): the argument check of rd_chan_set_gain / rd_wb_set_gain (rd_chan_tables.cpp); the float32 table the
 // handle's kernels use (what the last rd_chan_stream_gains queued, or the host's before the device tables exist); and the
 // update itself - the whole table through pinned slot `slot` in one copy on st, nothing when no entry differs.
 int rd_chan_check_gains(const rd_chan *h, const double *gain, int n);
 const float *rd_chan_gains(const rd_chan *h);
 int rd_chan_stream_gains(rd_chan *h, const float *gain, int slot, hipStream_t st);
-// Levels of one streamed chunk (k_chan_levels) behind its rd_chan_stream_launch on st: wide / chan_out as given to that
+// Levels of one streamed chunk (rd_chan_levels.hip: k_chan_levels) behind its rd_chan_stream_launch on st: wide / chan_out as given to that
 // launch; out ([n_channels]) and in: device addresses of mapped host memory; acc: RD_LV_ACC_WORDS zeroed device words
 // (the kernel leaves them zero).
 #define RD_LV_ACC_WORDS 8
@@ -333,6 +333,8 @@ int rd_burst_clips_launch(const rd_config *cfg, const uint8_t *chan_out, const u
                           const void *search_slot, int n_search, const rd_bc_header *prev_hdr, void *slot, hipStream_t st);
 int rd_chan_format(const rd_chan *h);             // RD_IQ_* of the handle
 int rd_chan_n_channels(const rd_chan *h);
+int rd_chan_decim(const rd_chan *h);
+const float *rd_chan_device_gains(const rd_chan *h);   // the device's gain table; null before the device tables exist
 int64_t rd_chan_out_rate(const rd_chan *h);
 int64_t rd_chan_wide_rate(const rd_chan *h);
 int rd_chan_bytes_per_sample(const rd_chan *h);   // of an IQ pair in the handle's sample format

@@ -671,7 +671,7 @@ struct wb_chunk {
 };
 static uint8_t *wb_dev(rd_wideband *w, int kind, const wb_chunk &c) { return w->slots[kind].d[c.s]; }
 
-// Levels (rd_wb_set_levels / rd_wb_levels; rd_channelizer.hip, LEVELS): k_chan_levels behind the chunk's k_channelize
+// Levels (rd_wb_set_levels / rd_wb_levels; rd_chan_levels.hip, LEVELS): k_chan_levels behind the chunk's k_channelize
 // (behind e_chan: the copy stream never waits for it).  It and k_chan_spectrum READ d_wide[s]: that buffer is next
 // overwritten by the copy of chunk k+2, which waits for e_chan of chunk k+1 - recorded later on the compute stream than
 // either kernel of chunk k, so the copy cannot overtake them although they come behind chunk k's own e_chan.

@@ -1,5 +1,5 @@
 """WidebandReceiver.set_gain / levels() on the device (rd_wb_set_gain -> the gains[ch] load of k_channelize, rd_wb_set_levels
--> k_chan_levels; rd_channelizer.hip): every chunk of a receiver whose per-channel gains change between chunks, with
+-> k_chan_levels; rd_channelizer.hip, rd_chan_levels.hip): every chunk of a receiver whose per-channel gains change between chunks, with
 chunks in flight and a retune beside them, against the float64 model at each channel's gain and its a-priori bound
 (tests/gain_cases.py); receivers that never call set_gain, are constructed with the gain or are reset - byte for byte;
 the level records against NumPy integers of the same bytes, exactly; and the gain loop closed through levels() and
