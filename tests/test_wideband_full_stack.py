@@ -164,13 +164,13 @@ def _assert_front(cfg, k, g, w, what):
     assert g["levels"].chunk == k and have == w["levels"][0], (what, k, "levels")
     assert g["levels"].channels["gain"].dtype == np.float32 and g["levels"].channels["gain"].tolist() == w["levels"][1].tolist(), (what, k)
     assert tuple(g["levels"].input) == w["levels"][2], (what, k, "input level")
-    sp, (p, s, tol) = g["spectrum"], w["spectrum"]
+    sp, (p, s, _) = g["spectrum"], w["spectrum"]
     assert sp.power.shape == (cfg.n_bins,) and sp.segments == s and sp.chunk == k, (what, k, "spectrum")
     assert np.array_equal(sp.freqs_hz, SM.freqs(RC.CENTRE, cfg.fw, cfg.n_bins))
-    err = float(np.abs(sp.power - p).max())
-    assert err <= tol, (what, k, "spectrum", err / tol)
+    ratio = SM.excess(sp.power, p, cfg.n_bins)                # per bin: spectrum_model.tol_bin
+    assert ratio <= 1.0, (what, k, "spectrum", ratio)
     assert_rows_match(_rows(g["parsed"]), w["parsed"], (what, k, "parsed"))
-    return err / tol
+    return ratio
 
 
 def _assert_chain(cfg, k, g, w, what, quality=True):
@@ -208,7 +208,7 @@ def test_every_accessor_equals_its_model(name):
         ratio = _assert_front(cfg, k, g, w, name)
         _assert_chain(cfg, k, g, w, name)
         print(f"\n[full-stack] {name} chunk {k}: exempt {s['exempt']:.2%}, mismatches {s['mismatches']}/{g['block'][rows].size}, "
-              f"worst distance {s['worst_dist']:.2e} ({s['worst_ratio']:.2f} of delta); spectrum err / tol {ratio:.4f}; records: "
+              f"worst distance {s['worst_dist']:.2e} ({s['worst_ratio']:.2f} of delta); spectrum err / tol_bin {ratio:.4f}; records: "
               f"parsed {len(g['parsed'])} bursts {g['bursts'].records.size} messages {g['messages'].records.size} "
               f"expected {g['expected'].records.size} quality {g['quality_m'].size}+{g['quality_x'].size} "
               f"packets {sum(len(p) for p in g['packets'])}")
