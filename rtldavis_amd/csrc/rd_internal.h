@@ -7,21 +7,12 @@
 #include "../../include/rtldavis_hip.h"
 #include "rd_hiphost.h"
 #include "rd_host.h"
+#include "rd_batch_plan.h"
 
-// counters[] slots (device uint32)
-// FIX: flagged runs; MATCH: preamble matches (= primary records); REC: second records of
-// block-boundary positions; PARSED: CRC-valid messages
-// OVF: the one-launch tail could not hold this input (1: a stream with more matches than its list, 2: more records
-// than the output array has room for, 8: a group's fix-up bucket overflowed, 16: a workgroup gave up waiting for the
-// totals of the groups in front of it)
-enum { RD_CNT_FIX = 0, RD_CNT_MATCH = 1, RD_CNT_REC = 2, RD_CNT_TASKS = 3, RD_CNT_PARSED = 4, RD_CNT_OVF = 5, RD_CNT_SLOTS = 8 };
-// RD_CNT_FIX: entries in the global fix-up list (k_fixup's input; written by k_tail as the sum over its groups' buckets)
+// the counter slots (RD_CNT_*), the counter set's layout and RD_FT_STREAMS: rd_batch_plan.h (pure host code decides by them)
 // rd_launch_demod flags
 #define RD_DEMOD_FIX_BUCKETS 4u    /* the fix-up entries go to per-group buckets (the one-launch tail, k_tail): fix_list =
                                       [groups][fix_cap] entries, bucket_cnt = [groups] counters, group = stream >> RD_FT_GSH */
-// The one-launch tail (rd_tail.hip: k_tail): a workgroup owns RD_FT_STREAMS consecutive streams
-#define RD_FT_GSH 2
-#define RD_FT_STREAMS (1 << RD_FT_GSH)
 struct rd_ft_bufs {
     uint32_t *fixb = nullptr;    // [groups][fix_bcap] fix-up entries, filled by the demod kernel's waves
     uint32_t *fixcnt = nullptr;  // [groups] entries written (lives behind the counter set of the run: cleared with it)
@@ -29,16 +20,8 @@ struct rd_ft_bufs {
     uint32_t bcap = 0;           // matches a stream's list in LDS holds (a multiple of 32, rd_host.h: rd_ord_bucket_cap)
     uint32_t *gstate = nullptr;  // [3][groups]: (seq << 20 | records), matches, fix-up entries per group
 };
-// Behind the RD_CNT_SLOTS counters the host reads back: the demod kernel's work queues (chunks handed out beyond
-// the first one of every wave).  One counter word sustains ~90 atomics per microsecond, so there are RD_NQUEUE of
-// them, 256 bytes apart; wave w draws from queue w % RD_NQUEUE, which owns the chunks nwaves + q + RD_NQUEUE k.
-#define RD_NQUEUE 32
-#define RD_QUEUE_STRIDE 64                                     /* words */
-#define RD_CNT_QUEUE0 RD_QUEUE_STRIDE                          /* first queue's word index */
-#define RD_CNT_TOTAL (RD_CNT_QUEUE0 + RD_NQUEUE * RD_QUEUE_STRIDE)  /* words per counter set */
-
 // Geometry of the fused demod kernel
-#define RD_TILE_SAMPLES 2048  // 64 lanes x 32 samples: one wave iteration
+// (RD_TILE_SAMPLES, 64 lanes x 32 samples, one wave iteration: rd_batch_plan.h)
 #define RD_TILE_BYTES 4096
 #define RD_INPUT_PAD 8192     // bytes readable past the last stream (ragged last tile)
 

@@ -283,7 +283,7 @@ def sched_of(shape: str, chunk_env: int) -> Sched:
 
 
 def fix_bcap(n):
-    """entries a group's fix-up bucket holds (rd_batch.hip: batch_alloc), a group being RD_FT_STREAMS = 4 consecutive streams"""
+    """entries a group's fix-up bucket holds (rd_batch_plan.cpp: rd_batch_sizes_of), a group being RD_FT_STREAMS = 4 consecutive streams"""
     tps = (n + TILE - 1) // TILE
     return min((2 * 4 * (tps // 4 + 8) + 63) & ~63, 1 << 20)
 

@@ -1274,7 +1274,7 @@ def test_one_launch_tail_overflows_fall_back(dsp, batchmod, golden_streams, monk
                    [synth.synth_stream(9)[: 2 * 8192 * nb]])
     bd = batchmod.BatchDemodulator(prod_cfg(dsp), raw.shape[0], nb)
     want, wbits = CO.demod_batch(raw, CO.make_cfg(), threads=4, want_bits=True)
-    for _ in range(2):   # (the second run of the same input goes straight to the separate kernels)
+    for _ in range(2):   # (every upload gives the one-launch tail its chance again: both runs overflow and fall back)
         bd.upload(raw)
         bd.run()
         res = bd.packets()
@@ -1284,6 +1284,36 @@ def test_one_launch_tail_overflows_fall_back(dsp, batchmod, golden_streams, monk
             assert np.array_equal(bd.bits(i), wbits[i]), i
             got = [(c, p.index, bytes(p.data).hex()) for c, ps in enumerate(res[i]) for p in ps]
             assert got == [(p.call, p.index, bytes(p.data).hex()) for p in want[i]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipelined", [False, True], ids=["event_per_run", "pipelined"])
+def test_tail_overflow_is_remembered_until_the_next_upload(dsp, batchmod, golden_streams, monkeypatch, pipelined):
+    """What an overflow teaches the handle (rd_batch_plan.h: rd_batch_learned).  A stream with more matches than its list
+    in k_tail's LDS (RD_TEST_BUCKET_CAP=2): the run falls back with a second pass.  Run again on the same input: the
+    separate kernels straight away, no one-launch tail and no second pass.  Upload again: the one-launch tail gets its
+    chance, overflows and falls back once more.  The fixtures' packets (dsp.py:128-253) every time."""
+    monkeypatch.setenv("RD_TEST_BUCKET_CAP", "2")
+    seeds = list(range(6))
+    raw = synth.synth_streams(seeds)
+    bd = batchmod.BatchDemodulator(prod_cfg(dsp), len(seeds), synth.BLOCKS_PER_STREAM)
+    bd.set_pipelined(pipelined)
+
+    def run_and_check():
+        bd.run()
+        res = bd.packets()
+        for i, seed in enumerate(seeds):
+            assert_calls_equal(res[i], dense_calls(golden_streams[str(seed)]["calls"], synth.BLOCKS_PER_STREAM))
+        return bd.last_run_forms()
+
+    bd.upload(raw)
+    f = run_and_check()
+    assert f["second_pass"] and not f["ordered_tail"] and not f["one_launch_tail"], f
+    f = run_and_check()          # no new upload: the handle remembers
+    assert not f["one_launch_tail"] and not f["second_pass"] and not f["ordered_tail"], f
+    bd.upload(raw)               # a new input
+    f = run_and_check()
+    assert f["second_pass"] and not f["ordered_tail"] and not f["one_launch_tail"], f
 
 
 @pytest.mark.gpu
