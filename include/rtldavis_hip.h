@@ -963,7 +963,8 @@ int rd_bc_window(int block_size, int have_prev, int64_t a, int64_t e, int32_t *o
  * job (rtldavis_amd/replay.py tiles a long recording with jobs instead).
  * rd_clips_create: RD_ERR_ARG for a configuration that rd_wb_set_burst_decode refuses, except the block_size rule -
  * block_size is ignored here.  No device work (safe before fork).
- * rd_clips_upload: the pool (nbytes even, at least 2), copied to the device and kept until the next upload.
+ * rd_clips_upload: the pool (nbytes even, at least 2), copied to the device and kept until the next upload or synthesis
+ * (CLIP SYNTH below).
  * rd_clips_decode: synchronous, its wait under the deadline of every host wait (RD_WAIT_TIMEOUT_MS).  Any number of
  * calls on one uploaded pool.  msgs[n_jobs] and hdr[n_jobs]: row j is job j, zeros where there is no record / the job is
  * idle; soft: NULL, or [n_jobs][N].  RD_ERR_ARG, with nothing launched, for max_flips outside 0 .. 2, narrow other than
@@ -996,6 +997,73 @@ int rd_clips_decode(rd_clips *h, const rd_clip_job *jobs, int n_jobs, int max_fl
                     rd_cd_header *hdr, int64_t *soft);
 int rd_clips_kernel_ms(rd_clips *h, float *ms);
 int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, int n_jobs, size_t pool_outputs, int *bad, const char **why);
+/* CLIP SYNTH (k_clip_synth, rd_clip_synth.hip): fill the pool of CLIP DECODE on the device with synthetic noisy burst
+ * clips, one small SPEC (rd_clip_spec) per clip and no host bytes - the replay decoder as a Monte-Carlo instrument.  All
+ * quantities are exact integers: tests/clip_synth_cases.py evaluates the same expressions in NumPy and must get the same
+ * bytes, and the same specs give the same pool on every machine and every run.
+ * Spec k describes a clip of `n` outputs at output `offset` of the pool; its output t (0 <= t < n) is two bytes I, Q.
+ *   Burst.  n_sym symbols (0 .. RD_CS_MAX_SYM) whose bits are packed MSB first in bits[] (symbol j is bit 7 - j % 8 of
+ *   bits[j / 8]); `pre` outputs of unmodulated carrier in front of them, `post` behind (each 0 .. RD_CS_MAX_PRE).  The
+ *   first symbol begins at output `at`, which may be negative or past the clip: the clip cuts the burst.  With SL the
+ *   handle's symbol_length, u = t - (at - pre) and L = pre + SL n_sym + post the burst is ON at t iff 0 <= u < L.
+ *   Phase.  phi(u) = phase0 + (u + 1) f_c + f_d D(u) mod 2^32, in units of 2^-32 cycle; D(u) = the sum over the burst's
+ *   outputs 0 .. u of +1 inside a symbol that is 1, -1 inside a symbol that is 0, 0 in pre / post.  f_c (int32) and f_d
+ *   (uint32 < 2^31) are in 2^-32 cycle per output: a Davis burst at the channelizer's IF has f_c = round((-1/4 + cfo /
+ *   out_rate) 2^32) and f_d = round(2^32 / (4 SL)).
+ *   Table.  T[j] = lrint(16384 cos(2 pi j / 4096)), j < 4096 (rd_cs_table; computed once on the host and uploaded);
+ *   c = T[phi >> 20], s = T[((phi - 2^30) mod 2^32) >> 20].
+ *   Noise.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85), key = (seed's low
+ *   word, seed's high word), counter = (t, comp, 0, 0) with comp = 0 for I and 1 for Q; g = the sum of the 16 bytes of
+ *   the four output words - 2040.  The noise depends on the seed and on t alone: not on offset, not on the spec's place
+ *   in the list, not on a neighbour.
+ *   Byte.  S = (256 << 21) + (ON ? amp_q * (c for I, s for Q) : 0) + noise_q * g in int64; byte = clamp((S + 2^21) >> 22,
+ *   0, 255), the shift arithmetic: the bytes are centred on 128 - mid-scale of the offset-binary byte, half a byte above
+ *   the 127.5 the decoders subtract (z = 2 b - 255) - and rounded half up, so the byte mean of a noise-only clip is 128.  amp_q <= 2^16: the amplitude in bytes is amp_q / 256.  noise_q <= 2^20: sigma in bytes
+ *   is noise_q sqrt(16 x 65535 / 12) / 2^22 = noise_q x 295.601 / 2^22.  With both 0 every byte is 128.
+ *   Pool.  rd_clips_synth zeroes the whole device pool (hipMemsetAsync on the handle's stream, in front of the launch)
+ *   and the kernel then writes each clip in whole vectors of 8 outputs: the slack between a clip's end and the next
+ *   multiple of 8 is written as 0, and every byte that belongs to no clip is 0 after the call, whatever the pool held.
+ * Rules (rd_cs_check_specs; no device is touched; *bad and *why as rd_cd_check_jobs): 1 <= n_specs <= RD_CS_MAX_SPECS;
+ * offset % 8 == 0; 1 <= n <= RD_CS_MAX_N; the specs ascend and do not overlap, offset[k] >= roundup8(offset[k-1] +
+ * n[k-1]); offset + n <= pool_outputs; n_sym <= RD_CS_MAX_SYM; pre, post <= RD_CS_MAX_PRE; amp_q <= RD_CS_MAX_AMP;
+ * noise_q <= RD_CS_MAX_NOISE; f_d < 2^31; |at| <= 2^30; pad == 0; the bits of bits[] from n_sym on are 0.  The kernel
+ * applies the per-spec bounds again: a spec that breaks one writes nothing, so no list makes it store outside the pool.
+ * rd_clips_synth: sizes the device pool to pool_outputs (grown as rd_clips_upload grows it, padded to whole vectors),
+ * runs the kernel and waits under the deadline of every host wait.  Afterwards the handle is in the state an upload of
+ * the same bytes leaves it in: rd_clips_decode works on it, and a later rd_clips_upload replaces it.  RD_ERR_ARG with
+ * nothing launched - the pool, and a decode that follows, untouched - for anything rd_cs_check_specs refuses and for a
+ * pool_outputs above RD_CS_MAX_POOL.  rd_clips_synth_ms: the device time of the last synthesis, the zeroing included, by
+ * device events; rd_clips_kernel_ms keeps its meaning.  rd_clips_download: the pool as the device holds it, uploaded or
+ * synthesised; RD_ERR_STATE without a pool, RD_ERR_ARG unless nbytes = 2 pool_outputs. */
+#define RD_CS_MAX_SYM 192
+#define RD_CS_MAX_PRE 4096
+#define RD_CS_MAX_N (1 << 24)
+#define RD_CS_MAX_SPECS (1 << 20)
+#define RD_CS_MAX_AMP (1u << 16)
+#define RD_CS_MAX_NOISE (1u << 20)
+#define RD_CS_MAX_AT (1 << 30)
+#define RD_CS_MAX_POOL (1ull << 40) /* outputs in a synthesised pool at most (2 TiB: above any device's memory) */
+#define RD_CS_TABLE 4096
+typedef struct rd_clip_spec {
+    uint64_t offset;             /* the clip's first output in the pool, in outputs; a multiple of 8 */
+    uint64_t seed;               /* the noise's Philox key */
+    uint32_t n;                  /* outputs in the clip, 1 .. RD_CS_MAX_N */
+    int32_t  at;                 /* the output at which the first symbol begins, relative to the clip's output 0 */
+    uint32_t phase0;             /* 2^-32 cycle */
+    int32_t  f_c;                /* carrier, 2^-32 cycle per output */
+    uint32_t f_d;                /* deviation, 2^-32 cycle per output, < 2^31 */
+    uint32_t amp_q;              /* amplitude in 1/256 byte, at most 2^16 */
+    uint32_t noise_q;            /* noise scale, at most 2^20 */
+    uint32_t n_sym;              /* symbols, 0 .. RD_CS_MAX_SYM */
+    uint16_t pre, post;          /* outputs of plain carrier before and behind the symbols, each 0 .. RD_CS_MAX_PRE */
+    uint32_t pad;                /* 0 */
+    uint8_t  bits[24];           /* the symbols, MSB first; 0 from bit n_sym on */
+} rd_clip_spec;
+int rd_clips_synth(rd_clips *h, const rd_clip_spec *specs, int n_specs, uint64_t pool_outputs);
+int rd_clips_download(rd_clips *h, uint8_t *out, size_t nbytes);
+int rd_clips_synth_ms(rd_clips *h, float *ms);
+int rd_cs_check_specs(const rd_clip_spec *specs, int n_specs, uint64_t pool_outputs, int *bad, const char **why);
+void rd_cs_table(int16_t out[RD_CS_TABLE]);
 /* The number (since create / reset; rd_packet.call of its packets) of the chunk the last fetch returned - the chunk whose
  * records rd_wb_levels, rd_wb_spectrum, rd_wb_bursts and rd_wb_burst_messages hand out, and against which the fetch
  * checked them.  RD_ERR_STATE before any fetch.  Host bookkeeping only. */

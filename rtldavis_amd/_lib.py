@@ -239,6 +239,11 @@ SIGNATURES = {
     "rd_clips_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rd_clips_kernel_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "rd_cd_check_jobs": (C.c_int, [C.POINTER(RdConfig), _P, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]),
+    "rd_clips_synth": (C.c_int, [_P, _P, C.c_int, C.c_uint64]),
+    "rd_clips_download": (C.c_int, [_P, _P, C.c_size_t]),
+    "rd_clips_synth_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "rd_cs_check_specs": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]),
+    "rd_cs_table": (None, [_P]),
     "rd_wb_fetched_chunk": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rd_wideband_debug_advance_clock": (C.c_int, [_P, C.c_uint64]),
     "rd_debug_mfma_taps": (None, [_P]),

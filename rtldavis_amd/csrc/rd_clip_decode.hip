@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rd_burst_common.h"
+#include "rd_clips.h"
 
 #define RD_CD_LEN (RD_CD_MAX_SPAN + RD_BD_MAX_LOOK_W * RD_BU_WINDOW)   // t1 - t0 at most: the span + N SL + 1
 #define RD_CD_LOAD (RD_CD_LEN + 128)                                    // outputs loaded at most
@@ -161,23 +162,6 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_clip_decode(const uint8_t 
 // ------------------------------------------------------------------------------------------
 // host side: the C ABI
 // ------------------------------------------------------------------------------------------
-struct rd_clips {
-    rd_config cfg;
-    uint8_t *d_pool = nullptr;           // the pool, padded to whole 16-byte vectors
-    size_t pool_cap = 0;                 // bytes allocated
-    uint64_t pool_outputs = 0;           // 0: nothing uploaded yet
-    rd_clip_job *d_jobs = nullptr;
-    rd_burst_msg *d_recs = nullptr;
-    rd_cd_header *d_hdr = nullptr;
-    int64_t *d_soft = nullptr;
-    int cap_jobs = 0, cap_soft = 0;      // jobs the buffers hold
-    uint32_t *d_nb = nullptr;            // the narrow-band table, from the first narrow decode on
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool busy = false;                   // a wait gave up: the stream may still hold work on the buffers
-    float kernel_ms = -1.0f;
-};
-
 // the configuration rule of rd_wb_set_burst_decode without its block_size rule: block_size takes no part here
 static int rd_cd_check_config(const rd_config *cfg) {
     if (!cfg) return rd_fail_msg(RD_ERR_ARG, "null argument");
@@ -187,14 +171,14 @@ static int rd_cd_check_config(const rd_config *cfg) {
 }
 
 // the library's polling wait with its deadline (rd_hiphost.h); a wait that gave up leaves the handle busy
-static int rd_cd_wait(rd_clips *h, const char *what) {
+int rd_cd_wait(rd_clips *h, const char *what) {
     const int rc = rd_wait_stream(h->st, what);
     if (!rc) h->busy = false;
     else if (hipStreamQuery(h->st) == hipErrorNotReady) h->busy = true;
     return rc ? rd_fail_msg(rc, "clip decode: %s", rd_last_error()) : RD_OK;
 }
 
-static int rd_cd_prepare(rd_clips *h) {
+int rd_cd_prepare(rd_clips *h) {
     int rc = rd_ensure_device();
     if (rc) return rc;
     if (!h->st) {
@@ -226,17 +210,15 @@ extern "C" void rd_clips_destroy(rd_clips *h) {
     }
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
-    void *bufs[] = {h->d_pool, h->d_jobs, h->d_recs, h->d_hdr, h->d_soft, h->d_nb};
+    if (h->sv0) (void)hipEventDestroy(h->sv0);
+    if (h->sv1) (void)hipEventDestroy(h->sv1);
+    void *bufs[] = {h->d_pool, h->d_jobs, h->d_recs, h->d_hdr, h->d_soft, h->d_nb, h->d_specs, h->d_cs_tab};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete h;
 }
 
-extern "C" int rd_clips_upload(rd_clips *h, const uint8_t *pool, size_t nbytes) {
-    if (!h || !pool) return rd_fail_msg(RD_ERR_ARG, "null argument");
-    if (nbytes < 2 || (nbytes & 1)) return rd_fail_msg(RD_ERR_ARG, "clip decode: a pool of %zu bytes (an even number, at least 2)", nbytes);
-    int rc = rd_cd_prepare(h);
-    if (rc) return rc;
+int rd_cd_size_pool(rd_clips *h, size_t nbytes, size_t *need_out) {
     const size_t need = (nbytes + 15) & ~(size_t)15;
     h->pool_outputs = 0;
     if (need > h->pool_cap) {
@@ -246,6 +228,17 @@ extern "C" int rd_clips_upload(rd_clips *h, const uint8_t *pool, size_t nbytes) 
         if (hipMalloc(&h->d_pool, need) != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "clip decode: hipMalloc of a pool of %zu bytes failed", need);
         h->pool_cap = need;
     }
+    *need_out = need;
+    return RD_OK;
+}
+
+extern "C" int rd_clips_upload(rd_clips *h, const uint8_t *pool, size_t nbytes) {
+    if (!h || !pool) return rd_fail_msg(RD_ERR_ARG, "null argument");
+    if (nbytes < 2 || (nbytes & 1)) return rd_fail_msg(RD_ERR_ARG, "clip decode: a pool of %zu bytes (an even number, at least 2)", nbytes);
+    int rc = rd_cd_prepare(h);
+    if (rc) return rc;
+    size_t need = 0;
+    if ((rc = rd_cd_size_pool(h, nbytes, &need))) return rc;
     if (hipMemcpyAsync(h->d_pool, pool, nbytes, hipMemcpyHostToDevice, h->st) != hipSuccess ||
         (need > nbytes && hipMemsetAsync(h->d_pool + nbytes, 0, need - nbytes, h->st) != hipSuccess))
         return rd_fail_msg(RD_ERR_DEVICE, "clip decode: the copy of the pool failed");

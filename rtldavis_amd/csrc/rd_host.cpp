@@ -322,6 +322,49 @@ extern "C" int rd_cd_check_jobs(const rd_config *cfg, const rd_clip_job *jobs, i
     return RD_OK;
 }
 
+// CLIP SYNTH (include/rtldavis_hip.h): the rules of a spec list.  k_clip_synth applies the per-spec bounds again; the
+// order of the specs and their distance are checked here alone.
+extern "C" int rd_cs_check_specs(const rd_clip_spec *specs, int n_specs, uint64_t pool_outputs, int *bad, const char **why) {
+    static const char *none = "";
+    const char *dummy_why;
+    int dummy_bad;
+    if (!why) why = &dummy_why;
+    if (!bad) bad = &dummy_bad;
+    *why = none;
+    *bad = -1;
+    if (n_specs < 1 || n_specs > RD_CS_MAX_SPECS) { *why = "the number of specs (1 .. 2^20)"; return RD_ERR_ARG; }
+    if (!specs) { *why = "null spec list"; return RD_ERR_ARG; }
+    uint64_t next = 0;                                          // roundup8 of the end of the clip before (below 2^64: see the pool rule)
+    for (int i = 0; i < n_specs; i++) {
+        const rd_clip_spec &s = specs[i];
+        *bad = i;
+        if (s.offset % 8u) { *why = "offset (a multiple of 8)"; return RD_ERR_ARG; }
+        if (s.n < 1u || s.n > (uint32_t)RD_CS_MAX_N) { *why = "n (1 .. 2^24)"; return RD_ERR_ARG; }
+        if (s.offset < next) { *why = "the specs ascend and do not overlap"; return RD_ERR_ARG; }
+        if (s.offset > pool_outputs || (uint64_t)s.n > pool_outputs - s.offset) { *why = "offset + n past the pool"; return RD_ERR_ARG; }
+        if (s.n_sym > (uint32_t)RD_CS_MAX_SYM) { *why = "n_sym (0 .. 192)"; return RD_ERR_ARG; }
+        if (s.pre > RD_CS_MAX_PRE || s.post > RD_CS_MAX_PRE) { *why = "pre, post (0 .. 4096)"; return RD_ERR_ARG; }
+        if (s.amp_q > RD_CS_MAX_AMP) { *why = "amp_q (at most 2^16)"; return RD_ERR_ARG; }
+        if (s.noise_q > RD_CS_MAX_NOISE) { *why = "noise_q (at most 2^20)"; return RD_ERR_ARG; }
+        if (s.f_d >= 0x80000000u) { *why = "f_d (below 2^31)"; return RD_ERR_ARG; }
+        if (s.at < -RD_CS_MAX_AT || s.at > RD_CS_MAX_AT) { *why = "at (-2^30 .. 2^30)"; return RD_ERR_ARG; }
+        if (s.pad != 0u) { *why = "pad != 0"; return RD_ERR_ARG; }
+        for (uint32_t j = s.n_sym; j < 8u * sizeof s.bits; j++)
+            if (s.bits[j >> 3] & (0x80u >> (j & 7u))) { *why = "a bit of bits[] past n_sym"; return RD_ERR_ARG; }
+        // (offset + n <= pool_outputs < 2^64; the round-up wraps only for an end within 7 of 2^64, to 0: then nothing may follow)
+        next = (s.offset + (uint64_t)s.n + 7u) & ~(uint64_t)7u;
+        if (next < s.offset) next = UINT64_MAX;
+    }
+    *bad = -1;
+    return RD_OK;
+}
+
+// CLIP SYNTH: T[j] = lrint(16384 cos(2 pi j / 4096)) in float64, the argument formed as written
+extern "C" void rd_cs_table(int16_t out[RD_CS_TABLE]) {
+    if (!out) return;
+    for (int j = 0; j < RD_CS_TABLE; j++) out[j] = (int16_t)lrint(16384.0 * cos(2.0 * M_PI * (double)j / 4096.0));
+}
+
 // BURST SEARCH (include/rtldavis_hip.h): the list's rules (a chunk's candidates, step 2s: rd_host.h, inline)
 int rd_bs_check_centres(const uint8_t *centres, int n, int *bad, const char **why) {
     static const char *none = "";

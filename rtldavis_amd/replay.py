@@ -15,7 +15,17 @@ A *pool* is a flat byte array of clips, a *job* (``CLIP_JOB_DTYPE``) names one c
 ``offset``, a multiple of 8 - and the range ``tau_lo .. tau_hi`` of candidate positions to test (at most ``MAX_SPAN`` wide,
 relative to the clip's output 0), the direction ``corr`` to slice around ((0, 0): the clip's own, the sum of
 ``z[t] conj(z[t-1])`` over the job's region) and the transmitter id to accept.  A job gives at most one row; ``plan``
-tiles a long recording with jobs instead."""
+tiles a long recording with jobs instead.
+
+``ClipDecoder.synthesize`` fills the pool on the device instead (CLIP SYNTH): one *spec* (``SPEC_DTYPE``) per clip - a burst
+of up to 192 symbols at an integer carrier and deviation, an amplitude, a noise level and a 64-bit seed - and no host
+bytes; ``burst_specs`` writes the specs of Davis bursts in the units of ``synth.synth_bursts``.  The same specs give the
+same pool on every machine: tests/clip_synth_cases.py holds the NumPy model, bit for bit.
+
+    specs, tau = burst_specs(payloads, n=2048, at=300, seed=1, amplitude=0.3, noise=0.2)
+    dec.synthesize(specs)
+    jobs = centred_jobs(specs, tau, span=64)
+    got = dec.decode_jobs(jobs, max_flips=2, narrow=True)"""
 from __future__ import annotations
 
 import ctypes as C
@@ -32,6 +42,18 @@ CLIP_JOB_DTYPE = np.dtype([("offset", np.uint64), ("clock", np.uint64), ("n", np
                            ("tau_lo", np.int32), ("tau_hi", np.int32), ("corr_re", np.int32), ("corr_im", np.int32),
                            ("channel", np.int32), ("pad", np.uint32)])
 CD_HEADER_DTYPE = np.dtype([("n_msgs", np.uint32), ("candidates", np.uint32), ("ca", np.int32), ("cb", np.int32)])
+SPEC_DTYPE = np.dtype([("offset", np.uint64), ("seed", np.uint64), ("n", np.uint32), ("at", np.int32), ("phase0", np.uint32),
+                       ("f_c", np.int32), ("f_d", np.uint32), ("amp_q", np.uint32), ("noise_q", np.uint32), ("n_sym", np.uint32),
+                       ("pre", np.uint16), ("post", np.uint16), ("pad", np.uint32), ("bits", np.uint8, (24,))])
+assert SPEC_DTYPE.itemsize == 80
+MAX_SYM = 192                          # symbols of a spec at most
+MAX_PRE = 4096                         # ``pre``, ``post`` at most
+MAX_N = 1 << 24                        # outputs of a synthesised clip at most
+MAX_SPECS = 1 << 20                    # specs per call of ``synthesize``
+MAX_AMP_Q = 1 << 16                    # ``amp_q`` at most: 256 bytes
+MAX_NOISE_Q = 1 << 20                  # ``noise_q`` at most: sigma of 73.9 bytes
+FULL_SCALE = 127.6                     # bytes per unit of ``synth.synth_bursts``' amplitude and noise
+NOISE_SIGMA = math.sqrt(16 * 65535 / 12.0) / 2 ** 22     # sigma in bytes per unit of ``noise_q``
 REPLAYED = 32                          # ``flags`` bit 5: a row of the clip decoder, ``first`` is the job's index
 MAX_SPAN = 2048                        # ``tau_hi - tau_lo`` at most
 MAX_JOBS = 1 << 20                     # jobs per call of ``decode_jobs``
@@ -115,6 +137,105 @@ def drop_repeats(records: np.ndarray, recording: np.ndarray, symbol_length: int)
     return np.asarray(keep, np.int64)
 
 
+def _per_clip(value, n, what, dtype=np.float64):
+    a = np.asarray(value, dtype)
+    if a.ndim > 1 or (a.ndim == 1 and a.size != n):
+        raise ValueError(f"{what}: one value, or one per clip")
+    return np.broadcast_to(a, (n,))
+
+
+def burst_specs(payloads, *, n, at, seed, amplitude, noise, offset_hz=0.0, lead_symbols=32, trail_symbols=8, pre=0, post=0,
+                phase0=None, count=None, symbol_length=14, bit_rate=19200, if_hz=None):
+    """``(specs, tau)``: one spec (``SPEC_DTYPE``) per payload - on-air bytes, as ``synth.make_packet`` gives them (a list of
+    bytes or hex strings, or a uint8 array [clips, bytes]) - for clips
+    of ``n`` outputs at consecutive multiples of 8 of a pool, each with ``synth.synth_bursts``' burst: ``lead_symbols``
+    alternating symbols 1 0 1 0 .., the payload's bits MSB first, ``trail_symbols`` zeros, at ``if_hz + offset_hz`` +- a
+    quarter of the bit rate, with ``pre`` / ``post`` outputs of plain carrier around them.  The lead-in begins at output
+    ``at`` of the clip (may lie outside it); ``tau`` (int64) is where the decoder reports the packet: the last output of the
+    payload's first symbol, ``at + (lead_symbols + 1) symbol_length - 1``.  ``amplitude`` and ``noise`` (sigma per
+    component) are in ``synth_bursts``' units, full scale ``FULL_SCALE`` bytes.  ``seed``: an integer - the clips' 64-bit
+    noise seeds and, with ``phase0=None``, their start phases are drawn from ``numpy.random.default_rng(seed)`` - or an
+    array of one seed per clip.  ``at``, ``offset_hz``, ``amplitude``, ``noise``, ``phase0``: one value, or one per clip.
+    ``payloads=None``: ``count`` noise-only clips (no burst, amplitude 0).  ``if_hz``: default ``-out_rate // 4``, the
+    channelizer's.  ValueError for what ``rd_cs_check_specs`` would refuse."""
+    sl = int(symbol_length)
+    out_rate = int(bit_rate) * sl
+    if payloads is None:
+        if count is None or int(count) < 1:
+            raise ValueError("noise-only clips: give their count")
+        k, rows = int(count), None
+        lead_symbols = trail_symbols = 0
+        amplitude = 0.0
+    else:
+        if isinstance(payloads, np.ndarray) and payloads.dtype == np.uint8 and payloads.ndim == 2:
+            rows = payloads                                   # [clips, bytes]
+        else:
+            rows = [bytes.fromhex(p) if isinstance(p, str) else bytes(p) for p in payloads]
+            if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+                raise ValueError("payloads: at least one, all of one length")
+            rows = np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), -1)
+        k = int(rows.shape[0])
+    if not 1 <= k <= MAX_SPECS:
+        raise ValueError(f"{k} clips, not 1 .. {MAX_SPECS}")
+    n, pre, post = int(n), int(pre), int(post)
+    n_sym = 0 if rows is None else int(lead_symbols) + 8 * int(rows.shape[1]) + int(trail_symbols)
+    if not 1 <= n <= MAX_N or not 0 <= pre <= MAX_PRE or not 0 <= post <= MAX_PRE or sl < 1:
+        raise ValueError(f"n in 1 .. {MAX_N}, pre and post in 0 .. {MAX_PRE}, symbol_length >= 1")
+    if int(lead_symbols) < 0 or int(trail_symbols) < 0 or n_sym > MAX_SYM:
+        raise ValueError(f"a burst of {n_sym} symbols, at most {MAX_SYM}")
+    at_a = _per_clip(at, k, "at", np.int64)
+    if np.any(np.abs(at_a) > 2 ** 30):
+        raise ValueError("at: -2**30 .. 2**30")
+    amp_q = np.rint(_per_clip(amplitude, k, "amplitude") * (FULL_SCALE * 256.0))
+    noise_q = np.rint(_per_clip(noise, k, "noise") * (FULL_SCALE / NOISE_SIGMA))
+    if np.any(amp_q < 0) or np.any(amp_q > MAX_AMP_Q) or np.any(noise_q < 0) or np.any(noise_q > MAX_NOISE_Q):
+        raise ValueError(f"amplitude in 0 .. {MAX_AMP_Q / 256 / FULL_SCALE:.3f}, noise in 0 .. {MAX_NOISE_Q * NOISE_SIGMA / FULL_SCALE:.3f}")
+    centre = float(-out_rate // 4 if if_hz is None else if_hz)
+    f_c = np.rint((centre + _per_clip(offset_hz, k, "offset_hz")) / out_rate * 2.0 ** 32).astype(np.int64)
+    seeds = np.asarray(seed)
+    rng = None
+    if seeds.ndim == 0:
+        rng = np.random.default_rng(int(seed))
+        seeds = rng.integers(0, 2 ** 64, k, dtype=np.uint64)
+    elif seeds.shape != (k,):
+        raise ValueError("seed: an integer, or one seed per clip")
+    if phase0 is None:
+        ph = (rng or np.random.default_rng(0)).integers(0, 2 ** 32, k, dtype=np.uint64)
+    else:
+        ph = _per_clip(phase0, k, "phase0", np.int64) % 2 ** 32
+    specs = np.zeros(k, SPEC_DTYPE)
+    specs["offset"] = np.arange(k, dtype=np.uint64) * np.uint64((n + 7) // 8 * 8)
+    specs["seed"] = seeds.astype(np.uint64)
+    specs["n"], specs["at"], specs["phase0"] = n, at_a, ph.astype(np.uint32)
+    specs["f_c"] = ((f_c + 2 ** 31) % 2 ** 32 - 2 ** 31).astype(np.int32)
+    specs["f_d"] = int(round(2.0 ** 32 / (4 * sl))) if rows is not None else 0
+    specs["amp_q"], specs["noise_q"] = amp_q.astype(np.uint32), noise_q.astype(np.uint32)
+    specs["n_sym"], specs["pre"], specs["post"] = n_sym, pre, post
+    if rows is not None:
+        sym = np.zeros((k, MAX_SYM), np.uint8)
+        sym[:, 0:int(lead_symbols):2] = 1
+        sym[:, int(lead_symbols): int(lead_symbols) + 8 * int(rows.shape[1])] = np.unpackbits(rows, axis=1)
+        specs["bits"] = np.packbits(sym, axis=1)
+    return specs, at_a + (int(lead_symbols) + 1) * sl - 1
+
+
+def centred_jobs(specs, tau, span: int = 64, corr=(0, 0), ident: int = ANY_ID) -> np.ndarray:
+    """One job (``CLIP_JOB_DTYPE``) per spec over ``tau - span // 2 .. tau - span // 2 + span``, the planted position in the
+    middle; ``corr``: one direction for all, or one ``(re, im)`` per spec; ``channel`` is the spec's index modulo 2**31."""
+    specs = np.asarray(specs, SPEC_DTYPE).reshape(-1)
+    span = int(span)
+    if not 0 <= span <= MAX_SPAN:
+        raise ValueError(f"span in 0 .. {MAX_SPAN}")
+    c = np.broadcast_to(np.asarray(corr, np.int64), (specs.size, 2))
+    jobs = np.zeros(specs.size, CLIP_JOB_DTYPE)
+    jobs["offset"], jobs["n"], jobs["id"] = specs["offset"], specs["n"], int(ident)
+    jobs["tau_lo"] = np.asarray(tau, np.int64) - span // 2
+    jobs["tau_hi"] = jobs["tau_lo"] + span
+    jobs["corr_re"], jobs["corr_im"] = c[:, 0], c[:, 1]
+    jobs["channel"] = np.arange(specs.size) % 2 ** 31
+    return jobs
+
+
 def _per_recording(value, n, what):
     if value is None:
         return [None] * n
@@ -163,6 +284,34 @@ class ClipDecoder:
         self.pool_outputs = 0
         _lib.check(_lib.lib().rd_clips_upload(self._h, a.ctypes.data, a.nbytes))
         self.pool_outputs = a.size // 2
+
+    def synthesize(self, specs, pool_outputs: Optional[int] = None) -> None:
+        """Fill the device pool from ``specs`` (``SPEC_DTYPE``, ascending and apart) with no host bytes: a pool of
+        ``pool_outputs`` outputs - default: the last clip's end rounded up to 8 - in which every byte outside a clip is 0.
+        It takes the place of an uploaded pool.  ValueError for what the library refuses; the pool before stays then."""
+        s = np.ascontiguousarray(specs, SPEC_DTYPE).reshape(-1)
+        if pool_outputs is None:
+            pool_outputs = (int(s["offset"][-1]) + int(s["n"][-1]) + 7) // 8 * 8 if s.size else 0
+        pool_outputs = int(pool_outputs)
+        if not 0 <= pool_outputs < 2 ** 64:
+            raise ValueError("pool_outputs: 0 .. 2**64 - 1")
+        rc = _lib.lib().rd_clips_synth(self._h, s.ctypes.data, int(s.size), pool_outputs)
+        if rc != _lib.RD_OK and rc != _lib.RD_ERR_ARG:
+            self.pool_outputs = 0                             # (a refusal touched nothing; a device error leaves no pool)
+        _lib.check(rc)
+        self.pool_outputs = pool_outputs
+
+    def download(self) -> np.ndarray:
+        """The pool as the device holds it (uint8, 2 pool_outputs), uploaded or synthesised.  RuntimeError without one."""
+        out = np.empty(2 * max(int(self.pool_outputs), 1), np.uint8)
+        _lib.check(_lib.lib().rd_clips_download(self._h, out.ctypes.data, 2 * int(self.pool_outputs)))
+        return out
+
+    def synth_ms(self) -> float:
+        """The device time of the last ``synthesize`` - the zeroing of the pool and the kernel -, by device events, in ms."""
+        ms = C.c_float()
+        _lib.check(_lib.lib().rd_clips_synth_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def decode_jobs(self, jobs, max_flips: int = 0, narrow: bool = False, soft: bool = False) -> Replay:
         """One launch over ``jobs`` (``CLIP_JOB_DTYPE``) on the uploaded pool, under one form.  ValueError for a job or a
