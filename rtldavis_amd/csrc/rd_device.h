@@ -185,8 +185,10 @@ __device__ __forceinline__ void rd_rssi_f64(const View &v, long origin, const rd
     if (lane == 0) RD_RSSI_OF_SUMS_F64(noise, sig, ns, pe, q, rssi, snr);
 }
 
-// uint8 input: the window means are evaluated in fp32 (|f|^2 to ~1e-6 relative, 4e-6 dB; the
-// tolerance on RSSI/SNR is 1e-3 dB).  Each lane takes a contiguous slice of the window so the
+// uint8 input: the window means are evaluated in fp32; the tolerance on RSSI/SNR is 1e-3 dB.  Measured against
+// the float64 oracle (profiles/rssi_windows.txt): at most 1e-5 dB on noise, random and clipped bytes, and 2.7e-5 dB on a
+// window of constant bytes 127, where |f|^2 = -81.4 dB is what remains of 2 c0 - 2 c2 + c4 after cancellation and the
+// float32 taps' own rounding shows.  Each lane takes a contiguous slice of the window so the
 // nine-sample FIR history slides through registers (15 conversions for 7 outputs).
 // One pass of the RSSI window for a wave: lane handles PER outputs from window index j0.
 // PH0 = phase (index mod 4) of the first sample it reads - wave-uniform because every lane's
@@ -238,7 +240,11 @@ __device__ __forceinline__ void rd_rssi_pass(const rd_stream_view &v, int n0, in
 // 32 columns in rd_mfma.h's formulation (six MFMAs, exact; rd_demod_mfma.hip: rd_mf_block) instead of 144 fp32
 // fma per lane.  Column n covers outputs A + 16 n + 1 .. A + 16 n + 16, lane (n, h) its half h; A is the
 // window's first output rounded down to a multiple of four samples (8-byte aligned loads).  Applies when every
-// sample the 32 columns touch is a real byte of the stream; otherwise the caller's fp32 path runs.
+// sample the 32 columns touch is a real byte of the stream; otherwise the caller's fp32 path runs.  The arithmetic is
+// exact for the QUANTISED taps, which costs 2.3e-4 dB on a window of constant bytes 127 (the quantised DC response
+// differs from 2 c0 - 2 c2 + c4 by that much; a quarter of the 1e-3 dB tolerance, the worst legal input) and at most
+// 6e-6 dB on anything else (profiles/rssi_windows.txt).  In the batch path only the condition on the stream's end can
+// fail (Davis: the last call from q = B - 282 on): tests/rssi_window_cases.py.
 typedef _Float16 rd_k_h8 __attribute__((ext_vector_type(8)));
 typedef float rd_k_f16v __attribute__((ext_vector_type(16)));
 // (static: k_rssi_u8 and k_tail live in different files and the library has no relocatable device code - 6 KiB in each)
@@ -334,8 +340,9 @@ __device__ __forceinline__ void rd_rssi_finish(float noise, float sig, int ns, i
     }
 }
 
-// uint8 input: the window means are evaluated in fp32 (|f|^2 to ~1e-6 relative; 10*log10 through
-// v_log_f32, ~3e-6 dB; the tolerance on RSSI/SNR is 1e-3 dB).
+// uint8 input: the window means are evaluated in fp32 and 10*log10 goes through v_log_f32; the tolerance on
+// RSSI/SNR is 1e-3 dB.  Measured: 1e-5 dB at the most where the window holds a signal of any kind (the wave sum and
+// v_log_f32 together; the NumPy model without them is within 1e-6 dB), 2.7e-5 dB on constant bytes 127 (rd_rssi_pass).
 __device__ __forceinline__ void rd_rssi_u8(const rd_stream_view &v, long origin64, const rd_devcfg &cfg, long q64,
                                            int lane, double &rssi, double &snr) {
     const int origin = (int)origin64, q = (int)q64;
