@@ -1,29 +1,36 @@
-// rd_burst_common.h - what the per-chunk burst kernels share: k_chan_burst_decode (rd_burst_decode.hip, "decode"),
-// k_chan_burst_expect (rd_burst_expect.hip, "expect"), k_chan_burst_search (rd_burst_search.hip, "search") and
-// k_chan_burst_quality (rd_burst_quality.hip, "quality").  The definition of every step: include/rtldavis_hip.h, BURST DECODE.
+// rd_burst_common.h - what the burst kernels share: k_chan_burst_decode (rd_burst_decode.hip, "decode"),
+// k_chan_burst_expect (rd_burst_expect.hip, "expect"), k_chan_burst_search (rd_burst_search.hip, "search"),
+// k_chan_burst_quality (rd_burst_quality.hip, "quality") and k_clip_decode (rd_clip_decode.hip, "clip decode").  The
+// definition of every step: include/rtldavis_hip.h, BURST DECODE.
 //
 // Device phases.  Each is one step of a kernel for a whole workgroup of RD_BURST_THREADS; it takes the LDS arrays it works
 // on as pointers and its geometry as plain values - ranges, pointers, an id to match, never which kernel calls it.  The
 // __shared__ arrays are declared by the kernels, which keep their own LDS budgets.  All forced inline: a kernel is
 // compiled as if it held the phases itself, and the pointers keep their LDS address space.  No phase ends in a barrier
 // unless it says so.
-//   rd_bd_syndrome_table   E[k] of the repair into LDS                                  decode, expect
+//   rd_bd_syndrome_table   E[k] of the repair into LDS                                  decode, expect, clip decode
 //   rd_bd_load_bytes       region bytes -> LDS, 16-byte vectors, seam into chunk k-1    decode, expect, quality, clip decode
-//   rd_bd_grid_choice      g of step 4n: 64 centres, a fixed tree of shuffles           decode, expect, quality
-//   rd_bd_load_taps        the taps of H[g] as the two int16 pairs a product wants      decode, expect, search, quality
-//   rd_bd_fill_z16         z as int16 pairs, zeros outside zf0 .. zf1                   decode, expect, quality
-//   rd_bd_filter           y, four outputs per lane, packed 16-bit dot products         decode, expect, search
-//   rd_bd_symbol_sums      the sliding sums s[t]                                        decode, expect
-//   rd_bd_consider         one candidate tau against the lane's best so far             decode, expect
-//   rd_bd_reduce_best      the workgroup's best candidate (ends behind a barrier)       decode, expect
-//   rd_bd_packet_f         the sum of p over the winner's packet (ends behind a barrier) decode, expect
-//   rd_bd_write_record     the winner's rd_burst_msg, field by field (one thread)       decode, expect
+//   rd_bd_grid_choice      g of step 4n: 64 centres, a fixed tree of shuffles           decode, expect, clip decode, quality
+//   rd_bd_load_taps        the taps of H[g] as the two int16 pairs a product wants      decode, expect, clip decode, search, quality
+//   rd_bd_fill_z16         z as int16 pairs, zeros outside zf0 .. zf1                   decode, expect, clip decode, quality
+//   rd_bd_filter           y, four outputs per lane, packed 16-bit dot products         decode, expect, clip decode, search
+//   rd_bd_symbol_sums      the sliding sums s[t]                                        decode, expect, clip decode
+//   rd_bd_consider         one candidate tau against the lane's best so far             decode, expect, clip decode
+//   rd_bd_reduce_best      the workgroup's best candidate (ends behind a barrier)       decode, expect, clip decode
+//   rd_bd_best_in_region   the region decoder: the seven rows above in their order, with their barriers, on a region
+//                          that lies in LDS (ends behind a barrier)                     decode, expect
+//   rd_bd_packet_f         the sum of p over the winner's packet (ends behind a barrier) decode, expect, clip decode
+//   rd_bd_write_record     the winner's rd_burst_msg, field by field (one thread)       decode, expect, clip decode
+// Decode and expect reach the rows from rd_bd_grid_choice to rd_bd_reduce_best through rd_bd_best_in_region alone.  Clip
+// decode holds the same sequence itself, barriers included, for its speed's sake (its head comment says why): a change
+// to rd_bd_best_in_region is a change to k_clip_decode too.
 // The candidate test itself (steps 5, 5a, 5b, 6') is host + device code of its own: rd_burst_candidate.h.
 // The search kernel's int32-pair sums, per-position slicing and ballot ranking and the quality kernel's one-output-per-lane
 // sums are other algorithms and stay in their files.
 //
-// Host side (below the phases): the sync word, the argument checks every *_launch and every rd_debug_burst_* hook makes,
-// and rd_burst_dbg, which owns what a hook allocates.
+// Host side (below the phases): the sync word, the packet's shape as the three decoders' params carry it (rd_bd_shape),
+// the ladder from (max_flips, narrow) to a kernel's <REPAIR, NARROW> form, the argument checks every *_launch and every
+// rd_debug_burst_* hook makes, and rd_burst_dbg, which owns what a hook allocates.
 #pragma once
 #include <cstring>
 #include <type_traits>
@@ -93,6 +100,24 @@ __device__ __forceinline__ bool rd_bd_better(uint32_t fa, uint64_t ma, int ta, u
     if (na != nb) return na < nb;
     return ma > mb || (ma == mb && ta < tb);
 }
+
+// The packet's shape and the repair's reach: what the params of decode, expect and clip decode have in common, filled by
+// rd_bd_shape_of (host side, below)
+struct rd_bd_shape {
+    int sl, n_sym;             // SL, N
+    uint32_t sync;             // the 16 sync symbols, the first in bit 15
+    int max_flips;             // R (the <true, *> forms alone read it)
+};
+
+// The work arrays of rd_bd_best_in_region, declared by the kernel: s (and z16 in its place before s is live), the waves'
+// slots of the reduction and, for the forms that read them, E and the waves' flips (REPAIR), y and the taps (NARROW)
+struct rd_bd_work {
+    int64_t *s_s;
+    uint64_t *s_m;
+    int *s_t;
+    const uint16_t *s_E;
+    uint32_t *s_f, *s_y, *s_hA, *s_hB;
+};
 
 // ------------------------------------------------------------------------------------------
 // phases
@@ -269,6 +294,46 @@ __device__ __forceinline__ void rd_bd_reduce_best(uint32_t &best_f, uint64_t &be
     }
 }
 
+// The region decoder.  The region t0 .. t0 + len - 1 lies in LDS, output L0 + j at zl[j] (L0 <= t0, behind a barrier): the
+// workgroup's best candidate among tau = t0 + i, SL <= i < len - SL (N - 1), tau >= tau_min (INT32_MIN: no such rule),
+// that carries want_id (>= 8: any), sliced around (cr, ci), into every thread's best_f, best_m, best_t (INT32_MAX:
+// none).  NARROW puts step 4n in front - the filter gets the samples of zf0 .. zf1 - 1 and zeros beyond, its input lies
+// in s's place, so s is written only after z16 has been read - and returns its g (0 otherwise).  Afterwards s[t0 + i] is
+// at W.s_s[i], y at W.s_y[i].  Ends behind a barrier.
+template <bool REPAIR, bool NARROW>
+__device__ __forceinline__ int rd_bd_best_in_region(const uint16_t *zl, int L0, int t0, int len, int zf0, int zf1, int32_t cr, int32_t ci,
+                                                    const rd_bd_shape &S, uint32_t want_id, int tau_min,
+                                                    const uint32_t *__restrict__ nb_tab, const rd_bd_work &W, unsigned tid,
+                                                    uint32_t &best_f, uint64_t &best_m, int &best_t) {
+    const int SL = S.sl, N = S.n_sym;
+    const unsigned lane = tid & 63u, wave = tid >> 6;
+    int g = 0;
+    if constexpr (NARROW) {
+        const int T = 2 * SL + 5, M = SL + 2;
+        uint32_t *z16 = (uint32_t *)W.s_s;                // output t0 - M + i at word i: zeros in front of zf0 and behind zf1
+        g = rd_bd_grid_choice(nb_tab, T, cr, ci, lane);
+        rd_bd_load_taps(nb_tab, g, T, W.s_hA, W.s_hB, tid);
+        rd_bd_fill_z16(z16, zl, L0, t0 - M, len + 2 * M, zf0, zf1, tid);
+        __syncthreads();
+        rd_bd_filter(z16, len, T, W.s_hA, W.s_hB, W.s_y, tid);
+        __syncthreads();                                  // y is whole, and z16 has been read: s may be written
+    }
+    rd_bd_symbol_sums<NARROW>(zl + (t0 - L0), W.s_y, W.s_s, SL, len, cr, ci, tid);
+    __syncthreads();
+    // ---- one lane per tau = t0 + i
+    best_m = 0ull;
+    best_t = INT32_MAX;
+    best_f = 0u;
+    const int i_hi = len - SL * (N - 1);                  // i + SL (N - 1) < len
+    for (int i = SL + (int)tid; i < i_hi; i += RD_BURST_THREADS) {
+        const int tau = t0 + i;
+        if (tau < tau_min) continue;
+        rd_bd_consider<REPAIR>(W.s_s + i, SL, N, S.sync, S.max_flips, W.s_E, want_id, tau, best_f, best_m, best_t);
+    }
+    rd_bd_reduce_best<REPAIR>(best_f, best_m, best_t, W.s_f, W.s_m, W.s_t, lane, wave);
+    return g;
+}
+
 // The sum of p (p' with NARROW) over j0 <= j <= j1, the packet's N SL samples, as the four waves' partial sums in s_fr,
 // s_fi.  |.| <= 2048 x 2 x 255^2 < 2^29: int; NARROW: a lane's 8 terms of p' < 2^28, the packet's 2047 < 2^36: 64 bits
 // before the lanes are added.  Ends behind a barrier.
@@ -345,6 +410,23 @@ static inline uint32_t rd_bd_sync_word(const rd_config *cfg) {
     uint32_t sync = 0u;
     for (int i = 0; i < 16; i++) sync = (sync << 1) | (cfg->preamble[i] ? 1u : 0u);
     return sync;
+}
+
+static inline rd_bd_shape rd_bd_shape_of(const rd_config *cfg, int max_flips) {
+    return {cfg->symbol_length, cfg->packet_symbols, rd_bd_sync_word(cfg), max_flips};
+}
+
+// The form ladder: f(std::bool_constant<REPAIR>(), std::bool_constant<NARROW>()) for the form the two switches ask for -
+// f launches its kernel's <REPAIR, NARROW> instantiation and the site checks hipGetLastError behind it
+template <typename F>
+static inline void rd_bd_with_form(bool repair, bool narrow, F &&f) {
+    if (!narrow) {
+        if (!repair) f(std::false_type(), std::false_type());
+        else f(std::true_type(), std::false_type());
+    } else {
+        if (!repair) f(std::false_type(), std::true_type());
+        else f(std::true_type(), std::true_type());
+    }
 }
 
 // The argument rule of a launch on a channelized chunk, in this order: max_flips, the pointers, the configuration

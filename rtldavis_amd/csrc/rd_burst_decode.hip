@@ -22,10 +22,10 @@
 //
 // Kernel.  One workgroup of 256 threads per channel, the channel's runs one after the other (the loop is bounded by the
 // record places, every inner loop by the region); thread 0 fetches a run's record with system-scope loads from the burst
-// slot where k_chan_bursts, earlier on the same stream, wrote it.  Per run the phases of rd_burst_common.h in order: the
-// region's bytes (t0 and the chunk boundary are multiples of 128), the sliding sums into s (int64, 48 KiB for the longest
-// region, 32 + 16 windows; the bytes 12 KiB), one lane per tau - all but a few leave at the sync word -, the reduction,
-// and the winner's record, completed by the whole workgroup and written by thread 0.
+// slot where k_chan_bursts, earlier on the same stream, wrote it.  Per run: the region's bytes (t0 and the chunk boundary
+// are multiples of 128; 12 KiB for the longest region, 32 + 16 windows), the region decoder of rd_burst_common.h (s is
+// int64, 48 KiB; one lane per tau - all but a few leave at the sync word), and the winner's record, completed by the whole
+// workgroup and written by thread 0.
 // Output: channel c owns cap = rd_bu_cap(nW) record places, as in the burst slot, and one header (n_msgs, long_runs,
 // chunk): a run gives at most one record, so there is no overflow and no ticket; the channel's records are its first
 // n_msgs places, in run order.  All stores are plain vector stores into the mapped host slot of the chunk's parity.  With
@@ -57,12 +57,10 @@ static_assert(RD_BD_MAX_REGION * 14 + 2 * 8 * RD_BD_DATA_BYTES + 2 * 4 * RD_BD_N
               "narrow: y (4 bytes per output) and the taps beside the rest, under gfx950's 160 KiB of LDS");
 
 struct rd_bd_params {
-    int sl, n_sym;             // SL, N
-    uint32_t sync;             // the 16 sync symbols, the first in bit 15
+    rd_bd_shape shape;
     int look;                  // LOOK
     int have_prev;
     unsigned n_win, cap;
-    int max_flips;             // R (k_chan_burst_decode<true, *> alone reads it)
     uint64_t clock, seq;
 };
 
@@ -84,19 +82,20 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_decode(const ui
     __shared__ uint32_t s_f[RD_BURST_THREADS / 64];      // (REPAIR) the waves' flips
     __shared__ uint32_t s_y[RD_BD_MAX_REGION];           // (NARROW) y[t0 + i] at i: re in the low half, im in the high one
     __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // (NARROW) H[g][kk - M] as (re, -im) and (im, re)
+    const rd_bd_work W = {s_s, s_m, s_t, s_E, s_f, s_y, s_hA, s_hB};
     const int c = (int)blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     const uint8_t *src = cur + (size_t)c * ch_stride;
     const uint8_t *src_prev = prev ? prev + (size_t)c * ch_stride : nullptr;
     const rd_burst *mine = runs + (size_t)c * P.cap;
     rd_burst_msg *out = recs + (size_t)c * P.cap;
     const uint16_t *zw = (const uint16_t *)s_z;           // output t0 + i: I in the low byte, Q in the high one
     if (tid == 0u) s_run[0] = rd_bd_sys_load(&floor[c].n_bursts);
-    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.n_sym, tid);
+    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.shape.n_sym, tid);
     __syncthreads();
     uint32_t n_runs = s_run[0];
     if (n_runs > P.cap) n_runs = P.cap;                   // (k_chan_bursts never writes more)
-    const int SL = P.sl, N = P.n_sym, need = N * SL + 1;
+    const int SL = P.shape.sl, N = P.shape.n_sym, need = N * SL + 1;
     uint32_t n_msgs = 0u, n_long = 0u;
     for (uint32_t r = 0; r < n_runs; r++) {
         __syncthreads();                                  // the run before has been read out of LDS
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_decode(const ui
         const int t1 = RD_BU_WINDOW * (int)(first + windows);
         const int len = t1 - t0;                          // a multiple of 128, <= RD_BD_MAX_REGION
         if (len < need || len > RD_BD_MAX_REGION) continue;
-        int nb_sh = 0, nb_g = 0;                          // (NARROW) sh and g of step 4n
+        int nb_sh = 0;                                    // (NARROW) sh of step 4n
         if constexpr (NARROW) {
             const int64_t mr = cr64 < 0 ? -cr64 : cr64, mi = ci64 < 0 ? -ci64 : ci64;
             const int bl = 64 - __clzll((long long)(mr > mi ? mr : mi));   // (not both 0: at least 1)
@@ -131,29 +130,13 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_decode(const ui
         const int32_t cr = NARROW ? (int32_t)(cr64 >> nb_sh) : (int32_t)cr64, ci = NARROW ? (int32_t)(ci64 >> nb_sh) : (int32_t)ci64;
         rd_bd_load_bytes(s_z, src, src_prev, t0, t1, (long)n_out, tid);
         __syncthreads();
-        if constexpr (NARROW) {
-            const int T = 2 * SL + 5, M = SL + 2;
-            uint32_t *z16 = (uint32_t *)s_s;              // output t0 - M + i at word i: zeros in front of the region and behind it
-            nb_g = rd_bd_grid_choice(nb_tab, T, cr, ci, lane);
-            rd_bd_load_taps(nb_tab, nb_g, T, s_hA, s_hB, tid);
-            rd_bd_fill_z16(z16, zw, t0, t0 - M, len + 2 * M, t0, t1, tid);
-            __syncthreads();
-            rd_bd_filter(z16, len, T, s_hA, s_hB, s_y, tid);
-            __syncthreads();                              // y is whole, and z16 has been read: s may be written
-        }
-        rd_bd_symbol_sums<NARROW>(zw, s_y, s_s, SL, len, cr, ci, tid);
-        __syncthreads();
-        // ---- one lane per tau = t0 + i
-        uint64_t best_m = 0ull;
-        int best_t = INT32_MAX;
-        uint32_t best_f = 0u;
-        const int i_hi = len - SL * (N - 1);              // i + SL (N - 1) < len
-        for (int i = SL + (int)tid; i < i_hi; i += RD_BURST_THREADS) {
-            const int tau = t0 + i;
-            if (tau + SL * (N - 1) < 0) continue;         // the packet ended in the chunk before: reported there
-            rd_bd_consider<REPAIR>(s_s + i, SL, N, P.sync, P.max_flips, s_E, 8u, tau, best_f, best_m, best_t);
-        }
-        rd_bd_reduce_best<REPAIR>(best_f, best_m, best_t, s_f, s_m, s_t, lane, wave);
+        // ---- the region decoder: the filter sees zeros outside the region; any id; tau + SL (N - 1) >= 0 - a packet that
+        // ended in the chunk before was reported there
+        uint64_t best_m;
+        int best_t;
+        uint32_t best_f;
+        const int nb_g = rd_bd_best_in_region<REPAIR, NARROW>(zw, t0, t0, len, t0, t1, cr, ci, P.shape, 8u, -SL * (N - 1), nb_tab, W, tid,
+                                                              best_f, best_m, best_t);
         if (best_t == INT32_MAX) continue;                // (uniform: every thread read the same four)
         // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
         const int i0 = best_t - t0;
@@ -223,33 +206,23 @@ int rd_burst_decode_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     if (rc) return rc;
     const size_t n_win = n_out / RD_BU_WINDOW;
     rd_bd_params P;
-    P.sl = cfg->symbol_length;
-    P.n_sym = cfg->packet_symbols;
-    P.sync = rd_bd_sync_word(cfg);
+    P.shape = rd_bd_shape_of(cfg, max_flips);
     P.look = RD_BU_WINDOW * rd_bd_look_windows(cfg);
     P.have_prev = chan_prev ? 1 : 0;
     P.n_win = (unsigned)n_win;
     P.cap = (unsigned)rd_bu_cap(n_win);
     P.clock = clock;
     P.seq = seq;
-    P.max_flips = max_flips;
     const uint8_t *bs = (const uint8_t *)burst_slot;
     uint8_t *base = (uint8_t *)slot;
     const rd_burst *runs = (const rd_burst *)bs;
     const rd_burst_floor *floor = (const rd_burst_floor *)(bs + rd_bu_floor_offset(n_ch, n_win));
     rd_burst_msg *recs = (rd_burst_msg *)base;
     rd_bd_header *hdr = (rd_bd_header *)(base + rd_bd_header_offset(n_ch, n_win));
-#define RD_BD_LAUNCH(REPAIR, NARROW)                                                                                          \
-    hipLaunchKernelGGL((k_chan_burst_decode<REPAIR, NARROW>), dim3((unsigned)n_ch), dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, \
-                       out_stride, n_out, P, runs, floor, recs, hdr, narrow_tab)
-    if (!narrow_tab) {
-        if (max_flips == 0) RD_BD_LAUNCH(false, false);
-        else RD_BD_LAUNCH(true, false);
-    } else {
-        if (max_flips == 0) RD_BD_LAUNCH(false, true);
-        else RD_BD_LAUNCH(true, true);
-    }
-#undef RD_BD_LAUNCH
+    rd_bd_with_form(max_flips != 0, narrow_tab != nullptr, [&](auto repair, auto narrow) {
+        hipLaunchKernelGGL((k_chan_burst_decode<decltype(repair)::value, decltype(narrow)::value>), dim3((unsigned)n_ch),
+                           dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, out_stride, n_out, P, runs, floor, recs, hdr, narrow_tab);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_decode: %s", hipGetErrorString(e));
     return RD_OK;

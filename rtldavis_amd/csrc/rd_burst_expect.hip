@@ -12,8 +12,8 @@
 // 4096 outputs; t0 is no multiple of 8, so the bytes are loaded from L0 = the filter's first output (t0 without the
 // filter) rounded DOWN to 8 up to its last rounded up - a 16-byte vector still lies in one chunk -, and everything
 // behind the load indexes from t0: the outputs loaded in front of it enter neither p nor, beyond zf0 .. zf1, the
-// filter, which gets the real samples of zf0 .. zf1 where a run of k_chan_burst_decode has zeros.  Then the phases of
-// rd_burst_common.h with one lane per tau over tau_a .. tau_b only.
+// filter, which gets the real samples of zf0 .. zf1 where a run of k_chan_burst_decode has zeros.  Then the region
+// decoder of rd_burst_common.h, one lane per tau over tau_a .. tau_b only, and the winner's record.
 // LDS: s (int64, 32 KiB), the bytes (8.25 KiB), y (16 KiB, narrow only) - less than the decode kernel's.  Plain vector
 // stores into the mapped slot, no atomics.
 #include <type_traits>
@@ -29,12 +29,10 @@ static_assert((RD_BX_LEN + RD_BD_NB_MAX_T - 1) * 4 <= RD_BX_LEN * 8, "the padded
 static_assert(sizeof(rd_bx_header) == 16 && sizeof(rd_bx_entry) == 32, "the slot layout of rd_bx_* (rd_internal.h)");
 
 struct rd_bx_params {
-    int sl, n_sym;             // SL, N
-    uint32_t sync;             // the 16 sync symbols, the first in bit 15
+    rd_bd_shape shape;
     int look;                  // LOOK
     int have_prev;
     int n_ch;
-    int max_flips;             // R (the <true, *> forms alone read it)
     uint64_t clock, seq;
 };
 
@@ -54,8 +52,9 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_expect(const ui
     __shared__ uint32_t s_f[RD_BURST_THREADS / 64];      // (REPAIR) the waves' flips
     __shared__ uint32_t s_y[RD_BX_LEN];                  // (NARROW) y[t0 + i] at i: re in the low half, im in the high one
     __shared__ uint32_t s_hA[RD_BD_NB_MAX_T], s_hB[RD_BD_NB_MAX_T];   // (NARROW) H[g][kk - M] as (re, -im) and (im, re)
+    const rd_bd_work W = {s_s, s_m, s_t, s_E, s_f, s_y, s_hA, s_hB};
     const int x = (int)blockIdx.x;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     if (tid == 0u) {                                     // one thread crosses the bus, the workgroup takes it from LDS
         s_ent[0] = rd_bd_sys_load(&tab[x].channel);
         s_ent[1] = (int32_t)rd_bd_sys_load(&tab[x].id);
@@ -64,12 +63,12 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_expect(const ui
         s_ent[4] = rd_bd_sys_load(&tab[x].corr_re);
         s_ent[5] = rd_bd_sys_load(&tab[x].corr_im);
     }
-    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.n_sym, tid);
+    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.shape.n_sym, tid);
     __syncthreads();
     const int c = s_ent[0], tau_a = s_ent[2], tau_b = s_ent[3];   // (workgroup-uniform from here on)
     const uint32_t want_id = (uint32_t)s_ent[1];
     const int32_t cr = s_ent[4], ci = s_ent[5];
-    const int SL = P.sl, N = P.n_sym, body = SL * (N - 1), M = SL + 2;
+    const int SL = P.shape.sl, N = P.shape.n_sym, body = SL * (N - 1), M = SL + 2;
     const int lo_lim = P.have_prev && prev ? -P.look : 0;
     const int t0 = tau_a - SL, t1 = tau_b + body + 1, len = t1 - t0;
     const int zf0 = NARROW ? max(t0 - M, lo_lim) : t0, zf1 = NARROW ? min(t1 + M, (int)n_out) : t1;
@@ -86,27 +85,12 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_chan_burst_expect(const ui
         const uint16_t *zw = zl + (t0 - L0);             // output t0 + i
         rd_bd_load_bytes(s_z, src, src_prev, L0, L1, (long)n_out, tid);   // (L0 < 0 only with lo_lim < 0: there is a chunk before)
         __syncthreads();
-        int nb_g = 0;                                     // (NARROW) g of step 4n
-        if constexpr (NARROW) {
-            const int T = 2 * SL + 5;
-            uint32_t *z16 = (uint32_t *)s_s;              // output t0 - M + i at word i
-            nb_g = rd_bd_grid_choice(nb_tab, T, cr, ci, lane);
-            rd_bd_load_taps(nb_tab, nb_g, T, s_hA, s_hB, tid);
-            rd_bd_fill_z16(z16, zl, L0, t0 - M, len + 2 * M, zf0, zf1, tid);
-            __syncthreads();
-            rd_bd_filter(z16, len, T, s_hA, s_hB, s_y, tid);
-            __syncthreads();                              // y is whole, and z16 has been read: s may be written
-        }
-        rd_bd_symbol_sums<NARROW>(zw, s_y, s_s, SL, len, cr, ci, tid);
-        __syncthreads();
-        // ---- one lane per tau = t0 + i, tau_a <= tau <= tau_b
-        uint64_t best_m = 0ull;
-        int best_t = INT32_MAX;
-        uint32_t best_f = 0u;
-        const int i_hi = len - body;                      // = SL + (tau_b - tau_a) + 1
-        for (int i = SL + (int)tid; i < i_hi; i += RD_BURST_THREADS)
-            rd_bd_consider<REPAIR>(s_s + i, SL, N, P.sync, P.max_flips, s_E, want_id, t0 + i, best_f, best_m, best_t);
-        rd_bd_reduce_best<REPAIR>(best_f, best_m, best_t, s_f, s_m, s_t, lane, wave);
+        // ---- the region decoder: one lane per tau = t0 + i, tau_a <= tau <= tau_b, under the entry's id
+        uint64_t best_m;
+        int best_t;
+        uint32_t best_f;
+        const int nb_g = rd_bd_best_in_region<REPAIR, NARROW>(zl, L0, t0, len, zf0, zf1, cr, ci, P.shape, want_id, INT32_MIN, nb_tab, W, tid,
+                                                              best_f, best_m, best_t);
         found = best_t != INT32_MAX;                      // (uniform: every thread read the same four)
         if (found) {
             // ---- the record: sum of p over the packet's N SL samples tau - SL + 1 .. tau + SL (N - 1)
@@ -163,30 +147,20 @@ int rd_burst_expect_launch(const rd_config *cfg, const uint8_t *chan_out, const 
     if (rc) return rc;
     if (n < 1 || n > RD_BX_MAX) return rd_fail_msg(RD_ERR_ARG, "burst expect: %d expectations, not 1 .. %d", n, RD_BX_MAX);
     rd_bx_params P;
-    P.sl = cfg->symbol_length;
-    P.n_sym = cfg->packet_symbols;
-    P.sync = rd_bd_sync_word(cfg);
+    P.shape = rd_bd_shape_of(cfg, max_flips);
     P.look = RD_BU_WINDOW * rd_bd_look_windows(cfg);
     P.have_prev = chan_prev ? 1 : 0;
     P.n_ch = n_ch;
-    P.max_flips = max_flips;
     P.clock = clock;
     P.seq = seq;
     uint8_t *base = (uint8_t *)slot_dev;
     rd_burst_msg *recs = (rd_burst_msg *)base;
     rd_bx_header *hdr = (rd_bx_header *)(base + RD_BX_HEADER_OFFSET);
     const rd_bx_entry *tab = (const rd_bx_entry *)(base + RD_BX_ENTRY_OFFSET);
-#define RD_BX_LAUNCH(REPAIR, NARROW)                                                                                          \
-    hipLaunchKernelGGL((k_chan_burst_expect<REPAIR, NARROW>), dim3((unsigned)n), dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, \
-                       out_stride, n_out, P, tab, recs, hdr, narrow_tab)
-    if (!narrow_tab) {
-        if (max_flips == 0) RD_BX_LAUNCH(false, false);
-        else RD_BX_LAUNCH(true, false);
-    } else {
-        if (max_flips == 0) RD_BX_LAUNCH(false, true);
-        else RD_BX_LAUNCH(true, true);
-    }
-#undef RD_BX_LAUNCH
+    rd_bd_with_form(max_flips != 0, narrow_tab != nullptr, [&](auto repair, auto narrow) {
+        hipLaunchKernelGGL((k_chan_burst_expect<decltype(repair)::value, decltype(narrow)::value>), dim3((unsigned)n),
+                           dim3(RD_BURST_THREADS), 0, st, chan_out, chan_prev, out_stride, n_out, P, tab, recs, hdr, narrow_tab);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_chan_burst_expect: %s", hipGetErrorString(e));
     return RD_OK;

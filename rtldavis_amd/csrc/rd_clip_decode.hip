@@ -16,7 +16,10 @@
 // Own direction (corr = (0, 0)): every thread sums p over its outputs of t0 < t < t1, a fixed tree of shuffles adds the
 // lanes and the four waves' sums meet in LDS - integers, no atomics; then the shift of step 4n.
 // Then the phases of rd_burst_common.h with one lane per tau over tau_a .. tau_b only, as in the expect kernel, and the
-// winner's N symbol sums go out as the job's soft values, one thread per symbol.
+// winner's N symbol sums go out as the job's soft values, one thread per symbol.  The kernel spells out what
+// rd_bd_best_in_region and rd_bd_packet_f<false> would do for it - the same phases, the same barriers: through them it
+// gave the same results 1 % slower in three of its four forms (profiles/burst_region_refactor.txt), and this is the
+// kernel whose time alone is a product figure (profiles/clip_replay.txt).  Keep the two in step.
 // LDS: the expect kernel's budget - s (int64, 32 KiB), the bytes (8.25 KiB), y (16 KiB, narrow only), plus 32 bytes
 // for the own direction: 41 KiB per workgroup without the filter (three workgroups on a CU's 160 KiB), 58 KiB with it
 // (two).  Plain vector stores into device memory, no atomics.
@@ -37,9 +40,7 @@ static_assert(sizeof(rd_clip_job) == 48 && sizeof(rd_cd_header) == 16 && sizeof(
 static_assert(8 * RD_BD_DATA_BYTES <= RD_BURST_THREADS, "one thread per symbol of the soft values");
 
 struct rd_cd_params {
-    int sl, n_sym;             // SL, N
-    uint32_t sync;             // the 16 sync symbols, the first in bit 15
-    int max_flips;             // R (the <true, *> forms alone read it)
+    rd_bd_shape shape;
     uint64_t pool_outputs;     // outputs the pool holds
 };
 
@@ -62,8 +63,8 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_clip_decode(const uint8_t 
     const unsigned x = blockIdx.x;
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const rd_clip_job J = jobs[x];                       // (a workgroup-uniform address: every thread gets the same job)
-    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.n_sym, tid);   // (read behind the barrier that follows the load)
-    const int SL = P.sl, N = P.n_sym, body = SL * (N - 1), M = SL + 2;
+    if constexpr (REPAIR) rd_bd_syndrome_table(s_E, P.shape.n_sym, tid);   // (read behind the barrier that follows the load)
+    const int SL = P.shape.sl, N = P.shape.n_sym, body = SL * (N - 1), M = SL + 2;
     // The job's geometry, in 64 bits until rd_cd_check_jobs' rules have been checked again: a job that fails is idle.
     const int64_t n = (int64_t)J.n;
     const int64_t a64 = J.tau_lo > SL ? (int64_t)J.tau_lo : (int64_t)SL;
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(RD_BURST_THREADS) void k_clip_decode(const uint8_t 
         uint32_t best_f = 0u;
         const int i_hi = len - body;                      // = SL + (tau_b - tau_a) + 1
         for (int i = SL + (int)tid; i < i_hi; i += RD_BURST_THREADS)
-            rd_bd_consider<REPAIR>(s_s + i, SL, N, P.sync, P.max_flips, s_E, J.id, t0 + i, best_f, best_m, best_t);
+            rd_bd_consider<REPAIR>(s_s + i, SL, N, P.shape.sync, P.shape.max_flips, s_E, J.id, t0 + i, best_f, best_m, best_t);
         rd_bd_reduce_best<REPAIR>(best_f, best_m, best_t, s_f, s_m, s_t, lane, wave);
         found = best_t != INT32_MAX;                      // (uniform: every thread read the same four)
         if (found) {
@@ -281,10 +282,7 @@ extern "C" int rd_clips_decode(rd_clips *h, const rd_clip_job *jobs, int n_jobs,
     }
     if (narrow && !h->d_nb && (rc = rd_bd_narrow_upload(h->cfg.symbol_length, &h->d_nb))) return rc;
     rd_cd_params P;
-    P.sl = h->cfg.symbol_length;
-    P.n_sym = h->cfg.packet_symbols;
-    P.sync = rd_bd_sync_word(&h->cfg);
-    P.max_flips = max_flips;
+    P.shape = rd_bd_shape_of(&h->cfg, max_flips);
     P.pool_outputs = h->pool_outputs;
     int64_t *d_soft = soft ? h->d_soft : nullptr;
     // the record and header places of a job that writes none read 0
@@ -294,17 +292,10 @@ extern "C" int rd_clips_decode(rd_clips *h, const rd_clip_job *jobs, int n_jobs,
         (d_soft && hipMemsetAsync(d_soft, 0, nj * N * sizeof(int64_t), h->st) != hipSuccess) ||
         hipEventRecord(h->ev0, h->st) != hipSuccess)
         return rd_fail_msg(RD_ERR_DEVICE, "clip decode: the copy of the jobs failed");
-#define RD_CD_LAUNCH(REPAIR, NARROW)                                                                                          \
-    hipLaunchKernelGGL((k_clip_decode<REPAIR, NARROW>), dim3((unsigned)n_jobs), dim3(RD_BURST_THREADS), 0, h->st, h->d_pool, P, \
-                       h->d_jobs, h->d_recs, h->d_hdr, d_soft, h->d_nb)
-    if (!narrow) {
-        if (max_flips == 0) RD_CD_LAUNCH(false, false);
-        else RD_CD_LAUNCH(true, false);
-    } else {
-        if (max_flips == 0) RD_CD_LAUNCH(false, true);
-        else RD_CD_LAUNCH(true, true);
-    }
-#undef RD_CD_LAUNCH
+    rd_bd_with_form(max_flips != 0, narrow != 0, [&](auto repair, auto narrow_form) {
+        hipLaunchKernelGGL((k_clip_decode<decltype(repair)::value, decltype(narrow_form)::value>), dim3((unsigned)n_jobs),
+                           dim3(RD_BURST_THREADS), 0, h->st, h->d_pool, P, h->d_jobs, h->d_recs, h->d_hdr, d_soft, h->d_nb);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rd_fail_msg(RD_ERR_DEVICE, "k_clip_decode: %s", hipGetErrorString(e));
     h->kernel_ms = -1.0f;
